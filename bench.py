@@ -15,11 +15,19 @@ smoothness loss) -> backward -> (RCCL all-reduce of the gradient buckets) -> Ada
 configs[1]: resnet18, 192x640, per-GPU batch 12, fp32; `--num-layers 50 --height 320 --width 1024 --batch 8` is
 configs[2] per rank.  Weak scaling: every rank processes its own batch.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
+A plain run sets up, runs W warm-up steps, times K steps and prints ONE JSON line from rank 0 (metric, value, unit,
+higher_is_better, dtype, ms_per_step = milliseconds of one timed step, ...).  `--dump-outputs DIR` then also writes what the
+last timed step computed -- the arrays Trainer.train_step() hands its caller (outputs, losses) and the parameters Adam left
+behind -- as DIR/<name>.npy in float32, at most 64 MB in all (a fixed, seeded sample of each larger array); the inputs are
+seeded, so two builds can be compared output for output.
+
+`--full` adds the diagnostics, each measured in steps of its own after the timed region (or around it):
+  windows      -- more windows of K steps after the timed one (windows_ms_per_step, steady_state_ms_per_step);
   roofline     -- the dominant kernel of the step (Winograd fp32-MFMA convolution): SURVEY 8d algorithmic FLOPs per launch /
                   its mean duration from hipEvents on the launch stream, against the fp32 matrix peak; the HBM-bound fused
                   photometric kernels (BASELINE metric 2) the same way under roofline.photometric, backward chain as a whole;
   phases_ms    -- forward / backward / exposed gradient exchange / Adam wall split of a step (N > 1: what scaling costs);
+  N > 1        -- who is in the group, the per-bucket exchange timeline, and the check that all replicas hold the same weights;
   cpu_baseline -- the CPU oracle's full training step timed on this host's cores (N=1 only; SURVEY 8d protocol).
 
 Rehearsal switches (not measurements, flagged in the line): DC_DIST_BACKEND=gloo exchanges over gloo instead of RCCL;
@@ -114,6 +122,44 @@ def launch(args, argv):
         print("bench.py: rank exit codes %r" % rcs, file=sys.stderr)
         return bad[0] if bad[0] > 0 else 1
     return 0
+
+
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_BYTES = 60 << 20          # float32 data of all arrays (each .npy adds a header of ~128 bytes): under 64 MB in all
+
+
+def step_arrays(outputs, losses, params):
+    """name -> tensor of what one training step hands back: `outputs.*` and `losses.*` (train_step's return values, keys
+    joined with '_') and `parameters` (every trained parameter after Adam, flattened in the optimiser's order)."""
+    arrays = {}
+    for prefix, d in (("outputs", outputs), ("losses", losses)):
+        for k, v in d.items():
+            if torch.is_tensor(v):
+                name = "_".join(str(p) for p in k) if isinstance(k, tuple) else str(k)
+                arrays["%s.%s" % (prefix, "".join(c if c.isalnum() or c in "_-." else "_" for c in name))] = v
+    arrays["parameters"] = torch.cat([p.detach().reshape(-1) for p in params])
+    return arrays
+
+
+def write_outputs(folder, arrays, budget=DUMP_BYTES):
+    """DIR/<name>.npy in float32.  When all of them do not fit `budget`, every array larger than an equal share of what is
+    left keeps a fixed, seeded sample of that many elements (indices ascending; the same for the same shape in every run)."""
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    flat = {k: v.detach().float().reshape(-1).cpu() for k, v in arrays.items()}
+    cap, left, rest = None, budget // 4, len(flat)
+    if sum(v.numel() for v in flat.values()) > left:
+        for n in sorted(v.numel() for v in flat.values()):
+            if n > left // rest:
+                cap = left // rest
+                break
+            left, rest = left - n, rest - 1
+    for k in sorted(flat):
+        v, shape = flat[k], tuple(arrays[k].shape)
+        if cap is not None and v.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(v.numel(), cap, replace=False))
+            v, shape = v[torch.from_numpy(idx)], (cap,)
+        np.save(os.path.join(folder, k + ".npy"), v.numpy().reshape(shape))
 
 
 # ------------------------------------------------------------------------------------------------ CPU baseline
@@ -284,6 +330,8 @@ def rehearse(args, world, rank):
         if float((hi - lo).abs().max()) > 1e-9 * float(hi.abs().max() + 1):
             raise SystemExit("replicas diverged")
     if rank == 0:
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, step_arrays({}, {"loss": loss}, list(net.parameters())))
         print(json.dumps({"metric": "REHEARSAL (CPU stand-in step, not a measurement)", "value": round(world * args.batch * args.steps / float(dt), 3),
                           "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                           "ms_per_step": round(float(dt) / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
@@ -364,7 +412,7 @@ def run_rank(args):
     _step_ctx = tr.on_step_stream()
     _step_ctx.__enter__()
     dist_info = None
-    if world > 1:        # who is really in the group: every rank reports (rank, device ordinal, device name)
+    if world > 1 and args.full:        # who is really in the group: every rank reports (rank, device ordinal, device name)
         mine = (rank, local, torch.cuda.get_device_name(device))
         everyone = [None] * world
         dist.all_gather_object(everyone, mine)
@@ -411,7 +459,7 @@ def run_rank(args):
     for _ in range(args.warmup):
         _, losses = tr.train_step(inputs)
         loss0 = losses["loss"].detach().clone() if loss0 is None else loss0
-    if not tr.graph_enabled:                    # (event pairs cannot be part of a captured step)
+    if args.full and not tr.graph_enabled:      # (event pairs cannot be part of a captured step)
         ops.profile_enable(args.steps + 8)
         # every 7th conv launch carries an event pair (7 is coprime with the launches per step, so all layers are
         # sampled over the timed region); bracketing every launch costs ~4 % of the step
@@ -422,106 +470,118 @@ def run_rank(args):
     host_s = 0.0                                # time spent INSIDE train_step(): launch work of an eager step, one replay of a captured one
     for _ in range(args.steps):
         th = time.perf_counter()
-        _, losses = tr.train_step(inputs)
+        outputs, losses = tr.train_step(inputs)
         host_s += time.perf_counter() - th
     sync()
     dt = time.perf_counter() - t0
     loss_last = float(losses["loss"].detach())
+    if args.dump_outputs and rank == 0:         # before any other step: a captured step's outputs are rewritten by the next replay
+        write_outputs(args.dump_outputs, step_arrays(outputs, losses, tr.parameters_to_train))
     # run-to-run spread: more windows of the same K steps right after the timed one (reported, not the headline)
     windows = [dt / args.steps * 1e3]
-    for _w in range(args.windows - 1):
+    for _w in range(args.windows - 1 if args.full else 0):
         sync()
         tw = time.perf_counter()
         for _ in range(args.steps):
-            _, losses = tr.train_step(inputs)
+            outputs, losses = tr.train_step(inputs)
         sync()
         windows.append((time.perf_counter() - tw) / args.steps * 1e3)
     phase[0] = "diagnostics-after-the-timed-region"
-    del losses, _                       # drop the autograd graph before the stream layout changes below
+    del outputs, losses                 # drop the autograd graph before the stream layout changes below
     graphed = tr.graph_enabled and tr._graph is not None
     tr.graph_enabled = False            # the diagnostic steps below are eager
-    prof = ops.profile_collect()
-    ops.profile_enable(0)
-    fam_c = {k: ops.conv_profile_collect(k) for k in FAMILIES}
-    ops.conv_profile_enable(0, 1)
-
-    # ---- wall split of a step: forward / backward / exposed exchange / Adam (host-synchronised, after the timed region)
-    # per-bucket timeline of the exchange (world > 1): one pipelined eager step with event pairs around every bucket's all-reduce
-    bucket_order, bucket_offsets_ms = [], None
-    if world > 1:
-        from depthcore.ddp import bucket_timeline
-        tr.buckets.timing = True
-        _o, _l = tr.process_batch(inputs)
-        tr.buckets.zero()
-        _l["loss"].backward()
-        tr.buckets.finish()
-        tr.model_optimizer.step()
-        tr.step += 1
+    if not args.full:
+        # `dtype` names the split-operand 1x1 GEMMs only where they ran: one eager step after the timed region counts them
+        ops.conv_profile_enable(400, 1)
+        tr.train_step(inputs)
         torch.cuda.synchronize()
-        tl = bucket_timeline(tr.buckets)
-        tr.buckets.timing = False
-        bucket_order = [b for b, _, _, _ in tl]
-        bucket_offsets_ms = [{"bucket": b, "bytes": nb, "starts_ms_after_backward_start": t0, "all_reduce_ms": d} for b, nb, t0, d in tl]
-        del _o, _l
-    PH = 4
-    ph = [0.0, 0.0, 0.0, 0.0]
-    for _ in range(PH):
-        ts = [time.perf_counter()]
-
-        def mark():
-            torch.cuda.synchronize()
-            ts.append(time.perf_counter())
-        outputs, losses = tr.process_batch(inputs); mark()
-        tr.buckets.zero()
-        losses["loss"].backward(); mark()
-        tr.buckets.finish(); mark()
-        tr.model_optimizer.step(); mark()
-        tr.step += 1
-        for i in range(4):
-            ph[i] += (ts[i + 1] - ts[i]) * 1e3 / PH
-        del outputs, losses
-    packed = tr.buckets.packed
-    # what the step would pay if the data loader did NOT deliver the pixel-interleaved copies: three dc_pack_rgbx launches
-    rgbx_pack_ms = None
-    if ("color_packed", 0, 0) in inputs:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        frames = [inputs[("color", f, 0)] for f in (0, -1, 1)]
-        for _ in range(3):
-            keep = [ops.pack_rgbx(fr) for fr in frames]
-        e0.record()
-        for _ in range(20):
-            keep = [ops.pack_rgbx(fr) for fr in frames]
-        e1.record()
-        torch.cuda.synchronize()
-        rgbx_pack_ms = e0.elapsed_time(e1) / 20.0
-        del keep
-
-    # In the timed region the pose and the depth network run on two HIP streams, so a launch's event pair also spans
-    # the time it shares the GPU with a kernel of the other stream.  The kernel's own duration (what rocprofv3, which
-    # serialises dispatches, reports) is taken from SERIAL_STEPS single-stream steps run right after the timed region
-    # with an event pair around every launch.
-    SERIAL_STEPS = 3
-    if tr.opt.overlap_streams:
-        tr.opt.overlap_streams = False
-        lanes, tr.wgrad_lanes = tr.wgrad_lanes, False
-        ops.profile_enable(SERIAL_STEPS + 2)
-        ops.conv_profile_enable((SERIAL_STEPS + 1) * 400, 1)
-        for _ in range(SERIAL_STEPS):
-            tr.train_step(inputs)
-        torch.cuda.synchronize()
-        prof = ops.profile_collect()
-        fam = {k: ops.conv_profile_collect(k) for k in FAMILIES}
-        ops.profile_enable(0)
+        fam = {7: ops.conv_profile_collect(7)}
         ops.conv_profile_enable(0, 1)
-        tr.opt.overlap_streams = True
-        tr.wgrad_lanes = lanes
-        roof_src, fam_steps = "%d single-stream steps after the timed region, every launch" % SERIAL_STEPS, SERIAL_STEPS
+        packed = tr.buckets.packed
     else:
-        fam = fam_c
-        roof_src, fam_steps = "timed region, every 7th launch", args.steps * args.windows / 7.0
+        prof = ops.profile_collect()
+        ops.profile_enable(0)
+        fam_c = {k: ops.conv_profile_collect(k) for k in FAMILIES}
+        ops.conv_profile_enable(0, 1)
+
+        # ---- wall split of a step: forward / backward / exposed exchange / Adam (host-synchronised, after the timed region)
+        # per-bucket timeline of the exchange (world > 1): one pipelined eager step with event pairs around every bucket's all-reduce
+        bucket_order, bucket_offsets_ms = [], None
+        if world > 1:
+            from depthcore.ddp import bucket_timeline
+            tr.buckets.timing = True
+            _o, _l = tr.process_batch(inputs)
+            tr.buckets.zero()
+            _l["loss"].backward()
+            tr.buckets.finish()
+            tr.model_optimizer.step()
+            tr.step += 1
+            torch.cuda.synchronize()
+            tl = bucket_timeline(tr.buckets)
+            tr.buckets.timing = False
+            bucket_order = [b for b, _, _, _ in tl]
+            bucket_offsets_ms = [{"bucket": b, "bytes": nb, "starts_ms_after_backward_start": t0, "all_reduce_ms": d} for b, nb, t0, d in tl]
+            del _o, _l
+        PH = 4
+        ph = [0.0, 0.0, 0.0, 0.0]
+        for _ in range(PH):
+            ts = [time.perf_counter()]
+
+            def mark():
+                torch.cuda.synchronize()
+                ts.append(time.perf_counter())
+            outputs, losses = tr.process_batch(inputs); mark()
+            tr.buckets.zero()
+            losses["loss"].backward(); mark()
+            tr.buckets.finish(); mark()
+            tr.model_optimizer.step(); mark()
+            tr.step += 1
+            for i in range(4):
+                ph[i] += (ts[i + 1] - ts[i]) * 1e3 / PH
+            del outputs, losses
+        packed = tr.buckets.packed
+        # what the step would pay if the data loader did NOT deliver the pixel-interleaved copies: three dc_pack_rgbx launches
+        rgbx_pack_ms = None
+        if ("color_packed", 0, 0) in inputs:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            frames = [inputs[("color", f, 0)] for f in (0, -1, 1)]
+            for _ in range(3):
+                keep = [ops.pack_rgbx(fr) for fr in frames]
+            e0.record()
+            for _ in range(20):
+                keep = [ops.pack_rgbx(fr) for fr in frames]
+            e1.record()
+            torch.cuda.synchronize()
+            rgbx_pack_ms = e0.elapsed_time(e1) / 20.0
+            del keep
+
+        # In the timed region the pose and the depth network run on two HIP streams, so a launch's event pair also spans
+        # the time it shares the GPU with a kernel of the other stream.  The kernel's own duration (what rocprofv3, which
+        # serialises dispatches, reports) is taken from SERIAL_STEPS single-stream steps run right after the timed region
+        # with an event pair around every launch.
+        SERIAL_STEPS = 3
+        if tr.opt.overlap_streams:
+            tr.opt.overlap_streams = False
+            lanes, tr.wgrad_lanes = tr.wgrad_lanes, False
+            ops.profile_enable(SERIAL_STEPS + 2)
+            ops.conv_profile_enable((SERIAL_STEPS + 1) * 400, 1)
+            for _ in range(SERIAL_STEPS):
+                tr.train_step(inputs)
+            torch.cuda.synchronize()
+            prof = ops.profile_collect()
+            fam = {k: ops.conv_profile_collect(k) for k in FAMILIES}
+            ops.profile_enable(0)
+            ops.conv_profile_enable(0, 1)
+            tr.opt.overlap_streams = True
+            tr.wgrad_lanes = lanes
+            roof_src, fam_steps = "%d single-stream steps after the timed region, every launch" % SERIAL_STEPS, SERIAL_STEPS
+        else:
+            fam = fam_c
+            roof_src, fam_steps = "timed region, every 7th launch", args.steps * args.windows / 7.0
     tmax = torch.tensor([dt], dtype=torch.float64, device=device)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+    if world > 1 and args.full:
         # replicas must stay in lock-step: after K identical Adam steps on averaged gradients ALL weights agree
         wsum = torch.stack([p.detach().double().sum() for p in tr.parameters_to_train])
         wmax, wmin = wsum.clone(), wsum.clone()
@@ -549,111 +609,112 @@ def run_rank(args):
         elif args.front == "fusion":
             label = "BASELINE configs[4] (per rank, %s): Fusion_v3 attention fusion on frames {-2,-1,0}, " % (
                 "fp32" if args.nets_dtype == "f32" else "networks' convolutions on the bf16 matrix cores, everything else fp32")
-        N = args.batch * args.height * args.width
-        bytes_fwd = sum(36.0 * N + 16.0 * (N >> (2 * s)) for s in range(4))
-        bytes_bwd = sum(36.0 * N + 20.0 * (N >> (2 * s)) for s in range(4))
-        nb, nf = max(prof["bwd_launches"], 1), max(prof["fwd_launches"], 1)
-        bwd_ms, fwd_ms = prof["bwd_ms"] / nb, prof["fwd_ms"] / nf
-        bwd_chain_ms, fwd_chain_ms = prof["bwd_chain_ms"] / nb, prof["fwd_chain_ms"] / nf
-        ach = bytes_bwd / (bwd_chain_ms * 1e-3) / 1e9 if bwd_chain_ms > 0 else 0.0
-        traffic, traffic_src = _traffic_for(cfg_key)
+        if args.full:
+            N = args.batch * args.height * args.width
+            bytes_fwd = sum(36.0 * N + 16.0 * (N >> (2 * s)) for s in range(4))
+            bytes_bwd = sum(36.0 * N + 20.0 * (N >> (2 * s)) for s in range(4))
+            nb, nf = max(prof["bwd_launches"], 1), max(prof["fwd_launches"], 1)
+            bwd_ms, fwd_ms = prof["bwd_ms"] / nb, prof["fwd_ms"] / nf
+            bwd_chain_ms, fwd_chain_ms = prof["bwd_chain_ms"] / nb, prof["fwd_chain_ms"] / nf
+            ach = bytes_bwd / (bwd_chain_ms * 1e-3) / 1e9 if bwd_chain_ms > 0 else 0.0
+            traffic, traffic_src = _traffic_for(cfg_key)
 
-        def tr_bytes(k):
-            v = traffic.get(k)
-            return round(v["hbm_bytes_calibrated"], 0) if v and "hbm_bytes_calibrated" in v else None
+            def tr_bytes(k):
+                v = traffic.get(k)
+                return round(v["hbm_bytes_calibrated"], 0) if v and "hbm_bytes_calibrated" in v else None
 
-        def valu(k):
-            v = traffic.get(k)
-            return v.get("sq_insts_valu") if v else None
-        # every instrumented kernel family of the step; the roofline entry is the one that takes the most GPU time
-        def family_entry(k):
-            d, dc_ = fam[k], fam_c[k]
-            if d["launches"] == 0 or d["ms"] <= 0:
-                return None
-            name, bound = FAMILIES[k]
-            sec = d["ms"] * 1e-3
-            tf, ex = d["flops"] / sec / 1e12, d["executed_flops"] / sec / 1e12
-            e = {"kernel": name, "bound": bound, "family": k,
-                 "ms_per_step": round(d["ms"] / fam_steps, 3), "launches_per_step": round(d["launches"] / fam_steps, 1),
-                 "avg_kernel_ms": round(d["ms"] / d["launches"], 4), "launches_timed": d["launches"],
-                 "algorithmic_flops_per_launch": round(d["flops"] / d["launches"], 0),
-                 "algorithmic_bytes_per_launch": round(d["bytes"] / d["launches"], 0)}
-            if bound == "mfma":
-                # `achieved` / `frac` = what the matrix pipe does (<= 1): FLOPs actually issued to the MFMA units.  For the
-                # Winograd kernels that is 16/36 of SURVEY 8d's algorithmic count (2 MAC of the direct convolution), which is
-                # kept beside it as the direct-convolution equivalent; for a direct GEMM the two are the same number
-                e.update({"achieved": round(ex, 2), "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                          "frac": round(ex / MFMA_F32_PEAK_TFLOPS, 4),
-                          "flops_definition": "FLOPs issued to the matrix cores (Winograd F(2x2,3x3): 16/36 of the direct "
-                                              "convolution's 2 MAC; GEMMs: all of them), summed over the launches",
-                          "issued_frac_of_peak": round(ex / MFMA_F32_PEAK_TFLOPS, 4),
-                          "direct_conv_equivalent_tflops": round(tf, 2),
-                          "direct_conv_equivalent_frac": round(tf / MFMA_F32_PEAK_TFLOPS, 4)})
-            elif bound == "mfma_bf16":
-                # split operands: `achieved` / `frac` = the bf16 matrix FLOPs actually issued (six products per fp32 multiply, padded
-                # tiles) against the dense bf16 peak; the fp32 GEMM it stands for (SURVEY 8d's 2 MAC) beside it
-                e.update({"bound": "mfma", "achieved": round(ex, 1), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
-                          "frac": round(ex / MFMA_BF16_PEAK_TFLOPS, 4),
-                          "flops_definition": "bf16 matrix FLOPs issued: 6 partial products per fp32 multiply-add, padded tiles",
-                          "fp32_equivalent_tflops": round(tf, 2), "fp32_equivalent_frac_of_fp32_matrix_peak": round(tf / MFMA_F32_PEAK_TFLOPS, 4)})
-            else:
-                gbs = d["bytes"] / sec / 1e9
-                e.update({"achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
-                          "bytes_definition": "each fp32 operand tensor and the fp32 result once, per launch",
-                          "matrix_core_tflops_bf16": round(ex, 1), "matrix_core_frac_of_bf16_peak": round(ex / MFMA_BF16_PEAK_TFLOPS, 4)})
-            if dc_["launches"]:
-                e["avg_kernel_ms_in_timed_region"] = round(dc_["ms"] / dc_["launches"], 4)
-            return e
-        fams = [e for e in (family_entry(k) for k in FAMILIES) if e]
-        fams.sort(key=lambda e: -e["ms_per_step"])
-        dom = dict(fams[0]) if fams else {"kernel": None, "bound": "mfma", "achieved": 0.0, "peak": MFMA_F32_PEAK_TFLOPS,
-                                          "unit": "TFLOP/s", "frac": 0.0}
-        dom_key = {0: "dc::wino_ps_kernel", 1: "dc::wino_wgrad_kernel", 2: "dc::c3b_conv_kernel", 3: "dc::c3b_wgrad_kernel", 4: "dc::g1_*",
-                   5: "dc::cg_*", 6: "dc::stem_*", 7: "dc::g1x3_*"}.get(dom.get("family"))
-        # ---- BASELINE metric 2: the fused warp + SSIM + smoothness kernels against HBM.  Round 4 moved the SSIM derivative, its
-        # transposed 3x3 spread and the contraction with d(warped)/d(coords) into the TRAINING FORWARD; round 5 lets it go all the
-        # way (dc::photo_fwdg_kernel<.., FULL>: Project3D / BackprojectDepth / disp_to_depth backward and the pose sums in the
-        # same row march, ONE float per pixel and scale out), so the backward chain is dc::disp_grad_kernel alone (transposed
-        # upsample + smoothness gradient + pose reduction, scaled by the step's upstream weights).  The honest figure is the
-        # PAIR: SURVEY 8d's algorithmic bytes of forward + backward over the time of both launch chains.
-        def chain(bytes_, ms):
-            gbs = bytes_ / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-            return {"algorithmic_bytes_per_launch": bytes_, "avg_chain_ms": round(ms, 4), "achieved": round(gbs, 1),
-                    "frac": round(gbs / HBM_PEAK_GBS, 4)}
+            def valu(k):
+                v = traffic.get(k)
+                return v.get("sq_insts_valu") if v else None
+            # every instrumented kernel family of the step; the roofline entry is the one that takes the most GPU time
+            def family_entry(k):
+                d, dc_ = fam[k], fam_c[k]
+                if d["launches"] == 0 or d["ms"] <= 0:
+                    return None
+                name, bound = FAMILIES[k]
+                sec = d["ms"] * 1e-3
+                tf, ex = d["flops"] / sec / 1e12, d["executed_flops"] / sec / 1e12
+                e = {"kernel": name, "bound": bound, "family": k,
+                     "ms_per_step": round(d["ms"] / fam_steps, 3), "launches_per_step": round(d["launches"] / fam_steps, 1),
+                     "avg_kernel_ms": round(d["ms"] / d["launches"], 4), "launches_timed": d["launches"],
+                     "algorithmic_flops_per_launch": round(d["flops"] / d["launches"], 0),
+                     "algorithmic_bytes_per_launch": round(d["bytes"] / d["launches"], 0)}
+                if bound == "mfma":
+                    # `achieved` / `frac` = what the matrix pipe does (<= 1): FLOPs actually issued to the MFMA units.  For the
+                    # Winograd kernels that is 16/36 of SURVEY 8d's algorithmic count (2 MAC of the direct convolution), which is
+                    # kept beside it as the direct-convolution equivalent; for a direct GEMM the two are the same number
+                    e.update({"achieved": round(ex, 2), "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                              "frac": round(ex / MFMA_F32_PEAK_TFLOPS, 4),
+                              "flops_definition": "FLOPs issued to the matrix cores (Winograd F(2x2,3x3): 16/36 of the direct "
+                                                  "convolution's 2 MAC; GEMMs: all of them), summed over the launches",
+                              "issued_frac_of_peak": round(ex / MFMA_F32_PEAK_TFLOPS, 4),
+                              "direct_conv_equivalent_tflops": round(tf, 2),
+                              "direct_conv_equivalent_frac": round(tf / MFMA_F32_PEAK_TFLOPS, 4)})
+                elif bound == "mfma_bf16":
+                    # split operands: `achieved` / `frac` = the bf16 matrix FLOPs actually issued (six products per fp32 multiply, padded
+                    # tiles) against the dense bf16 peak; the fp32 GEMM it stands for (SURVEY 8d's 2 MAC) beside it
+                    e.update({"bound": "mfma", "achieved": round(ex, 1), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
+                              "frac": round(ex / MFMA_BF16_PEAK_TFLOPS, 4),
+                              "flops_definition": "bf16 matrix FLOPs issued: 6 partial products per fp32 multiply-add, padded tiles",
+                              "fp32_equivalent_tflops": round(tf, 2), "fp32_equivalent_frac_of_fp32_matrix_peak": round(tf / MFMA_F32_PEAK_TFLOPS, 4)})
+                else:
+                    gbs = d["bytes"] / sec / 1e9
+                    e.update({"achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
+                              "bytes_definition": "each fp32 operand tensor and the fp32 result once, per launch",
+                              "matrix_core_tflops_bf16": round(ex, 1), "matrix_core_frac_of_bf16_peak": round(ex / MFMA_BF16_PEAK_TFLOPS, 4)})
+                if dc_["launches"]:
+                    e["avg_kernel_ms_in_timed_region"] = round(dc_["ms"] / dc_["launches"], 4)
+                return e
+            fams = [e for e in (family_entry(k) for k in FAMILIES) if e]
+            fams.sort(key=lambda e: -e["ms_per_step"])
+            dom = dict(fams[0]) if fams else {"kernel": None, "bound": "mfma", "achieved": 0.0, "peak": MFMA_F32_PEAK_TFLOPS,
+                                              "unit": "TFLOP/s", "frac": 0.0}
+            dom_key = {0: "dc::wino_ps_kernel", 1: "dc::wino_wgrad_kernel", 2: "dc::c3b_conv_kernel", 3: "dc::c3b_wgrad_kernel", 4: "dc::g1_*",
+                       5: "dc::cg_*", 6: "dc::stem_*", 7: "dc::g1x3_*"}.get(dom.get("family"))
+            # ---- BASELINE metric 2: the fused warp + SSIM + smoothness kernels against HBM.  Round 4 moved the SSIM derivative, its
+            # transposed 3x3 spread and the contraction with d(warped)/d(coords) into the TRAINING FORWARD; round 5 lets it go all the
+            # way (dc::photo_fwdg_kernel<.., FULL>: Project3D / BackprojectDepth / disp_to_depth backward and the pose sums in the
+            # same row march, ONE float per pixel and scale out), so the backward chain is dc::disp_grad_kernel alone (transposed
+            # upsample + smoothness gradient + pose reduction, scaled by the step's upstream weights).  The honest figure is the
+            # PAIR: SURVEY 8d's algorithmic bytes of forward + backward over the time of both launch chains.
+            def chain(bytes_, ms):
+                gbs = bytes_ / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
+                return {"algorithmic_bytes_per_launch": bytes_, "avg_chain_ms": round(ms, 4), "achieved": round(gbs, 1),
+                        "frac": round(gbs / HBM_PEAK_GBS, 4)}
 
-        def kern(name, ms, bytes_, slots):
-            v = valu(name)
-            e = {"kernel": name, "avg_kernel_ms": round(ms, 4), "traffic": tr_bytes(name), "valu_wave_insts": v}
-            if v and ms > 0:
-                floor_s = v * slots * 64.0 / VALU_LANE_OPS_PEAK
-                e.update({"valu_issue_floor_ms": round(floor_s * 1e3, 4), "valu_issue_frac": round(floor_s / (ms * 1e-3), 4),
-                          "hbm_frac_at_valu_floor": round(bytes_ / floor_s / 1e9 / HBM_PEAK_GBS, 4)})
-            return e
-        pair_ms = fwd_chain_ms + bwd_chain_ms
-        pair = chain(bytes_fwd + bytes_bwd, pair_ms)
-        photometric = dict(pair, **{
-            "kernel": "fused warp + SSIM + L1 + automask + smoothness, forward AND backward launch chains of a step (4 scales x 2 "
-                      "frames): identity + smooth + dc::photo_fwdg_kernel (contracts to d loss / d upsampled disp + pose sums) + "
-                      "finalize | dc::disp_grad_kernel (transposed upsample, smoothness gradient, pose-gradient reduction)",
-            "bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "traffic": (tr_bytes("dc::identity_kernel") or 0) + (tr_bytes("dc::photo_fwdg_kernel") or 0) + (tr_bytes("dc::smooth_fwd_kernel") or 0)
-                       + (tr_bytes("dc::photo_bwdg_kernel") or 0) + (tr_bytes("dc::disp_grad_kernel") or 0)
-                       if tr_bytes("dc::photo_fwdg_kernel") else None,
-            "traffic_source": traffic_src, "launches": prof["bwd_launches"],
-            "bytes_definition": "SURVEY 8d: forward sum_s 36 N + 16 n_s, backward sum_s 36 N + 20 n_s (fp32, N = B H W)",
-            # (only the PAIR is priced against SURVEY 8d's bytes: since round 4 the backward's window work runs in the forward, so a
-            # per-chain fraction would credit the backward with bytes it no longer moves)
-            "forward_chain": dict({"avg_chain_ms": round(fwd_chain_ms, 4)}, **kern("dc::photo_fwdg_kernel", fwd_ms, bytes_fwd + bytes_bwd, VALU_SLOTS_PER_INST["fwd"])),
-            "backward_chain": dict({"avg_chain_ms": round(bwd_chain_ms, 4)}, **kern("dc::disp_grad_kernel", bwd_chain_ms, bytes_fwd + bytes_bwd, VALU_SLOTS_PER_INST["bwd"])),
-            "valu_wave_insts_per_step": (sum(valu(k) or 0 for k in ("dc::identity_kernel", "dc::smooth_fwd_kernel", "dc::photo_fwdg_kernel",
-                                                                     "dc::finalize_kernel", "dc::photo_bwdg_kernel", "dc::disp_grad_kernel"))
-                                         if valu("dc::photo_fwdg_kernel") else None),
-            "round3": {"forward_chain_ms": 0.17, "backward_chain_ms": 0.2487, "pair_frac": 0.148,
-                       "note": "forward without gradient emission + the window backward (profiles/round3_c2_bench_n1.json)"},
-            "limiter": "the training forward is VALU-issue bound (3 waves per SIMD at 167 VGPRs: loads issued behind stage B, the "
-                       "projection backward and the 18 pose accumulators in stage C); the transposed upsample is latency / HBM bound",
-            "valu_note": "SQ_INSTS_VALU per launch (cited PMC pass) x issue slots per instruction from the ISA mix "
-                         "(profiles/round6_photo_isa_mix.txt); 2 cycles per slot per SIMD-32"})
+            def kern(name, ms, bytes_, slots):
+                v = valu(name)
+                e = {"kernel": name, "avg_kernel_ms": round(ms, 4), "traffic": tr_bytes(name), "valu_wave_insts": v}
+                if v and ms > 0:
+                    floor_s = v * slots * 64.0 / VALU_LANE_OPS_PEAK
+                    e.update({"valu_issue_floor_ms": round(floor_s * 1e3, 4), "valu_issue_frac": round(floor_s / (ms * 1e-3), 4),
+                              "hbm_frac_at_valu_floor": round(bytes_ / floor_s / 1e9 / HBM_PEAK_GBS, 4)})
+                return e
+            pair_ms = fwd_chain_ms + bwd_chain_ms
+            pair = chain(bytes_fwd + bytes_bwd, pair_ms)
+            photometric = dict(pair, **{
+                "kernel": "fused warp + SSIM + L1 + automask + smoothness, forward AND backward launch chains of a step (4 scales x 2 "
+                          "frames): identity + smooth + dc::photo_fwdg_kernel (contracts to d loss / d upsampled disp + pose sums) + "
+                          "finalize | dc::disp_grad_kernel (transposed upsample, smoothness gradient, pose-gradient reduction)",
+                "bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "traffic": (tr_bytes("dc::identity_kernel") or 0) + (tr_bytes("dc::photo_fwdg_kernel") or 0) + (tr_bytes("dc::smooth_fwd_kernel") or 0)
+                           + (tr_bytes("dc::photo_bwdg_kernel") or 0) + (tr_bytes("dc::disp_grad_kernel") or 0)
+                           if tr_bytes("dc::photo_fwdg_kernel") else None,
+                "traffic_source": traffic_src, "launches": prof["bwd_launches"],
+                "bytes_definition": "SURVEY 8d: forward sum_s 36 N + 16 n_s, backward sum_s 36 N + 20 n_s (fp32, N = B H W)",
+                # (only the PAIR is priced against SURVEY 8d's bytes: since round 4 the backward's window work runs in the forward, so a
+                # per-chain fraction would credit the backward with bytes it no longer moves)
+                "forward_chain": dict({"avg_chain_ms": round(fwd_chain_ms, 4)}, **kern("dc::photo_fwdg_kernel", fwd_ms, bytes_fwd + bytes_bwd, VALU_SLOTS_PER_INST["fwd"])),
+                "backward_chain": dict({"avg_chain_ms": round(bwd_chain_ms, 4)}, **kern("dc::disp_grad_kernel", bwd_chain_ms, bytes_fwd + bytes_bwd, VALU_SLOTS_PER_INST["bwd"])),
+                "valu_wave_insts_per_step": (sum(valu(k) or 0 for k in ("dc::identity_kernel", "dc::smooth_fwd_kernel", "dc::photo_fwdg_kernel",
+                                                                         "dc::finalize_kernel", "dc::photo_bwdg_kernel", "dc::disp_grad_kernel"))
+                                             if valu("dc::photo_fwdg_kernel") else None),
+                "round3": {"forward_chain_ms": 0.17, "backward_chain_ms": 0.2487, "pair_frac": 0.148,
+                           "note": "forward without gradient emission + the window backward (profiles/round3_c2_bench_n1.json)"},
+                "limiter": "the training forward is VALU-issue bound (3 waves per SIMD at 167 VGPRs: loads issued behind stage B, the "
+                           "projection backward and the 18 pose accumulators in stage C); the transposed upsample is latency / HBM bound",
+                "valu_note": "SQ_INSTS_VALU per launch (cited PMC pass) x issue slots per instruction from the ISA mix "
+                             "(profiles/round6_photo_isa_mix.txt); 2 cycles per slot per SIMD-32"})
         out = {
             "metric": "training images/sec at %dx%d bs%d (resnet%d depth+pose, 4-scale photometric+smoothness)"
                       % (args.height, args.width, args.batch, args.num_layers),
@@ -664,8 +725,6 @@ def run_rank(args):
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": ("f32" if not split_on else "f32 (1x1 convolutions: bf16x3 split operands, fp32 accumulate)") if args.nets_dtype == "f32"
                      else "bf16-nets/f32-loss", "data": "synthetic",
-            "windows_ms_per_step": [round(w, 3) for w in windows],
-            "steady_state_ms_per_step": round(sorted(windows[1:])[len(windows[1:]) // 2], 3) if len(windows) > 1 else None,
             "config": {"workload": "%sresnet%d depth+pose, %dx%d, per-GPU batch %d, 4 scales, "
                                    "frames {0,-1,+1}, automasking, Adam lr 1e-4; random-init weights"
                                    % (label, args.num_layers, args.height, args.width, args.batch),
@@ -675,49 +734,53 @@ def run_rank(args):
                            "as the device data step delivers them: planar (\"color\", f, s) / (\"color_aug\", f, s) plus the "
                            "pixel-interleaved RGBx copy (\"color_packed\", f, 0) of the three loss frames (dc_data_to_rgbx)"
                            if ("color_packed", 0, 0) in inputs else "planar tensors only (the loss repacks the three frames per step)"),
-                       "rgbx_pack_ms_if_done_inside_the_step": round(rgbx_pack_ms, 4) if rgbx_pack_ms is not None else None,
                        "setup_steps": SETUP_STEPS,
                        "step_launch": "one hipGraph replay per step" if graphed else "eager (one launch per kernel)",
                        "streams": (("depth and pose branches on two HIP streams" + ("; the depth branch's is a high-priority stream (opt.step_priority)"
                                                                                      if tr._main_stream is not None and not graphed else ""))
                                    if tr.opt.overlap_streams else "one HIP stream")
                                   + ("; weight-gradient kernels on a companion stream of each (opt.wgrad_lanes)" if tr.wgrad_lanes else "")},
-            "roofline": dict(dom, **{
-                         # HBM bytes per launch from the PMC counters: CITED from the separate `rocprofv3 --pmc` passes kept under
-                         # profiles/ (a counter pass serialises the step and cannot share a process with the timed region)
-                         "traffic": tr_bytes(dom_key) if dom_key else None, "traffic_cited": bool(dom_key and tr_bytes(dom_key)),
-                         "traffic_source": traffic_src if dom_key and tr_bytes(dom_key) else None,
-                         "measured_in": roof_src,
-                         "selection": "the instrumented kernel family with the largest GPU time per step; all of them under `families`",
-                         "timed_region_note": "two-stream overlap: a launch shares the GPU with the other branch's kernels "
-                                              "(sampled every 7th launch); rocprofv3 serialises dispatches and matches avg_kernel_ms",
-                         "note": "`frac` is the fraction of the fp32 MFMA peak the pipe actually delivers (issued FLOPs); the Winograd "
-                                 "kernels issue 16/36 of SURVEY 8d's algorithmic MACs, so their direct-convolution equivalent "
-                                 "(`direct_conv_equivalent_frac`) is 2.25x that and may exceed 1",
-                         "families": fams[1:],
-                         "photometric": photometric}),
             "host_enqueue_ms_per_step": round(host_s / args.steps * 1e3, 3),
             "accumulate_grad_stream_warning_first_seen_in": accgrad_phase[0] if accgrad_phase else None,
-            "phases_ms": {"forward": round(ph[0], 3), "backward_incl_overlapped_exchange": round(ph[1], 3),
-                          "exposed_exchange_wait": round(ph[2], 3), "adam": round(ph[3], 3),
-                          "note": "host-synchronised between phases (slower than the pipelined step); %d steps after the "
-                                  "timed region" % PH},
             "loss_first": round(float(loss0), 6), "loss_last": round(loss_last, 6),
             "grad_bytes_allreduced_per_step": tr.buckets.nbytes if world > 1 else 0,
             "grad_buckets": len(tr.buckets.buckets) if world > 1 else 0,
             "grads_packed_by_copy_per_step": packed if world > 1 else 0,
             "dist_backend": (backend if world > 1 else None),
-            # what the exchange actually ran on (checkable against the driver's launch): ranks the process group connected, the
-            # device ordinal of every rank, the buckets in launch order with their bytes, and the communicator settings in effect
-            "rccl_ranks": dist_info["ranks"] if world > 1 else None,
-            "rank_devices": dist_info["devices"] if world > 1 else None,
-            "grad_bucket_bytes_in_launch_order": [tr.buckets.flat[b].numel() * 4 for b in bucket_order] if world > 1 else None,
-            "grad_bucket_launch_ms_after_backward_start": bucket_offsets_ms if world > 1 else None,
             "rccl_env": {k: os.environ[k] for k in sorted(os.environ) if k.startswith(("NCCL_", "RCCL_"))} if world > 1 else None,
         }
+        if args.full:
+            out["config"]["rgbx_pack_ms_if_done_inside_the_step"] = round(rgbx_pack_ms, 4) if rgbx_pack_ms is not None else None
+            out.update({
+                "windows_ms_per_step": [round(w, 3) for w in windows],
+                "steady_state_ms_per_step": round(sorted(windows[1:])[len(windows[1:]) // 2], 3) if len(windows) > 1 else None,
+                "roofline": dict(dom, **{
+                             # HBM bytes per launch from the PMC counters: CITED from the separate `rocprofv3 --pmc` passes kept under
+                             # profiles/ (a counter pass serialises the step and cannot share a process with the timed region)
+                             "traffic": tr_bytes(dom_key) if dom_key else None, "traffic_cited": bool(dom_key and tr_bytes(dom_key)),
+                             "traffic_source": traffic_src if dom_key and tr_bytes(dom_key) else None,
+                             "measured_in": roof_src,
+                             "selection": "the instrumented kernel family with the largest GPU time per step; all of them under `families`",
+                             "timed_region_note": "two-stream overlap: a launch shares the GPU with the other branch's kernels "
+                                                  "(sampled every 7th launch); rocprofv3 serialises dispatches and matches avg_kernel_ms",
+                             "note": "`frac` is the fraction of the fp32 MFMA peak the pipe actually delivers (issued FLOPs); the Winograd "
+                                     "kernels issue 16/36 of SURVEY 8d's algorithmic MACs, so their direct-convolution equivalent "
+                                     "(`direct_conv_equivalent_frac`) is 2.25x that and may exceed 1",
+                             "families": fams[1:],
+                             "photometric": photometric}),
+                "phases_ms": {"forward": round(ph[0], 3), "backward_incl_overlapped_exchange": round(ph[1], 3),
+                              "exposed_exchange_wait": round(ph[2], 3), "adam": round(ph[3], 3),
+                              "note": "host-synchronised between phases (slower than the pipelined step); %d steps after the "
+                                      "timed region" % PH},
+                # what the exchange actually ran on (checkable against the driver's launch): ranks the process group connected, the
+                # device ordinal of every rank, the buckets in launch order with their bytes (the communicator settings: rccl_env)
+                "rccl_ranks": dist_info["ranks"] if world > 1 else None,
+                "rank_devices": dist_info["devices"] if world > 1 else None,
+                "grad_bucket_bytes_in_launch_order": [tr.buckets.flat[b].numel() * 4 for b in bucket_order] if world > 1 else None,
+                "grad_bucket_launch_ms_after_backward_start": bucket_offsets_ms if world > 1 else None})
         if world > 1 and (backend != "nccl" or args.oversubscribe):
             out["rehearsal"] = "backend %s%s: not an RCCL/xGMI measurement" % (backend, ", ranks share GPUs" if args.oversubscribe else "")
-        if world == 1 and not args.no_cpu_baseline and args.front == "none":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.front == "none":
             out["cpu_baseline"] = cpu_baseline(opt, tr)
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -735,7 +798,11 @@ def main():
     ap.add_argument("--height", type=int, default=192)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--num-layers", type=int, default=18)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: the spread windows, "
+                    "roofline, phase split, exchange timeline and replica check at N > 1, and the CPU baseline (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-probe", type=int, default=0, help="internal: child process of cpu_baseline (one B=1 oracle step at N threads)")
     ap.add_argument("--cpu-noise", action="store_true", help="reference-style CPU randn tie-break noise + H2D copy")
     ap.add_argument("--front", choices=["none", "gru", "fusion"], default="none",
@@ -745,8 +812,8 @@ def main():
                     help="bf16: the reduced-precision-networks policy of BASELINE configs[4] (convolution operands rounded to bf16 "
                          "for the matrix cores, fp32 accumulate; tensors, master weights, BatchNorm and the loss stay fp32); "
                          "reported under its own dtype, never the headline")
-    ap.add_argument("--windows", type=int, default=4, help="timed windows of --steps steps: the first is the reported value, the "
-                                                            "others show the run-to-run spread (windows_ms_per_step)")
+    ap.add_argument("--windows", type=int, default=4, help="--full: timed windows of --steps steps: the first is the reported value, "
+                                                            "the others show the run-to-run spread (windows_ms_per_step)")
     ap.add_argument("--graph", action="store_true", help="capture the training step (with world > 1: incl. the RCCL exchange) in one hipGraph and replay it (opt.hip_graph)")
     ap.add_argument("--no-wino-cache", action="store_true", help="per-launch Winograd weight transforms (A/B of wino_weight_cache)")
     ap.add_argument("--no-packed-inputs", action="store_true",
@@ -776,6 +843,8 @@ def main():
         raise SystemExit("bench.py measures the product library; unset DEPTHCORE_LIB (%s)" % _dc_lib.LIB_PATH)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch(args, sys.argv[1:])
     return run_rank(args)

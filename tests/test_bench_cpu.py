@@ -44,3 +44,39 @@ def test_self_launch_two_ranks_rehearsal_over_gloo():
     assert d["n_gpus"] == 2 and d["steps"] == 3 and d["warmup"] == 1 and d["rehearsal"] is True
     assert d["config"]["global_batch"] == 4 and d["config"]["parallelism"] == "dp2"
     assert d["grad_bytes_allreduced_per_step"] > 0 and d["value"] > 0
+
+
+def test_dump_outputs_repeat_run_for_run(tmp_path):
+    """`--dump-outputs DIR`: the last timed step's arrays as float32 .npy files, identical for two runs with the same arguments
+    (here on the CPU stand-in step; tests/test_bench_gpu.py runs it on the product path)."""
+    import numpy as np
+    for d in ("a", "b"):
+        r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2", "--rehearse", "--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-800:]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert "losses.loss.npy" in names and "parameters.npy" in names
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and np.array_equal(a, b), n
+    loss = float(np.load(tmp_path / "a" / "losses.loss.npy"))
+    assert abs(loss - json.loads(r.stdout.strip().splitlines()[-1])["loss_last"]) <= 1e-6 * abs(loss) + 1e-6
+
+
+def test_dump_outputs_fit_64_mb(tmp_path):
+    """Arrays that do not fit together are cut to a fixed, seeded sample (indices ascending); small ones stay whole."""
+    import numpy as np
+    import torch
+    import bench
+    arrays = {"outputs.big": torch.arange(20_000_000, dtype=torch.float32), "outputs.small": torch.ones(3, 4, dtype=torch.float64),
+              "parameters": torch.arange(10_000_000, dtype=torch.float32).neg()}
+    bench.write_outputs(str(tmp_path / "a"), arrays)
+    bench.write_outputs(str(tmp_path / "b"), arrays)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 << 20
+    small = np.load(tmp_path / "a" / "outputs.small.npy")
+    assert small.shape == (3, 4) and small.dtype == np.float32 and (small == 1).all()
+    big, par = np.load(tmp_path / "a" / "outputs.big.npy"), np.load(tmp_path / "a" / "parameters.npy")
+    assert big.dtype == np.float32 and 5_000_000 < big.size < 20_000_000 and (np.diff(big) >= 0).all()
+    assert 5_000_000 < par.size < 10_000_000 and (np.diff(par) <= 0).all()
+    for n in ("outputs.big.npy", "parameters.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n))

@@ -109,7 +109,7 @@ def test_two_ranks_on_one_gpu_full_bench_step_over_gloo():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--oversubscribe", "--steps", "3", "--warmup", "1",
-                        "--batch", "2", "--height", "64", "--width", "96", "--no-cpu-baseline"],
+                        "--batch", "2", "--height", "64", "--width", "96", "--full", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -186,7 +186,7 @@ def test_two_gpus_capture_failure_on_one_rank():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "DC_DIST_BACKEND"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "5", "--graph",
-                        "--batch", "2", "--height", "64", "--width", "128", "--no-cpu-baseline"],
+                        "--batch", "2", "--height", "64", "--width", "128", "--full", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -206,7 +206,7 @@ def test_two_gpus_bench_step_over_rccl():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "DC_DIST_BACKEND"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

@@ -12,6 +12,32 @@ from oracle import ref_cpu as R
 import make_golden as MG
 
 B, H, W = MG.B, MG.H, MG.W
+_matmul = torch.matmul
+
+
+def _fixture_matmul(a, b):
+    """torch.matmul, with the oracle's float32 products of depth K <= 4 (the pose matrices, BackprojectDepth, Project3D)
+    rounded as the BLAS that wrote the fixtures rounds them: k ascending, a fused multiply-add per step for the per-pixel
+    products (N = H*W), a separate multiply and add for the 4x4 matrices.  The BLAS picks its code path by CPU, and a path
+    without fused multiply-adds lands some pixels one bit away; the warp's floor / argmin / clamp then turn that into more
+    outliers than the tolerances below allow.  Computed this way the comparison is the same on every host."""
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or a.dim() < 2 or b.dim() < 2 or a.shape[-1] > 4:
+        return _matmul(a, b)
+    A, Bm = torch.broadcast_tensors(a.double().unsqueeze(-1), b.double().unsqueeze(-3))        # (..., M, K, N)
+    fused = b.shape[-1] > 4
+    acc = None
+    for k in range(A.shape[-2]):
+        p = A[..., k, :] * Bm[..., k, :]                  # exact: a product of two floats fits a double
+        if acc is None:
+            acc = p.float()
+        else:
+            acc = (p + acc.double() if fused else p.float().double() + acc.double()).float()
+    return acc
+
+
+@pytest.fixture(autouse=True)
+def _host_independent_gemm(monkeypatch):
+    monkeypatch.setattr(torch, "matmul", _fixture_matmul)
 
 
 def T(a):

@@ -48,7 +48,7 @@ for cfg in ("c2", "c3", "c5", "c5bf16"):
     u = json.load(open(os.path.join(SRC, "bench_%s_under_rocprof.json" % cfg)))
     tot = sum(float(r["TotalDurationNs"]) for r in rows)
     steps = u["steps"] + u["warmup"] + 3 + 4
-    L = ["# @R@, %s -- `rocprofv3 --kernel-trace --stats -- python3 bench.py%s --no-cpu-baseline --windows 1 --wgrad-lanes 0` (1x MI355X)\n".replace("@R@", RND)
+    L = ["# @R@, %s -- `rocprofv3 --kernel-trace --stats -- python3 bench.py --full%s --no-cpu-baseline --windows 1 --wgrad-lanes 0` (1x MI355X)\n".replace("@R@", RND)
          % (cfg.upper(), ARGS[cfg]),
          "Workload: %s.\n" % b["config"]["workload"],
          ("Plain run (default options: weight-gradient lanes on where the step is GPU-bound): **%.3f ms/step = %.1f images/s** "

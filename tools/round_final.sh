@@ -7,6 +7,7 @@
 #   3. with `pmc`: the three separate --pmc passes (FETCH_SIZE, WRITE_SIZE, SQ_INSTS_VALU; tools/pmc_traffic.sh)
 set -e
 CFG=$1
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/${ROUND_DIR:-r5final}
 mkdir -p $OUT
 case $CFG in
@@ -21,11 +22,11 @@ case $CFG in
 esac
 cd $GRAFT_REPO_ROOT
 NOCPU="--no-cpu-baseline"; [ $CFG = c2 ] && NOCPU=""
-python3 bench.py $ARGS $NOCPU > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err
+python3 bench.py --full $ARGS $NOCPU > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err
 echo "bench $CFG done"; head -c 400 $OUT/bench_$CFG.json; echo
 if [ $CFG = c1g ] || [ $CFG = c4 ] || [ $CFG = c4g ]; then exit 0; fi
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/rocprof_$CFG -- python3 $GRAFT_REPO_ROOT/bench.py $ARGS --no-cpu-baseline --windows 1 --wgrad-lanes 0 > $OUT/bench_${CFG}_under_rocprof.json 2> $OUT/rocprof_$CFG.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/rocprof_$CFG -- python3 $REPO/bench.py --full $ARGS --no-cpu-baseline --windows 1 --wgrad-lanes 0 > $OUT/bench_${CFG}_under_rocprof.json 2> $OUT/rocprof_$CFG.err
 echo "rocprof $CFG done"
 if [ "$2" = pmc ]; then
   cd $GRAFT_REPO_ROOT
