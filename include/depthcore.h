@@ -30,6 +30,7 @@ extern "C" {
 #define DC_EINVAL (-1)      /* bad shape / null pointer / unsupported option */
 #define DC_ELAUNCH (-2)     /* hipLaunch error */
 #define DC_EWORKSPACE (-3)  /* workspace too small */
+#define DC_EEMPTY (-4)      /* a depth-metrics group whose mask selects no pixel (dc_depth_errors: status) */
 
 #define DC_MAX_SCALES 4
 
@@ -310,7 +311,8 @@ int dc_bn_stats(const float* x, float* part, int N, int C, int HW, int groups, v
 int dc_bn_finalize(const float* part, int nparts, int ppg, double count, const float* gamma, const float* beta,
                    float* running_mean, float* running_var, float* mean, float* invstd, float* scale, float* shift,
                    int C, int groups, float eps, float momentum, void* stream);
-/* y = relu?(scale*x + shift [+ res]); relu_mask (nullable) as in dc_bn_relu_fwd.  HW % 4 == 0 */
+/* y = relu?(scale*x + shift [+ res]); relu_mask (nullable) as in dc_bn_relu_fwd.  HW % 4 != 0 (odd maps, the small
+ * levels of a pose encoder) takes a scalar kernel of the same arithmetic; relu_mask must be NULL there. */
 int dc_bn_apply(const float* x, const float* res, const float* scale, const float* shift, float* y, void* relu_mask,
                 int N, int C, int HW, int relu, int groups, void* stream);
 /* coef: (groups, C, 4) floats; dgamma, dbeta (C) nullable */
@@ -319,6 +321,21 @@ int dc_bn_bwd_finalize(const float* part, int nparts, int ppg, double count, con
 /* dx = a*gp + b*(x - mean) + c0 with gp the MASKED upstream gradient (which is also the residual input's gradient) */
 int dc_bn_bwd_apply(const float* x, const float* gp, const float* coef, float* dx, int N, int C, int HW, int groups,
                     void* stream);
+
+/* ------------------------------------------------------------------ a1 eval-mode BatchNorm2d (+ residual) (+ ReLU)
+ * networks/resnet_encoder.py:87-98 after model.eval() (trainer.py:222-226 set_eval, used by val, trainer.py:444-463):
+ * y = relu?(scale*x + shift [+ res]) with the RUNNING statistics, which are read and never written.
+ *   dc_bn_eval_coef: scale = gamma * rsqrt(running_var + eps), shift = beta - running_mean * scale, invstd = rsqrt(running_var
+ *     + eps) (all (C), invstd nullable) -- then dc_bn_apply(groups = 1) writes y.
+ *   dc_bn_eval_bwd: with g' = gy masked by the ReLU decision [y > 0] (relu = 1; y then required):  dx = scale*g', dres = g'
+ *     (nullable), dbeta = sum g', dgamma = sum g' (x - running_mean) invstd (nullable), summed in a fixed order: per-block
+ *     partials in ws (dc_bn_eval_bwd_workspace bytes), then one block per channel. */
+int dc_bn_eval_coef(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float* scale,
+                    float* shift, float* invstd, int C, float eps, void* stream);
+size_t dc_bn_eval_bwd_workspace(int N, int C, int HW);
+int dc_bn_eval_bwd(const float* x, const float* y, const float* gy, const float* scale, const float* running_mean,
+                   const float* invstd, float* dx, float* dres, float* dgamma, float* dbeta, void* ws, int N, int C, int HW,
+                   int relu, void* stream);
 
 /* nn.MaxPool2d(3, 2, 1) of the ResNet stem (networks/resnet_encoder.py:93).  x (NC planes of HxW) ->
  * y (NC planes of Ho x Wo, Ho = (H-1)/2+1) and `code` (one byte per output: window position of the first
@@ -699,6 +716,37 @@ int dc_data_jitter_to_tensor(const uint8_t* img, float* color, float* color_aug,
  *     callers whose data loader produced the planar tensors (the reference's).  `out` 16-byte aligned. */
 int dc_data_to_rgbx(const uint8_t* img, float* out, int n_img, int npix, void* stream);
 int dc_pack_rgbx(const float* x, float* out, int n_img, int npix, void* stream);
+
+/* ------------------------------------------------------------------ depth metrics (validation)
+ * Trainer.compute_depth_losses (trainer.py:624-652, called at :248 and from val at :460) and the KITTI Eigen protocol of
+ * evaluate_depth.py:190-235, with layers.compute_depth_errors (layers.py:251-269) / evaluate_depth.compute_errors.
+ *   pred (B,1,h,w) at network resolution, gt (B,1,Hg,Wg).  pred is upsampled to (Hg,Wg) by F.interpolate(bilinear,
+ *   align_corners=False), evaluated only where the mask passes, bit for bit the value dc_upsample_bilinear_fwd writes there.
+ *   DC_EVAL_TRAINER: pred holds depth, clamped to [1e-3, 80]; mask gt > 0 inside `crop`; ONE group for the whole batch;
+ *     median = torch.median (element (n-1)/2 of the sorted values).
+ *   DC_EVAL_EIGEN: pred holds scaled disparity, depth = 1/disp (correctly rounded) * scale_factor; mask 1e-3 < gt < 80
+ *     inside `crop`; one group PER IMAGE; median = np.median (fp32 (a+b)/2 of the two middle elements when n is even).
+ *   Then (median_scaling) pred *= median(gt) / median(pred), clamp to [1e-3, 80], and the seven metrics in the reference
+ *   order abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3 -> out (G,7), G = 1 (trainer) or B (eigen).  ratios (G, nullable):
+ *   the ratio applied (1 without median scaling).  status (G, required): 0, or DC_EEMPTY for a group whose mask selects
+ *   no pixel (its row is NaN) -- the launch function never synchronises, so that verdict arrives in device memory.
+ * Medians by radix selection over order-preserving uint32 keys of the fp32 values (three integer-histogram passes, plus
+ * one integer-min pass for numpy's upper middle): no compaction, no sort.  Sums in fp64, per-block partials reduced in a
+ * fixed order: bitwise reproducible.  ws: dc_depth_errors_workspace(d) bytes. */
+#define DC_EVAL_TRAINER 0
+#define DC_EVAL_EIGEN 1
+typedef struct dc_depth_eval_desc {
+    int32_t B, h, w;              /* pred (B,1,h,w) */
+    int32_t Hg, Wg;               /* gt (B,1,Hg,Wg) */
+    int32_t protocol;             /* DC_EVAL_TRAINER | DC_EVAL_EIGEN */
+    int32_t crop[4];              /* rows [crop[0], crop[1]), cols [crop[2], crop[3]) of the gt frame (clipped to it) */
+    int32_t median_scaling;       /* 0 = --disable_median_scaling */
+    float scale_factor;           /* eigen: pred_depth_scale_factor (1 = mono) */
+    float* ratios;                /* (G) or NULL */
+    int32_t* status;              /* (G) */
+} dc_depth_eval_desc;
+size_t dc_depth_errors_workspace(const dc_depth_eval_desc* d);
+int dc_depth_errors(const dc_depth_eval_desc* d, const float* pred, const float* gt, float* out, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

@@ -564,6 +564,84 @@ __global__ __launch_bounds__(256) void bn_bwd_apply2_kernel(const float* __restr
     }
 }
 
+// bn_apply2_kernel's arithmetic one element per thread, for planes with HW % 4 != 0 (no ReLU bit mask).  grid (ceil(HW / 256),
+// C, N)
+__global__ __launch_bounds__(256) void bn_apply_tail_kernel(const float* __restrict__ x, const float* __restrict__ res,
+                                                            const float* __restrict__ scale, const float* __restrict__ shift,
+                                                            float* __restrict__ y, int C, int HW, int relu, int n_per_group) {
+    const int i = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y, n = blockIdx.z;
+    if (i >= HW) return;
+    const int gc = (n / n_per_group) * C + c;
+    const size_t off = ((size_t)n * C + c) * HW + i;
+    float w = fmaf(x[off], scale[gc], shift[gc]);
+    if (res) w += res[off];
+    if (relu) w = fmaxf(w, 0.f);
+    y[off] = w;
+}
+
+// eval mode: scale / shift from the running statistics (never written)
+__global__ __launch_bounds__(256) void bn_eval_coef_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           const float* __restrict__ rmean, const float* __restrict__ rvar,
+                                                           float* __restrict__ scale, float* __restrict__ shift,
+                                                           float* __restrict__ invstd, int C, float eps) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    const float is = 1.f / sqrtf(rvar[c] + eps);
+    const float a = gamma[c] * is;
+    scale[c] = a;
+    shift[c] = beta[c] - rmean[c] * a;
+    if (invstd) invstd[c] = is;
+}
+
+// eval-mode backward, pass 1: g' = gy [y > 0], dx = scale g', dres = g', and per-block fp64 partials {sum g', sum g' (x - mean)}
+// of channel c over its N * HW elements.  grid (chunks, C), chunk = BN_CHUNK elements of the channel's (n, i) range.
+__global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                          const float* __restrict__ gy, const float* __restrict__ scale,
+                                                          const float* __restrict__ rmean, float* __restrict__ dx,
+                                                          float* __restrict__ dres, double2* __restrict__ part, int N, int C,
+                                                          int HW, int relu) {
+    __shared__ double sm[8];
+    const int c = blockIdx.y;
+    const float a = scale[c], m = rmean[c];
+    const long long tot = (long long)N * HW, lo = (long long)blockIdx.x * BN_CHUNK;
+    const long long hi = lo + BN_CHUNK < tot ? lo + BN_CHUNK : tot;
+    double s = 0., q = 0.;
+    for (long long e = lo + threadIdx.x; e < hi; e += 256) {
+        const int n = (int)(e / HW), i = (int)(e - (long long)n * HW);
+        const size_t off = ((size_t)n * C + c) * HW + i;
+        float g = gy[off];
+        if (relu && !(y[off] > 0.f)) g = 0.f;
+        dx[off] = a * g;
+        if (dres) dres[off] = g;
+        s += (double)g;
+        q += (double)g * (double)(x[off] - m);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); q += __shfl_xor(q, o); }
+    if ((threadIdx.x & 63) == 0) { sm[threadIdx.x >> 6] = s; sm[4 + (threadIdx.x >> 6)] = q; }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        part[(size_t)c * gridDim.x + blockIdx.x] = make_double2((sm[0] + sm[1]) + (sm[2] + sm[3]), (sm[4] + sm[5]) + (sm[6] + sm[7]));
+}
+
+// pass 2: one block per channel sums its partials in a fixed order -> dbeta = sum g', dgamma = invstd sum g' (x - mean)
+__global__ __launch_bounds__(256) void bn_eval_bwd_reduce_kernel(const double2* __restrict__ part, int nparts,
+                                                                 const float* __restrict__ invstd, float* __restrict__ dgamma,
+                                                                 float* __restrict__ dbeta) {
+    __shared__ double sm[8];
+    const int c = blockIdx.x;
+    double s = 0., q = 0.;
+    for (int i = threadIdx.x; i < nparts; i += 256) { const double2 v = part[(size_t)c * nparts + i]; s += v.x; q += v.y; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); q += __shfl_xor(q, o); }
+    if ((threadIdx.x & 63) == 0) { sm[threadIdx.x >> 6] = s; sm[4 + (threadIdx.x >> 6)] = q; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (dbeta) dbeta[c] = (float)((sm[0] + sm[1]) + (sm[2] + sm[3]));
+        if (dgamma) dgamma[c] = (float)(((sm[4] + sm[5]) + (sm[6] + sm[7])) * (double)invstd[c]);
+    }
+}
+
 }  // namespace dc
 
 // stand-alone statistics pass in the partial layout (for producers without a statistics epilogue): the partials of
@@ -597,10 +675,48 @@ extern "C" int dc_bn_finalize(const float* part, int nparts, int ppg, double cou
 
 extern "C" int dc_bn_apply(const float* x, const float* res, const float* scale, const float* shift, float* y, void* relu_mask,
                            int N, int C, int HW, int relu, int groups, void* stream) {
-    if (!x || !scale || !shift || !y || N <= 0 || C <= 0 || HW <= 0 || (HW & 3) || groups < 1 || N % groups) return DC_EINVAL;
+    if (!x || !scale || !shift || !y || N <= 0 || C <= 0 || HW <= 0 || groups < 1 || N % groups) return DC_EINVAL;
+    if (HW & 3) {       // (odd maps, small pose-encoder levels): no float4 walk, no bit mask
+        if ((relu && relu_mask) || C > 65535 || N > 65535) return DC_EINVAL;
+        hipLaunchKernelGGL(bn_apply_tail_kernel, dim3(ceil_div(HW, 256), C, N), dim3(256), 0, ST, x, res, scale, shift, y, C, HW,
+                           relu, N / groups);
+        DC_CHECK_LAUNCH();
+        return DC_OK;
+    }
     const int chunks = ceil_div(HW, BN_CHUNK), ns = bn_ns(N / groups, HW);
     hipLaunchKernelGGL(bn_apply2_kernel, dim3(chunks, C, N / ns), dim3(256), 0, ST, x, res, scale, shift, y, C, HW, relu, N / groups,
                        relu ? (unsigned long long*)relu_mask : (unsigned long long*)nullptr, ns);
+    DC_CHECK_LAUNCH();
+    return DC_OK;
+}
+
+extern "C" int dc_bn_eval_coef(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                               float* scale, float* shift, float* invstd, int C, float eps, void* stream) {
+    if (!gamma || !beta || !running_mean || !running_var || !scale || !shift || C <= 0) return DC_EINVAL;
+    hipLaunchKernelGGL(bn_eval_coef_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, ST, gamma, beta, running_mean, running_var, scale,
+                       shift, invstd, C, eps);
+    DC_CHECK_LAUNCH();
+    return DC_OK;
+}
+
+static long long bn_eval_chunks(int N, int HW) { return ((long long)N * HW + BN_CHUNK - 1) / BN_CHUNK; }
+
+extern "C" size_t dc_bn_eval_bwd_workspace(int N, int C, int HW) {
+    if (N <= 0 || C <= 0 || HW <= 0) return 0;
+    return (size_t)C * (size_t)bn_eval_chunks(N, HW) * sizeof(double2);
+}
+
+extern "C" int dc_bn_eval_bwd(const float* x, const float* y, const float* gy, const float* scale, const float* running_mean,
+                              const float* invstd, float* dx, float* dres, float* dgamma, float* dbeta, void* ws, int N, int C, int HW,
+                              int relu, void* stream) {
+    if (!x || !gy || !scale || !running_mean || !invstd || !dx || !ws || (relu && !y) || N <= 0 || C <= 0 || HW <= 0 ||
+        C > 65535 || bn_eval_chunks(N, HW) > 0x7fffffffLL)
+        return DC_EINVAL;
+    const int chunks = (int)bn_eval_chunks(N, HW);
+    hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(chunks, C), dim3(256), 0, ST, x, y, gy, scale, running_mean, dx, dres, (double2*)ws, N,
+                       C, HW, relu);
+    if (dgamma || dbeta)
+        hipLaunchKernelGGL(bn_eval_bwd_reduce_kernel, dim3(C), dim3(256), 0, ST, (const double2*)ws, chunks, invstd, dgamma, dbeta);
     DC_CHECK_LAUNCH();
     return DC_OK;
 }

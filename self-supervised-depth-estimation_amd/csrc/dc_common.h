@@ -52,6 +52,17 @@ __device__ __forceinline__ LinTap lin_tap(int dst, float scale, int n_in) {
     t.w1 = src - (float)i0;
     return t;
 }
+// value of output pixel (oy, ox) of F.interpolate(bilinear, align_corners=False) of the h x w plane d to Ho x Wo, with
+// ry = (float)h / Ho and rx = (float)w / Wo: the one expression of dc_upsample_bilinear_fwd, shared with the depth metrics
+// (metrics.hip), which evaluate it only where their mask passes and must see the same bits.
+__device__ __forceinline__ float bilinear_at(const float* d, int h, int w, int Ho, int Wo, int oy, int ox, float ry, float rx) {
+    if (h == Ho && w == Wo) return d[oy * w + ox];
+    LinTap ty = lin_tap(oy, ry, h), tx = lin_tap(ox, rx, w);
+    const float a = d[ty.i0 * w + tx.i0], b = d[ty.i0 * w + tx.i1];
+    const float c = d[ty.i1 * w + tx.i0], e = d[ty.i1 * w + tx.i1];
+    const float w0 = 1.f - tx.w1, h0 = 1.f - ty.w1;
+    return h0 * (w0 * a + tx.w1 * b) + ty.w1 * (w0 * c + tx.w1 * e);
+}
 
 // ---- grid_sample coordinate handling (border padding) -------------------------------------------
 // returns the clamped source coordinate; `mult` = d(coord)/d(grid) including the zero of the clamp.

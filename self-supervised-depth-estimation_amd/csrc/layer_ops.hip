@@ -236,17 +236,7 @@ __global__ void upsample_fwd_kernel(const float* x, float* out, int h, int w, in
     if (i >= n) return;
     const float* d = x + (size_t)bc * h * w;
     const int oy = i / Wo, ox = i - oy * Wo;
-    float v;
-    if (h == Ho && w == Wo) {
-        v = d[i];
-    } else {
-        LinTap ty = lin_tap(oy, ry, h), tx = lin_tap(ox, rx, w);
-        const float a = d[ty.i0 * w + tx.i0], b = d[ty.i0 * w + tx.i1];
-        const float c = d[ty.i1 * w + tx.i0], e = d[ty.i1 * w + tx.i1];
-        const float w0 = 1.f - tx.w1, h0 = 1.f - ty.w1;
-        v = h0 * (w0 * a + tx.w1 * b) + ty.w1 * (w0 * c + tx.w1 * e);
-    }
-    out[(size_t)bc * n + i] = v;
+    out[(size_t)bc * n + i] = bilinear_at(d, h, w, Ho, Wo, oy, ox, ry, rx);
 }
 __global__ void upsample_bwd_kernel(const float* gout, float* dx, int h, int w, int Ho, int Wo, float ry, float rx) {
     const int n = h * w;

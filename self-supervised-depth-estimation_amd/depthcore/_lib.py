@@ -30,7 +30,10 @@ PREC_F32, PREC_BF16 = 0, 1
 
 _ERR = {-1: "DC_EINVAL (bad shape / null pointer / unsupported option)",
         -2: "DC_ELAUNCH (hip launch failed)",
-        -3: "DC_EWORKSPACE (workspace too small)"}
+        -3: "DC_EWORKSPACE (workspace too small)",
+        -4: "DC_EEMPTY (mask selects no pixel)"}
+DC_EEMPTY = -4
+EVAL_TRAINER, EVAL_EIGEN = 0, 1
 
 
 class DepthcoreError(RuntimeError):
@@ -76,6 +79,12 @@ class BnFold(Structure):
     _fields_ = [("groups", c_int32), ("in_scale", _F), ("in_shift", _F), ("stat_part", _F),
                 ("bn_x", _F), ("bn_mean", _F), ("bn_mask", _F), ("bwd_part", _F)]
 
+
+
+class DepthEvalDesc(Structure):
+    """Mirror of `dc_depth_eval_desc` (include/depthcore.h: dc_depth_errors)."""
+    _fields_ = [("B", c_int32), ("h", c_int32), ("w", c_int32), ("Hg", c_int32), ("Wg", c_int32), ("protocol", c_int32),
+                ("crop", c_int32 * 4), ("median_scaling", c_int32), ("scale_factor", c_float), ("ratios", _F), ("status", _F)]
 
 
 class PoseGroup(Structure):
@@ -130,6 +139,11 @@ def _sig(lib):
         "dc_bn_stats": (i, [p, p, i, i, i, i, p]),
         "dc_bn_finalize": (i, [p, i, i, c_double, p, p, p, p, p, p, p, p, i, i, f, f, p]),
         "dc_bn_apply": (i, [p, p, p, p, p, p, i, i, i, i, i, p]),
+        "dc_bn_eval_coef": (i, [p, p, p, p, p, p, p, i, f, p]),
+        "dc_bn_eval_bwd_workspace": (z, [i, i, i]),
+        "dc_bn_eval_bwd": (i, [p, p, p, p, p, p, p, p, p, p, p, i, i, i, i, p]),
+        "dc_depth_errors_workspace": (z, [POINTER(DepthEvalDesc)]),
+        "dc_depth_errors": (i, [POINTER(DepthEvalDesc), p, p, p, p, p]),
         "dc_bn_bwd_finalize": (i, [p, i, i, c_double, p, p, p, p, p, p, i, i, p]),
         "dc_bn_bwd_apply": (i, [p, p, p, p, i, i, i, i, p]),
         "dc_conv1x1_bn_ok": (i, [i, i, i, i, i]),

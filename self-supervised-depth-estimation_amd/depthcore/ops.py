@@ -981,6 +981,125 @@ def bn_relu(x, bn, res=None, relu=True, groups=1, fork=None):
 
 
 # ----------------------------------------------------------------------------------------------
+# a1 eval-mode BatchNorm2d (+ residual add) (+ ReLU): running statistics, read only  (trainer.py:222-226 set_eval)
+# ----------------------------------------------------------------------------------------------
+class _BNEval(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, res, gamma, beta, running_mean, running_var, eps, relu):
+        L = _lib.lib()
+        xx = _c(x.detach())
+        rr = _c(res.detach()) if res is not None else None
+        g, b = _c(gamma.detach()), _c(beta.detach())
+        rm, rv = running_mean.detach(), running_var.detach()
+        N, C, H, W = xx.shape
+        coef = torch.empty(3, C, dtype=torch.float32, device=xx.device)        # scale, shift, invstd
+        check(L.dc_bn_eval_coef(ptr(g), ptr(b), ptr(rm), ptr(rv), ptr(coef[0]), ptr(coef[1]), ptr(coef[2]), C, float(eps),
+                                stream(xx)), "dc_bn_eval_coef")
+        y = torch.empty_like(xx)
+        check(L.dc_bn_apply(ptr(xx), ptr(rr), ptr(coef[0]), ptr(coef[1]), ptr(y), None, N, C, H * W, int(relu), 1, stream(xx)),
+              "dc_bn_apply")
+        ctx.save_for_backward(xx, y if relu else None, coef, rm)
+        if relu:
+            _record_kink("relu", y)
+        ctx.cfg = (int(relu), res is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        L = _lib.lib()
+        xx, y, coef, rm = ctx.saved_tensors
+        relu, has_res = ctx.cfg
+        N, C, H, W = xx.shape
+        g_c = _c(gy)
+        dx = torch.empty_like(xx)
+        dres = torch.empty_like(xx) if (has_res and ctx.needs_input_grad[1]) else None
+        dgamma = torch.empty(C, dtype=torch.float32, device=xx.device) if ctx.needs_input_grad[2] else None
+        dbeta = torch.empty(C, dtype=torch.float32, device=xx.device) if ctx.needs_input_grad[3] else None
+        ws = torch.empty(L.dc_bn_eval_bwd_workspace(N, C, H * W), dtype=torch.uint8, device=xx.device)
+        check(L.dc_bn_eval_bwd(ptr(xx), ptr(y), ptr(g_c), ptr(coef[0]), ptr(rm), ptr(coef[2]), ptr(dx), ptr(dres), ptr(dgamma),
+                               ptr(dbeta), ws.data_ptr(), N, C, H * W, relu, stream(xx)), "dc_bn_eval_bwd")
+        return dx, dres, dgamma, dbeta, None, None, None, None
+
+
+def bn_eval(x, bn, res=None, relu=True):
+    """y = relu?(bn(x) [+ res]) with `bn` an nn.BatchNorm2d in eval mode: its running statistics (never modified; nor is
+    `num_batches_tracked`).  Differentiable -- frozen-statistics fine-tuning: dx = scale g', dres = g', dbeta = sum g',
+    dgamma = sum g' (x - running_mean) invstd, with g' the gradient masked by the ReLU decision.  `bn_groups` play no role in
+    eval mode.  A BatchNorm without running statistics (track_running_stats=False normalises with batch statistics even in
+    eval mode) or without affine parameters is refused."""
+    if not bn.track_running_stats or bn.running_mean is None or bn.running_var is None:
+        raise DepthcoreError("eval-mode BatchNorm2d without running statistics (track_running_stats=False) is not supported")
+    if bn.weight is None or bn.bias is None:
+        raise DepthcoreError("eval-mode BatchNorm2d without affine parameters is not supported")
+    return _BNEval.apply(x, res, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, relu)
+
+
+# ----------------------------------------------------------------------------------------------
+# depth metrics of validation  (trainer.py:624-652, evaluate_depth.py:190-235, layers.py:251-269)
+# ----------------------------------------------------------------------------------------------
+TRAINER_CROP = (153, 371, 44, 1197)      # trainer.py:638 (garg / eigen crop of a 375 x 1242 frame)
+
+
+def eigen_crop(Hg, Wg):
+    """evaluate_depth.py:207-208: the crop rows / columns as numpy computes them (fp64 products, truncated to int32)."""
+    import numpy as np
+    c = np.array([0.40810811 * Hg, 0.99189189 * Hg, 0.03594771 * Wg, 0.96405229 * Wg]).astype(np.int32)
+    return tuple(int(v) for v in c)
+
+
+def _depth_errors(pred, gt, protocol, crop, median_scaling, scale_factor):
+    """-> (metrics (G, 7), ratios (G,), host copy of [metrics | ratios | status]) after ONE device-to-host copy."""
+    if protocol not in ("trainer", "eigen"):
+        raise ValueError("protocol: 'trainer' (trainer.py:624-652) or 'eigen' (evaluate_depth.py:190-235)")
+    L = _lib.lib()
+    p, g = _c(pred.detach()), _c(gt.detach())
+    if p.dim() != 4 or g.dim() != 4 or p.shape[1] != 1 or g.shape[1] != 1 or p.shape[0] != g.shape[0]:
+        raise DepthcoreError("depth_errors: pred (B,1,h,w) and gt (B,1,Hg,Wg), got %s and %s" % (tuple(p.shape), tuple(g.shape)))
+    B, _, h, w = p.shape
+    Hg, Wg = g.shape[-2:]
+    eigen = protocol == "eigen"
+    if crop is None:
+        crop = eigen_crop(Hg, Wg) if eigen else TRAINER_CROP
+    G = B if eigen else 1
+    buf = torch.empty(G * 9, dtype=torch.float32, device=p.device)       # metrics | ratios | status (int32)
+    d = _lib.DepthEvalDesc()
+    d.B, d.h, d.w, d.Hg, d.Wg = B, h, w, Hg, Wg
+    d.protocol = _lib.EVAL_EIGEN if eigen else _lib.EVAL_TRAINER
+    for i in range(4):
+        d.crop[i] = int(crop[i])
+    d.median_scaling = int(bool(median_scaling))
+    d.scale_factor = float(scale_factor)
+    d.ratios = buf[G * 7:].data_ptr()
+    status = buf[G * 8:].view(torch.int32)
+    d.status = ptr(status, torch.int32)
+    ws = torch.empty(L.dc_depth_errors_workspace(ctypes.byref(d)), dtype=torch.uint8, device=p.device)
+    check(L.dc_depth_errors(ctypes.byref(d), ptr(p), ptr(g), ptr(buf), ws.data_ptr(), stream(p)), "dc_depth_errors")
+    host = buf.cpu()
+    bad = [i for i, v in enumerate(host[G * 8:].view(torch.int32).tolist()) if v != 0]
+    if bad:
+        what = ("image %d of the batch" % bad[0]) if eigen else "the batch"
+        raise DepthcoreError("depth_errors (%s protocol): the mask of %s selects no pixel (%s)" % (protocol, what, _lib._ERR.get(
+            host[G * 8:].view(torch.int32)[bad[0]].item(), "status %d")))
+    return buf[:G * 7].view(G, 7), buf[G * 7:G * 8], host
+
+
+def depth_errors(pred, gt, protocol="trainer", crop=None, median_scaling=True, scale_factor=1.0):
+    """Depth metrics abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3 of `pred` (B,1,h,w) against `gt` (B,1,Hg,Wg), pred
+    bilinearly upsampled to gt's size on the way (dc_depth_errors: one launch chain, medians by radix selection, fp64 sums,
+    bitwise reproducible).
+      protocol="trainer": Trainer.compute_depth_losses (trainer.py:624-652) -- pred is depth; gt > 0 inside `crop` (default
+        rows 153:371, cols 44:1197); torch.median; one ratio for the whole batch.  Returns a (7,) device tensor.
+      protocol="eigen": evaluate_depth.py:198-232 -- pred is scaled disparity (depth = 1 / disp * scale_factor);
+        1e-3 < gt < 80 inside the fractional Eigen crop; np.median; per image.  Returns ((B, 7), ratios (B,)).
+    median_scaling=False: --disable_median_scaling (ratios are then 1).  A group whose mask selects no pixel raises
+    DepthcoreError naming it (this waits for the result: one small device-to-host copy per call)."""
+    out, ratios, _ = _depth_errors(pred, gt, protocol, crop, median_scaling, scale_factor)
+    if protocol == "trainer":
+        return out[0]
+    return out, ratios
+
+
+# ----------------------------------------------------------------------------------------------
 # a1 nn.MaxPool2d(3, 2, 1) of the ResNet stem
 # ----------------------------------------------------------------------------------------------
 class _MaxPool(torch.autograd.Function):

@@ -46,3 +46,25 @@ def synthetic_sequence_batch(len_sequence, height, width, device, num_scales=4, 
         for j in range(len_sequence):
             out[k + (j,)] = v[j:j + 1].contiguous()
     return out
+
+
+def synthetic_depth_gt(batch, device, seed, height=375, width=1242, density=0.05):
+    """Sparse LiDAR-like ground truth ("depth_gt", (batch, 1, height, width) fp32, KITTI's raw size by default): a smooth
+    road-like depth field (near at the bottom rows, far at the top) sampled at a `density` fraction of the pixels, quantised
+    to 1/256 m as KITTI's uint16 depth maps are (so the values tie heavily), zero where there is no return.  About 1 % of the
+    returns are below 1e-3 and 1 % above 80, so that both the trainer's (gt > 0) and the Eigen (1e-3 < gt < 80) masks have
+    something to drop.  Drawn on a CPU generator from `seed` (same values on every device), then moved to `device`."""
+    g = torch.Generator().manual_seed(int(seed))
+    y = torch.linspace(0.0, 1.0, height).view(1, 1, height, 1)
+    x = torch.linspace(-1.0, 1.0, width).view(1, 1, 1, width)
+    base = 2.0 + 70.0 * (1.0 - y) ** 2 + 3.0 * x.abs()
+    depth = base * (1.0 + 0.1 * torch.randn(batch, 1, height, width, generator=g))
+    depth = torch.round(depth.clamp(min=0.5) * 256.0) / 256.0
+    u = torch.rand(batch, 1, height, width, generator=g)
+    ret = u < density
+    low = u < density * 0.01
+    high = (u >= density * 0.01) & (u < density * 0.02)
+    depth = torch.where(low, torch.rand(batch, 1, height, width, generator=g) * 1e-3, depth)
+    depth = torch.where(high, 80.0 + 40.0 * torch.rand(batch, 1, height, width, generator=g), depth)
+    depth = torch.where(ret, depth, torch.zeros(()))
+    return depth.to(torch.float32).contiguous().to(device)

@@ -12,23 +12,19 @@ import os
 import numpy as np
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from depthcore import bnfold as _bnf
 from depthcore import ops as _ops
 
 
 def _bn_act(x, bn, res=None, relu=True, groups=1, fork=None):
-    """BatchNorm2d (+ residual) (+ ReLU).  Training mode (the hot path) is one fused depthcore launch chain and has no
-    fallback: a CPU tensor raises DepthcoreError.  Eval mode (running statistics; validation / export, not on the
-    training path) uses the stock functional ops.
-    `groups`: number of independent sub-batches stacked along dim 0 (statistics per sub-batch)."""
+    """BatchNorm2d (+ residual) (+ ReLU) on depthcore's kernels, no fallback (a CPU tensor raises DepthcoreError).  Training
+    mode (the hot path): one fused launch chain with batch statistics.  Eval mode (running statistics; Trainer.val, export):
+    ops.bn_eval, differentiable, statistics untouched.
+    `groups`: number of independent sub-batches stacked along dim 0 (statistics per sub-batch; no role in eval mode)."""
     if bn.training:
         return _ops.bn_relu(x, bn, res, relu, groups, fork)
-    y = F.batch_norm(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, False, bn.momentum or 0.1, bn.eps)
-    if res is not None:
-        y = y + res
-    return F.relu(y) if relu else y
+    return _ops.bn_eval(x, bn, res, relu)
 
 
 CONV_S2 = True        # 7x7 / 2 stem and 3x3 / 2 convolutions on depthcore's implicit-GEMM kernels (GPU)

@@ -24,6 +24,7 @@ import json
 import os
 import types
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 import torch.optim as optim
@@ -200,6 +201,8 @@ class Trainer:
             h, w = self.opt.height // (2 ** s), self.opt.width // (2 ** s)
             self.backproject_depth[s] = BackprojectDepth(self.loss_batch, h, w).to(self.device)
             self.project_3d[s] = Project3D(self.loss_batch, h, w).to(self.device)
+        self.depth_metric_names = [                                # trainer.py:189-190
+            "de/abs_rel", "de/sq_rel", "de/rms", "de/log_rms", "da/a1", "da/a2", "da/a3"]
         self.step = 0
         self.epoch = 0
         self._side_stream = None
@@ -234,6 +237,49 @@ class Trainer:
     def set_eval(self):
         for m in self.models.values():
             m.eval()
+
+    # ------------------------------------------------------------------ trainer.py:444-463, 624-652
+    def val(self, inputs):
+        """Validate the model on a single minibatch (trainer.py:444-463): eval mode, process_batch under no_grad, the depth
+        metrics when the batch carries "depth_gt", back to train mode; returns (outputs, losses).  The project has no loaders:
+        the batch is the argument (the reference pulls it from val_loader); tensorboard logging stays with the caller.
+        Training is left where it was -- parameters, BatchNorm statistics and num_batches_tracked (eval mode reads the running
+        statistics), optimiser state, self.step, the device noise seed, captured graphs -- and the Winograd weight cache is
+        invalidated again.  With opt.cpu_tiebreak_noise the loss draws its tie-break noise from the CPU generator, as the
+        reference's val does: later training steps then see shifted noise, exactly as there.
+        The sequence front-ends (Fusion_v3, ConvGRU) raise NotImplementedError."""
+        if self.opt.fusion or self.opt.gru:
+            raise NotImplementedError(
+                "val for the %s front-end: its depth output is not the depth of frame 0 of a batch (Fusion_v3 refines the decoder "
+                "output of frame -2; run_gru_v5 stacks a sequence along the batch), so the trainer protocol's depth_gt pairing of "
+                "trainer.py:624-652 does not apply" % ("Fusion_v3" if self.opt.fusion else "ConvGRU"))
+        self.set_eval()
+        try:
+            with torch.no_grad():
+                self.wino_cache.refresh()
+                try:
+                    outputs, losses = self.process_batch(inputs)
+                finally:
+                    self.wino_cache.invalidate()
+                if "depth_gt" in inputs:
+                    self.compute_depth_losses(inputs, outputs, losses)
+        finally:
+            self.set_train()
+        return outputs, losses
+
+    def compute_depth_losses(self, inputs, outputs, losses):
+        """Depth metrics for monitoring (trainer.py:624-652): depth upsampled to gt's size (375 x 1242 in the reference), clamped
+        to [1e-3, 80], gt > 0 inside the Garg crop, scaled by the ratio of the batch's medians, clamped again -- one
+        ops.depth_errors launch chain ("trainer" protocol) and ONE device-to-host copy for the seven values.  Depth comes from
+        outputs[("depth", 0, 0)], or (fused loss without materialize_logs) from disp_to_depth of outputs[("disp", 0)], which is
+        what generate_images_pred would have stored.  Per rank: no cross-rank reduction."""
+        depth = outputs.get(("depth", 0, 0))
+        if depth is None:
+            _, depth = ops.disp_to_depth(outputs[("disp", 0)].detach(), self.opt.min_depth, self.opt.max_depth)
+        _, _, host = ops._depth_errors(depth.detach(), inputs["depth_gt"], "trainer", None, True, 1.0)
+        vals = host.numpy()
+        for i, metric in enumerate(self.depth_metric_names):
+            losses[metric] = np.array(vals[i])
 
     # ------------------------------------------------------------------ trainer.py:256-376
     def _stack_sequence(self, inputs):
