@@ -726,8 +726,10 @@ int dc_pack_rgbx(const float* x, float* out, int n_img, int npix, void* stream);
  *     median = torch.median (element (n-1)/2 of the sorted values).
  *   DC_EVAL_EIGEN: pred holds scaled disparity, depth = 1/disp (correctly rounded) * scale_factor; mask 1e-3 < gt < 80
  *     inside `crop`; one group PER IMAGE; median = np.median (fp32 (a+b)/2 of the two middle elements when n is even).
+ *   DC_EVAL_GT_POSITIVE: DC_EVAL_EIGEN in everything but the mask: gt > 0 over the WHOLE gt frame (`crop` is ignored) --
+ *     the branch of evaluate_depth.py:210-211 for every split but "eigen" (eigen_benchmark).
  *   Then (median_scaling) pred *= median(gt) / median(pred), clamp to [1e-3, 80], and the seven metrics in the reference
- *   order abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3 -> out (G,7), G = 1 (trainer) or B (eigen).  ratios (G, nullable):
+ *   order abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3 -> out (G,7), G = 1 (trainer) or B (eigen, gt_positive).  ratios (G, nullable):
  *   the ratio applied (1 without median scaling).  status (G, required): 0, or DC_EEMPTY for a group whose mask selects
  *   no pixel (its row is NaN) -- the launch function never synchronises, so that verdict arrives in device memory.
  * Medians by radix selection over order-preserving uint32 keys of the fp32 values (three integer-histogram passes, plus
@@ -735,18 +737,34 @@ int dc_pack_rgbx(const float* x, float* out, int n_img, int npix, void* stream);
  * fixed order: bitwise reproducible.  ws: dc_depth_errors_workspace(d) bytes. */
 #define DC_EVAL_TRAINER 0
 #define DC_EVAL_EIGEN 1
+#define DC_EVAL_GT_POSITIVE 2
 typedef struct dc_depth_eval_desc {
     int32_t B, h, w;              /* pred (B,1,h,w) */
     int32_t Hg, Wg;               /* gt (B,1,Hg,Wg) */
-    int32_t protocol;             /* DC_EVAL_TRAINER | DC_EVAL_EIGEN */
+    int32_t protocol;             /* DC_EVAL_TRAINER | DC_EVAL_EIGEN | DC_EVAL_GT_POSITIVE */
     int32_t crop[4];              /* rows [crop[0], crop[1]), cols [crop[2], crop[3]) of the gt frame (clipped to it) */
     int32_t median_scaling;       /* 0 = --disable_median_scaling */
-    float scale_factor;           /* eigen: pred_depth_scale_factor (1 = mono) */
+    float scale_factor;           /* eigen, gt_positive: pred_depth_scale_factor (1 = mono) */
     float* ratios;                /* (G) or NULL */
     int32_t* status;              /* (G) */
 } dc_depth_eval_desc;
 size_t dc_depth_errors_workspace(const dc_depth_eval_desc* d);
 int dc_depth_errors(const dc_depth_eval_desc* d, const float* pred, const float* gt, float* out, void* ws, void* stream);
+
+/* ------------------------------------------------------------------ depth evaluation (evaluate_depth.py)
+ * The prediction side of evaluate_depth.py:95-135 and the benchmark export of :159-171 (csrc/eval.hip).
+ * dc_flip_concat: x (B,C,H,W) -> out (2B,C,H,W) = [x; x mirrored along W] -- torch.cat((x, torch.flip(x, [3])), 0), one launch.
+ * dc_disp_post_process: disp (2B,1,h,w), the decoder's sigmoid output for [x; flip_w(x)] -> out (B,1,h,w):
+ *   disp_to_depth's scaled disparity (bit for bit dc_disp_to_depth_fwd's) of both halves, the second read mirrored, blended as
+ *   batch_post_process_disparity (evaluate_depth.py:48-56): m = 0.5 * (l + r) in fp32; masks (numpy's linspace(0, 1, w)
+ *   values, 1 - clip(20 (l - 0.05), 0, 1) and its mirror) and the blend r_mask*l + l_mask*r + (1 - l_mask - r_mask)*m in fp64
+ *   in numpy's operation order, unfused; one rounding to fp32 at the end.
+ * dc_depth_png16: scaled disparity (N,1,h,w) -> out (N,Ho,Wo) uint16 = uint16(clip(scale / bilinear(disp), 0, 80) * 256), the
+ *   upsample F.interpolate(bilinear, align_corners=False)'s (bit for bit dc_upsample_bilinear_fwd), the conversion truncating
+ *   as numpy's uint16 cast does (NaN -> 0). */
+int dc_flip_concat(const float* x, float* out, int B, int C, int H, int W, void* stream);
+int dc_disp_post_process(const float* disp, float* out, int B, int h, int w, float min_depth, float max_depth, void* stream);
+int dc_depth_png16(const float* disp, uint16_t* out, int N, int h, int w, int Ho, int Wo, float scale, void* stream);
 
 #ifdef __cplusplus
 }

@@ -38,6 +38,11 @@ __device__ __forceinline__ int reflect_clamp(int i, int n) {
 
 __device__ __forceinline__ float frcp(float x) { return __builtin_amdgcn_rcpf(x); }
 
+// disp_to_depth's scaled disparity (layers.py:16-25), lo = 1/max_depth, rng = 1/min_depth - 1/max_depth: the one expression of
+// dc_disp_to_depth_fwd, shared with dc_disp_post_process (eval.hip).  The multiply-add is written fused so that a
+// `fp contract(off)` around a caller cannot change its bits.
+__device__ __forceinline__ float disp_scaled(float d, float lo, float rng) { return __builtin_fmaf(rng, d, lo); }
+
 // ---- F.interpolate(bilinear, align_corners=False) source taps along one axis ------------------
 struct LinTap {
     int i0, i1;

@@ -12,7 +12,7 @@ __global__ void d2d_fwd_kernel(const float* disp, float* scaled, float* depth, s
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (; i < n; i += stride) {
-        float s = lo + rng * disp[i];
+        float s = disp_scaled(disp[i], lo, rng);
         if (scaled) scaled[i] = s;
         if (depth) depth[i] = 1.0f / s;
     }

@@ -1,5 +1,6 @@
-// Depth metrics of validation: Trainer.compute_depth_losses (reference trainer.py:624-652) and the KITTI Eigen protocol of
-// evaluate_depth.py:190-235, scored as layers.compute_depth_errors (layers.py:251-269).  include/depthcore.h: dc_depth_errors.
+// Depth metrics of validation: Trainer.compute_depth_losses (reference trainer.py:624-652) and the two masks of evaluate_depth.py:
+// 190-235 (the Eigen crop; gt > 0 on the whole frame), scored as layers.compute_depth_errors (layers.py:251-269).
+// include/depthcore.h: dc_depth_errors.
 //
 // Every pass walks the crop rectangle of every image (grid (blocks per image, B)) and re-derives, per pixel, the mask from gt
 // and -- where it passes -- the prediction: the bilinear upsample of dc_upsample_bilinear_fwd (bilinear_at), the protocol's
@@ -29,7 +30,7 @@ struct MtState {                                       // one per (group, gt | p
 struct MtArgs {
     const float* pred;
     const float* gt;
-    int B, h, w, Hg, Wg, eigen, y0, y1, x0, x1, nbx, scaling;
+    int B, h, w, Hg, Wg, eigen, gtpos, y0, y1, x0, x1, nbx, scaling;   // eigen: evaluate_depth.py's per-image protocol (either mask)
     float ry, rx, scale_factor;
 };
 
@@ -45,7 +46,7 @@ __device__ __forceinline__ bool mt_pixel(const MtArgs& a, int b, int j, float& g
     const int cw = a.x1 - a.x0;
     const int oy = a.y0 + j / cw, ox = a.x0 + j % cw;
     g = a.gt[((size_t)b * a.Hg + oy) * a.Wg + ox];
-    const bool ok = a.eigen ? (g > 1e-3f && g < 80.f) : (g > 0.f);
+    const bool ok = (a.eigen && !a.gtpos) ? (g > 1e-3f && g < 80.f) : (g > 0.f);
     if (!ok) return false;
     const float v = bilinear_at(a.pred + (size_t)b * a.h * a.w, a.h, a.w, a.Hg, a.Wg, oy, ox, a.ry, a.rx);
     if (a.eigen) p = (1.0f / v) * a.scale_factor;              // evaluate_depth.py:203, 219
@@ -276,12 +277,17 @@ struct MtLayout {
 
 static bool mt_layout(const dc_depth_eval_desc* d, MtArgs& a, MtLayout& L) {
     if (!d || d->B <= 0 || d->h <= 0 || d->w <= 0 || d->Hg <= 0 || d->Wg <= 0 ||
-        (d->protocol != DC_EVAL_TRAINER && d->protocol != DC_EVAL_EIGEN))
+        (d->protocol != DC_EVAL_TRAINER && d->protocol != DC_EVAL_EIGEN && d->protocol != DC_EVAL_GT_POSITIVE))
         return false;
     a.B = d->B; a.h = d->h; a.w = d->w; a.Hg = d->Hg; a.Wg = d->Wg;
-    a.eigen = d->protocol == DC_EVAL_EIGEN;
-    a.y0 = max(d->crop[0], 0); a.y1 = min(d->crop[1], d->Hg);
-    a.x0 = max(d->crop[2], 0); a.x1 = min(d->crop[3], d->Wg);
+    a.eigen = d->protocol != DC_EVAL_TRAINER;
+    a.gtpos = d->protocol == DC_EVAL_GT_POSITIVE;
+    if (a.gtpos) {                                             // evaluate_depth.py:210-211: the whole frame
+        a.y0 = 0; a.y1 = d->Hg; a.x0 = 0; a.x1 = d->Wg;
+    } else {
+        a.y0 = max(d->crop[0], 0); a.y1 = min(d->crop[1], d->Hg);
+        a.x0 = max(d->crop[2], 0); a.x1 = min(d->crop[3], d->Wg);
+    }
     if (a.y1 < a.y0) a.y1 = a.y0;
     if (a.x1 < a.x0) a.x1 = a.x0;
     const long long npix = (long long)(a.y1 - a.y0) * (a.x1 - a.x0);

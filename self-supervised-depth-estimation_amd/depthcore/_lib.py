@@ -33,7 +33,7 @@ _ERR = {-1: "DC_EINVAL (bad shape / null pointer / unsupported option)",
         -3: "DC_EWORKSPACE (workspace too small)",
         -4: "DC_EEMPTY (mask selects no pixel)"}
 DC_EEMPTY = -4
-EVAL_TRAINER, EVAL_EIGEN = 0, 1
+EVAL_TRAINER, EVAL_EIGEN, EVAL_GT_POSITIVE = 0, 1, 2
 
 
 class DepthcoreError(RuntimeError):
@@ -144,6 +144,9 @@ def _sig(lib):
         "dc_bn_eval_bwd": (i, [p, p, p, p, p, p, p, p, p, p, p, i, i, i, i, p]),
         "dc_depth_errors_workspace": (z, [POINTER(DepthEvalDesc)]),
         "dc_depth_errors": (i, [POINTER(DepthEvalDesc), p, p, p, p, p]),
+        "dc_flip_concat": (i, [p, p, i, i, i, i, p]),
+        "dc_disp_post_process": (i, [p, p, i, i, i, f, f, p]),
+        "dc_depth_png16": (i, [p, p, i, i, i, i, i, f, p]),
         "dc_bn_bwd_finalize": (i, [p, i, i, c_double, p, p, p, p, p, p, i, i, p]),
         "dc_bn_bwd_apply": (i, [p, p, p, p, i, i, i, i, p]),
         "dc_conv1x1_bn_ok": (i, [i, i, i, i, i]),

@@ -1038,6 +1038,7 @@ def bn_eval(x, bn, res=None, relu=True):
 # depth metrics of validation  (trainer.py:624-652, evaluate_depth.py:190-235, layers.py:251-269)
 # ----------------------------------------------------------------------------------------------
 TRAINER_CROP = (153, 371, 44, 1197)      # trainer.py:638 (garg / eigen crop of a 375 x 1242 frame)
+_PROTOCOLS = {"trainer": _lib.EVAL_TRAINER, "eigen": _lib.EVAL_EIGEN, "gt_positive": _lib.EVAL_GT_POSITIVE}
 
 
 def eigen_crop(Hg, Wg):
@@ -1047,24 +1048,28 @@ def eigen_crop(Hg, Wg):
     return tuple(int(v) for v in c)
 
 
-def _depth_errors(pred, gt, protocol, crop, median_scaling, scale_factor):
-    """-> (metrics (G, 7), ratios (G,), host copy of [metrics | ratios | status]) after ONE device-to-host copy."""
-    if protocol not in ("trainer", "eigen"):
-        raise ValueError("protocol: 'trainer' (trainer.py:624-652) or 'eigen' (evaluate_depth.py:190-235)")
+def _depth_errors(pred, gt, protocol, crop, median_scaling, scale_factor, image_ids=None):
+    """-> (metrics (G, 7), ratios (G,), host copy of [metrics | ratios | status]) after ONE device-to-host copy.
+    image_ids: the caller's numbers of the B images, for the error message of an empty mask."""
+    if protocol not in _PROTOCOLS:
+        raise ValueError("protocol: 'trainer' (trainer.py:624-652), 'eigen' (evaluate_depth.py:190-235) or 'gt_positive' "
+                         "(evaluate_depth.py:210-211)")
     L = _lib.lib()
     p, g = _c(pred.detach()), _c(gt.detach())
     if p.dim() != 4 or g.dim() != 4 or p.shape[1] != 1 or g.shape[1] != 1 or p.shape[0] != g.shape[0]:
         raise DepthcoreError("depth_errors: pred (B,1,h,w) and gt (B,1,Hg,Wg), got %s and %s" % (tuple(p.shape), tuple(g.shape)))
     B, _, h, w = p.shape
     Hg, Wg = g.shape[-2:]
-    eigen = protocol == "eigen"
-    if crop is None:
+    eigen = protocol != "trainer"                  # per-image groups (either mask of evaluate_depth.py)
+    if protocol == "gt_positive":
+        crop = (0, Hg, 0, Wg)                       # the whole frame (the kernel ignores crop for this protocol)
+    elif crop is None:
         crop = eigen_crop(Hg, Wg) if eigen else TRAINER_CROP
     G = B if eigen else 1
     buf = torch.empty(G * 9, dtype=torch.float32, device=p.device)       # metrics | ratios | status (int32)
     d = _lib.DepthEvalDesc()
     d.B, d.h, d.w, d.Hg, d.Wg = B, h, w, Hg, Wg
-    d.protocol = _lib.EVAL_EIGEN if eigen else _lib.EVAL_TRAINER
+    d.protocol = _PROTOCOLS[protocol]
     for i in range(4):
         d.crop[i] = int(crop[i])
     d.median_scaling = int(bool(median_scaling))
@@ -1077,7 +1082,7 @@ def _depth_errors(pred, gt, protocol, crop, median_scaling, scale_factor):
     host = buf.cpu()
     bad = [i for i, v in enumerate(host[G * 8:].view(torch.int32).tolist()) if v != 0]
     if bad:
-        what = ("image %d of the batch" % bad[0]) if eigen else "the batch"
+        what = ("image %d" % image_ids[bad[0]] if image_ids is not None else "image %d of the batch" % bad[0]) if eigen else "the batch"
         raise DepthcoreError("depth_errors (%s protocol): the mask of %s selects no pixel (%s)" % (protocol, what, _lib._ERR.get(
             host[G * 8:].view(torch.int32)[bad[0]].item(), "status %d")))
     return buf[:G * 7].view(G, 7), buf[G * 7:G * 8], host
@@ -1091,12 +1096,65 @@ def depth_errors(pred, gt, protocol="trainer", crop=None, median_scaling=True, s
         rows 153:371, cols 44:1197); torch.median; one ratio for the whole batch.  Returns a (7,) device tensor.
       protocol="eigen": evaluate_depth.py:198-232 -- pred is scaled disparity (depth = 1 / disp * scale_factor);
         1e-3 < gt < 80 inside the fractional Eigen crop; np.median; per image.  Returns ((B, 7), ratios (B,)).
+      protocol="gt_positive": as "eigen" but the mask is gt > 0 over the whole frame (`crop` is not used) -- every split
+        but "eigen" in evaluate_depth.py:210-211 (eigen_benchmark).  Returns ((B, 7), ratios (B,)).
     median_scaling=False: --disable_median_scaling (ratios are then 1).  A group whose mask selects no pixel raises
     DepthcoreError naming it (this waits for the result: one small device-to-host copy per call)."""
     out, ratios, _ = _depth_errors(pred, gt, protocol, crop, median_scaling, scale_factor)
     if protocol == "trainer":
         return out[0]
     return out, ratios
+
+
+# ----------------------------------------------------------------------------------------------
+# depth evaluation: the prediction side of evaluate_depth.py:95-135 and its benchmark export (:159-171)
+# ----------------------------------------------------------------------------------------------
+def flip_concat(x):
+    """torch.cat((x, torch.flip(x, [3])), 0) of evaluate_depth.py:123 in one launch (dc_flip_concat): (B,C,H,W) -> (2B,C,H,W).
+    No gradient (an evaluation input)."""
+    L = _lib.lib()
+    xx = _c(x.detach())
+    if xx.dim() != 4:
+        raise DepthcoreError("flip_concat: (B,C,H,W), got %s" % (tuple(xx.shape),))
+    B, C, H, W = xx.shape
+    out = torch.empty((2 * B, C, H, W), dtype=torch.float32, device=xx.device)
+    check(L.dc_flip_concat(ptr(xx), ptr(out), B, C, H, W, stream(xx)), "dc_flip_concat")
+    return out
+
+
+def post_process_disparity(disp, min_depth, max_depth):
+    """The decoder's sigmoid disparity (2B,1,h,w) of the batch [x; flip_w(x)] -> (B,1,h,w) post-processed scaled disparity
+    (dc_disp_post_process): disp_to_depth's scaled disparity of both halves (bit for bit ops.disp_to_depth's), the second
+    mirrored back, blended as batch_post_process_disparity (evaluate_depth.py:48-56) in its own types -- fp32 mean, fp64 masks
+    and products -- and rounded to fp32 once.  No gradient."""
+    L = _lib.lib()
+    d = _c(disp.detach())
+    if d.dim() != 4 or d.shape[1] != 1 or d.shape[0] % 2:
+        raise DepthcoreError("post_process_disparity: (2B,1,h,w), got %s" % (tuple(d.shape),))
+    B, _, h, w = d.shape
+    out = torch.empty((B // 2, 1, h, w), dtype=torch.float32, device=d.device)
+    check(L.dc_disp_post_process(ptr(d), ptr(out), B // 2, h, w, float(min_depth), float(max_depth), stream(d)),
+          "dc_disp_post_process")
+    return out
+
+
+STEREO_SCALE_FACTOR = 5.4       # evaluate_depth.py:24
+BENCHMARK_SIZE = (352, 1216)    # evaluate_depth.py:166 (cv2's (width, height) = (1216, 352))
+
+
+def depth_png16(disp, size=BENCHMARK_SIZE, scale=STEREO_SCALE_FACTOR):
+    """KITTI benchmark depth maps of evaluate_depth.py:165-169 (dc_depth_png16): scaled disparity (N,1,h,w) ->
+    (N, Ho, Wo) uint16 = uint16(clip(scale / bilinear(disp), 0, 80) * 256), the upsample F.interpolate(bilinear,
+    align_corners=False)'s (bit for bit ops.upsample_bilinear's).  The PNG encoding is the caller's."""
+    L = _lib.lib()
+    d = _c(disp.detach())
+    if d.dim() != 4 or d.shape[1] != 1:
+        raise DepthcoreError("depth_png16: (N,1,h,w), got %s" % (tuple(d.shape),))
+    N, _, h, w = d.shape
+    Ho, Wo = int(size[0]), int(size[1])
+    out = torch.empty((N, Ho, Wo), dtype=torch.uint16, device=d.device)
+    check(L.dc_depth_png16(ptr(d), out.data_ptr(), N, h, w, Ho, Wo, float(scale), stream(d)), "dc_depth_png16")
+    return out
 
 
 # ----------------------------------------------------------------------------------------------
