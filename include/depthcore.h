@@ -489,10 +489,13 @@ int dc_bias_act_bwd(const float* y, const float* gy, float* gpre, float* dbias, 
  * pose encoder, the temporal pair concat `torch.cat([f_a, f_b], 1)` of trainer.py:398-412 are index arithmetic of the
  * kernels' patch loader (the same two IEEE operations per pixel; conv1's zero padding stays zero), so neither the
  * normalised image nor the 6-channel pair tensor exists in HBM.
- *   frames: HOST array of nf device pointers, each (Bf,3,Hi,Wi).  nf = 1: Ci = 3, output batch Bf.  nf = 3: the two pairs
+ *   frames: HOST array of nf device pointers, each (Bf,3,Hi,Wi).  nf = 1: Ci = 3, output batch Bf.  nf = 2: ONE pair group --
+ *   Ci = 6, output batch Bf, item b = cat(f0[b], f1[b]); the two pointers may be overlapping views of one tensor (X[i : i+Bf]
+ *   and X[i+1 : i+Bf+1] of a resident sequence: pair b = (frame i+b, frame i+b+1), each frame read twice, no pair tensor) --
+ *   the evaluation layout of evaluate_pose.py:94-96.  dc_stem_wgrad takes nf = 2 as well (the loader is shared).  nf = 3: the two pairs
  *   (f0,f1), (f1,f2) stacked along the batch -- output batch 2*Bf, item b < Bf = cat(f0[b], f1[b]), item Bf + b = cat(f1[b],
  *   f2[b]) (= trainer.py's pairs (-1,0), (0,+1) for frames (f-1, f0, f+1)).
- *   weight (64, 3 or 6, 7, 7); y / gy (Bf or 2*Bf, 64, Hi/2, Wi/2); ws: dc_convs2_fwd_workspace / _wgrad_workspace bytes of
+ *   weight (64, 3 or 6, 7, 7); y / gy (Bf (nf = 1, 2) or 2*Bf (nf = 3), 64, Hi/2, Wi/2); ws: dc_convs2_fwd_workspace / _wgrad_workspace bytes of
  *   the equivalent dc_convs2_* call (B = output batch, Ci, ksize 7).  Same arithmetic as dc_convs2_fwd / _wgrad on the
  *   materialised input, bit for bit.  No data gradient (the input is the image). */
 int dc_stem_supported(int nf, int Bf, int Co, int Hi, int Wi);
@@ -765,6 +768,19 @@ int dc_depth_errors(const dc_depth_eval_desc* d, const float* pred, const float*
 int dc_flip_concat(const float* x, float* out, int B, int C, int H, int W, void* stream);
 int dc_disp_post_process(const float* disp, float* out, int B, int h, int w, float min_depth, float max_depth, void* stream);
 int dc_depth_png16(const float* disp, uint16_t* out, int N, int h, int w, int Ho, int Wo, float scale, void* stream);
+
+/* ------------------------------------------------------------------ pose evaluation (evaluate_pose.py)
+ * Absolute trajectory error of 5-frame snippets, evaluate_pose.py:23-46 (dump_xyz, compute_ate) and :104-125 (csrc/pose_eval.hip).
+ *   pred (N,4,4) fp32: the pose network's source-to-target transform of every consecutive frame pair;
+ *   gt_global (M,3,4) fp64: the rows of KITTI's poses/XX.txt; N must be M - 1 (DC_EINVAL otherwise), track_length >= 1 (5).
+ *   out (M - 1 + 2) fp64: ates[i] of snippet i, then np.mean(ates) and np.std(ates) -- one buffer, so one device-to-host copy.
+ * All arithmetic in fp64 (predictions widened on load).  Ground-truth local pose j = inv(inv(G[j]) G[j+1]) with the general
+ * affine inverse (the files' rotations are orthogonal to ~1e-6 only).  Snippet i chains pred[i : i+track_length-1] and the local
+ * poses of the same range, clipped at the end of the arrays (the last snippets have fewer points); its ATE is compute_ate's:
+ * first points aligned, scale = sum(gt * pred) / sum(pred^2), sqrt(sum((pred * scale - gt)^2)) / points.  A snippet whose
+ * predicted points all coincide is 0 / 0 = NaN as in numpy (and so are mean and std); that is not an error.  Mean and std by a
+ * fixed-order two-pass reduction: bitwise reproducible.  Two launches, no host synchronisation. */
+int dc_pose_ate(const float* pred, const double* gt_global, double* out, int N, int M, int track_length, void* stream);
 
 #ifdef __cplusplus
 }

@@ -554,7 +554,8 @@ constexpr int ST_TH = 2, ST_TW = 64, ST_PW = 68, ST_ROWS = 2 * ST_TH + 5, ST_ROW
 struct StemArgs {
     const float* x; const float* w; const float* gy; float* out;
     // raw-frame mode (dc_stem_fwd / dc_stem_wgrad): nf > 0 frames (Bf,3,Hi,Wi); the network input is (x - mean) / stdv of
-    // frames[0] (nf = 1, Ci = 3) or of the temporal pairs cat(f[p], f[p+1]) stacked along the batch (nf = 3: B = 2 Bf, Ci = 6)
+    // frames[0] (nf = 1, Ci = 3), of the one pair group cat(f[0], f[1]) (nf = 2: B = Bf, Ci = 6; the two may be overlapping views
+    // of one sequence) or of the temporal pairs cat(f[p], f[p+1]) stacked along the batch (nf = 3: B = 2 Bf, Ci = 6)
     const float* f[3]; int nf, Bf; float mean, stdv;
     int B, Ci, Co, Hi, Wi, Ho, Wo, K, Kp;
     int tiles_x, tiles_y, ntiles;     // tiles per row, per image column, total (B * tiles_y * tiles_x)
@@ -1233,8 +1234,8 @@ extern "C" int dc_convs2_wgrad(const float* x, const float* gy, float* dweight, 
 
 // ---- the stem on the RAW frames: normalisation and temporal pair concat folded into the patch loader -------------------------
 static int stem_frames(StemArgs& sa, const float* const* frames, int nf, float mean, float stdv, int Bf, int Hi, int Wi, int Co) {
-    if (!frames || (nf != 1 && nf != 3) || !(stdv > 0.f) || Bf <= 0) return DC_EINVAL;
-    const int B = nf == 3 ? 2 * Bf : Bf, Ci = nf == 3 ? 6 : 3;
+    if (!frames || nf < 1 || nf > 3 || !(stdv > 0.f) || Bf <= 0) return DC_EINVAL;
+    const int B = nf == 3 ? 2 * Bf : Bf, Ci = nf == 1 ? 3 : 6;
     if (!cg_ok(B, Ci, Co, Hi, Wi, 7) || !stem_ok(Ci, Co, 7)) return DC_EINVAL;
     for (int i = 0; i < nf; ++i)
         if (!frames[i]) return DC_EINVAL;
@@ -1245,8 +1246,8 @@ static int stem_frames(StemArgs& sa, const float* const* frames, int nf, float m
 }
 
 extern "C" int dc_stem_supported(int nf, int Bf, int Co, int Hi, int Wi) {
-    if ((nf != 1 && nf != 3) || Bf <= 0) return 0;
-    const int B = nf == 3 ? 2 * Bf : Bf, Ci = nf == 3 ? 6 : 3;
+    if (nf < 1 || nf > 3 || Bf <= 0) return 0;
+    const int B = nf == 3 ? 2 * Bf : Bf, Ci = nf == 1 ? 3 : 6;
     return (cg_ok(B, Ci, Co, Hi, Wi, 7) && stem_ok(Ci, Co, 7)) ? 1 : 0;
 }
 

@@ -1,4 +1,5 @@
-"""Depth evaluation of a trained model: the reference's evaluate_depth.py (lines 59-235) as two library calls.
+"""Evaluation of trained models: the reference's evaluate_depth.py (lines 59-235) and evaluate_pose.py (lines 49-129), each as two
+library calls.
 
   predict_disparities  -- lines 95-135: the networks in eval mode under no_grad, disp_to_depth's scaled disparity of every
                           image, optionally flip post-processed (ops.flip_concat, ops.post_process_disparity);
@@ -6,8 +7,13 @@
                           the split's mask, median scaling or a fixed scale factor, the clamp and the seven errors
                           (ops.depth_errors), then the mean over the images and the statistics of the median ratios.
 
-Everything that touches a pixel runs on depthcore's kernels; the host sees the (N, 7) errors and (N,) ratios only.
-The drop-in script `evaluate_depth.py` next to `trainer.py` wraps both with the reference's options."""
+  predict_poses        -- evaluate_pose.py:89-102: every consecutive frame pair of a sequence through the pose network in eval
+                          mode, the pair formed by the stem kernel's loader (ResnetEncoder.forward_pair);
+  evaluate_pose        -- evaluate_pose.py:104-125: the absolute trajectory error of every snippet (ops.pose_ate).
+
+Everything that touches a pixel runs on depthcore's kernels; the host sees the (N, 7) errors and (N,) ratios, or the (N,) ATEs
+with their mean and std, only.  The drop-in scripts `evaluate_depth.py` / `evaluate_pose.py` next to `trainer.py` wrap them
+with the reference's options."""
 import collections
 
 import numpy as np
@@ -97,7 +103,7 @@ def evaluate_depth(pred_disps, gt_depths, split="eigen", median_scaling=True, sc
     -> dict(errors (N,7) float32 per image, ratios (N,) float32 or None, mean_errors (7,) float64 -- the mean over the images,
     ratio_median = np.median(ratios), ratio_std = np.std(ratios / ratio_median) (None without median scaling), names)."""
     if split.startswith("odom"):
-        raise ValueError("split %r: the odometry splits are pose evaluation (evaluate_pose.py), not depth" % split)
+        raise ValueError("split %r: the odometry splits are pose evaluation (evaluate_pose / evaluate_pose.py), not depth" % split)
     protocol = "eigen" if split == "eigen" else "gt_positive"
     if not torch.is_tensor(pred_disps):
         pred_disps = torch.from_numpy(np.ascontiguousarray(pred_disps, np.float32))
@@ -137,3 +143,94 @@ def evaluate_depth(pred_disps, gt_depths, split="eigen", median_scaling=True, sc
         med = np.median(ratios)                                   # evaluate_depth.py:228-230, fp32 as there
         res.update(ratios=ratios, ratio_median=float(med), ratio_std=float(np.std(ratios / med)))
     return res
+
+
+def _pair_groups(frames, batch_size):
+    """(f_a, f_b) views of up to batch_size consecutive pairs: f_a[b], f_b[b] are frames i+b, i+b+1 of the sequence.  A tensor is
+    sliced in place.  Chunks of an iterable are gathered in a staging buffer of batch_size + 1 frames whose last frame is
+    carried over to slot 0 -- the same groups as for the tensor, whatever the chunk sizes; no pair tensor either way."""
+    if torch.is_tensor(frames):
+        for i0 in range(0, frames.shape[0] - 1, batch_size):
+            b = min(batch_size, frames.shape[0] - 1 - i0)
+            yield frames[i0:i0 + b], frames[i0 + 1:i0 + b + 1]
+        return
+    buf, k = None, 0
+    for chunk in frames:
+        if chunk.dim() != 4 or chunk.shape[1] != 3 or chunk.dtype != torch.float32:
+            raise _lib.DepthcoreError("predict_poses: a chunk must be (n,3,h,w) float32, got %s %s" % (tuple(chunk.shape), chunk.dtype))
+        if buf is None:
+            if not chunk.is_cuda:
+                raise _lib.DepthcoreError("predict_poses: frames must live on the device (got %s)" % chunk.device)
+            buf = torch.empty((batch_size + 1, 3) + tuple(chunk.shape[2:]), dtype=torch.float32, device=chunk.device)
+        if chunk.shape[2:] != buf.shape[2:]:
+            raise _lib.DepthcoreError("predict_poses: the chunks differ in their image size")
+        c0 = 0
+        while c0 < chunk.shape[0]:
+            n = min(batch_size + 1 - k, chunk.shape[0] - c0)
+            buf[k:k + n].copy_(chunk[c0:c0 + n])                     # staging copy
+            k, c0 = k + n, c0 + n
+            if k == batch_size + 1:
+                yield buf[:batch_size], buf[1:]
+                buf[0:1].copy_(buf[batch_size:])                     # staging copy: the carried frame
+                k = 1
+    if k >= 2:
+        yield buf[:k - 1], buf[1:k]
+
+
+def predict_poses(pose_encoder, pose_decoder, frames, batch_size=16):
+    """evaluate_pose.py:89-102 -> (N,4,4) float32 source-to-target transforms on the device, one per consecutive frame pair.
+
+    `frames`: the N+1 consecutive frames of a sequence at the network's resolution -- a (N+1,3,h,w) float32 device tensor, or an
+    iterable of chunks (n,3,h,w) of consecutive frames.  Pair i goes in as (frame i, frame i+1) and its matrix is
+    transformation_from_parameters(axisangle[:, 0], translation[:, 0]), not inverted (lines 94-100).  The networks are the ones
+    the reference evaluates: ResnetEncoder(num_layers, False, 2) and PoseDecoder(num_ch_enc, 1, 2).  They run in eval mode
+    under no_grad; every submodule's `training` flag is restored on exit, and parameters and BatchNorm running statistics are
+    not touched (the contract of predict_disparities)."""
+    if batch_size <= 0:
+        raise ValueError("batch_size must be positive")
+    if not hasattr(pose_encoder, "forward_pair") or not hasattr(pose_decoder, "forward_poses"):
+        raise NotImplementedError("predict_poses evaluates ResnetEncoder(num_layers, False, 2) + PoseDecoder(num_ch_enc, 1, 2) "
+                                  "(--pose_model_type separate_resnet), as the reference's evaluate_pose.py does")
+    if torch.is_tensor(frames) and (frames.dim() != 4 or frames.shape[1] != 3 or frames.dtype != torch.float32 or not frames.is_cuda):
+        raise _lib.DepthcoreError("predict_poses: frames must be a (N+1,3,h,w) float32 device tensor, got %s %s on %s"
+                                  % (tuple(frames.shape), frames.dtype, frames.device))
+    flags = [(m, m.training) for net in (pose_encoder, pose_decoder) for m in net.modules()]
+    outs = []
+    try:
+        pose_encoder.eval()
+        pose_decoder.eval()
+        with torch.no_grad():
+            for f_a, f_b in _pair_groups(frames, batch_size):
+                features = [pose_encoder.forward_pair(f_a, f_b)]
+                outs.append(pose_decoder.forward_poses(features, [(0, f_a.shape[0], 0, 0)])[2][0])
+    finally:
+        for m, t in flags:
+            m.training = t
+    if not outs:
+        raise ValueError("predict_poses: a sequence needs at least two frames")
+    return outs[0] if len(outs) == 1 else ops.stack_frames([outs])[0]
+
+
+def evaluate_pose(pred_poses, gt_global_poses, track_length=5):
+    """evaluate_pose.py:104-125 on the device.
+
+    pred_poses:      (N,4,4) float32 transforms of predict_poses -- a device tensor, or host data that is copied over.
+    gt_global_poses: the N+1 global poses of KITTI's poses/XX.txt, (N+1,3,4) or (N+1,12), host or device data; compared in fp64.
+    -> dict(ates (N,) float64 -- the absolute trajectory error of the snippet starting at each frame, mean = np.mean(ates),
+    std = np.std(ates), track_length).  A snippet whose predicted points all coincide is NaN, as in numpy."""
+    if not torch.is_tensor(pred_poses):
+        pred_poses = torch.from_numpy(np.ascontiguousarray(pred_poses, np.float32))
+    if not torch.is_tensor(gt_global_poses):
+        gt_global_poses = torch.from_numpy(np.ascontiguousarray(gt_global_poses, np.float64))
+    if pred_poses.dim() != 3 or tuple(pred_poses.shape[1:]) != (4, 4):
+        raise ValueError("evaluate_pose: pred_poses must be (N,4,4), got %s" % (tuple(pred_poses.shape),))
+    if gt_global_poses.dim() not in (2, 3) or gt_global_poses[0].numel() != 12:
+        raise ValueError("evaluate_pose: gt_global_poses must be (M,3,4) or (M,12), got %s" % (tuple(gt_global_poses.shape),))
+    N, M = pred_poses.shape[0], gt_global_poses.shape[0]
+    if N < 1 or N != M - 1:
+        raise ValueError("evaluate_pose: %d predicted transforms (frame pairs) need %d ground-truth poses, got %d" % (N, N + 1, M))
+    dev = pred_poses.device if pred_poses.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    pred = pred_poses.to(device=dev, dtype=torch.float32)
+    gt = gt_global_poses.to(device=dev, dtype=torch.float64).reshape(M, 3, 4)
+    ates, mean, std = ops.pose_ate(pred, gt, track_length)
+    return {"ates": ates.numpy(), "mean": float(mean), "std": float(std), "track_length": int(track_length)}

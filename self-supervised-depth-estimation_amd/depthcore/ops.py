@@ -1107,6 +1107,29 @@ def depth_errors(pred, gt, protocol="trainer", crop=None, median_scaling=True, s
 
 
 # ----------------------------------------------------------------------------------------------
+# pose evaluation: the trajectory scoring of evaluate_pose.py:23-46, 104-125
+# ----------------------------------------------------------------------------------------------
+def pose_ate(pred, gt_global, track_length=5):
+    """Absolute trajectory error of every `track_length`-frame snippet (dc_pose_ate: fp64, two launches, bitwise reproducible).
+    pred (N,4,4) float32 source-to-target transforms on the device; gt_global (N+1,3,4) float64 rows of KITTI's poses/XX.txt
+    on the device.  -> (ates (N,), mean, std) as views of ONE host float64 tensor: the call ends with the only device-to-host
+    copy.  A snippet whose predicted points all coincide is NaN (0 / 0 as in numpy), and so are mean and std then."""
+    L = _lib.lib()
+    p, g = _c(pred.detach()), _c(gt_global.detach())
+    if p.dim() != 3 or tuple(p.shape[1:]) != (4, 4) or g.dim() != 3 or tuple(g.shape[1:]) != (3, 4):
+        raise DepthcoreError("pose_ate: pred (N,4,4) and gt_global (M,3,4), got %s and %s" % (tuple(p.shape), tuple(g.shape)))
+    N, M = p.shape[0], g.shape[0]
+    if M < 2 or N != M - 1:
+        raise DepthcoreError("pose_ate: %d predicted transforms need %d ground-truth poses, got %d" % (N, N + 1, M))
+    if int(track_length) < 1:
+        raise DepthcoreError("pose_ate: track_length must be at least 1")
+    out = torch.empty(N + 2, dtype=torch.float64, device=p.device)
+    check(L.dc_pose_ate(ptr(p), ptr(g, torch.float64), ptr(out, torch.float64), N, M, int(track_length), stream(p)), "dc_pose_ate")
+    host = out.cpu()
+    return host[:N], host[N], host[N + 1]
+
+
+# ----------------------------------------------------------------------------------------------
 # depth evaluation: the prediction side of evaluate_depth.py:95-135 and its benchmark export (:159-171)
 # ----------------------------------------------------------------------------------------------
 def flip_concat(x):
@@ -1550,8 +1573,8 @@ def conv2d_direct(x, weight, bias=None, stride=1, padding=0):
 # ----------------------------------------------------------------------------------------------
 def stem_supported(frames, weight):
     f0 = frames[0]
-    return (f0.is_cuda and f0.dtype == torch.float32 and len(frames) in (1, 3) and f0.shape[1] == 3
-            and tuple(weight.shape[1:]) == (3 * (2 if len(frames) == 3 else 1), 7, 7)
+    return (f0.is_cuda and f0.dtype == torch.float32 and len(frames) in (1, 2, 3) and f0.shape[1] == 3
+            and tuple(weight.shape[1:]) == (3 * (1 if len(frames) == 1 else 2), 7, 7)
             and all(t.shape == f0.shape and not t.requires_grad for t in frames)
             and bool(_lib.lib().dc_stem_supported(len(frames), f0.shape[0], weight.shape[0], f0.shape[2], f0.shape[3])))
 
@@ -1565,7 +1588,7 @@ class _StemConv(torch.autograd.Function):
         nf = len(fr)
         Bf, _, Hi, Wi = fr[0].shape
         Co = ww.shape[0]
-        B, Ci = (2 * Bf, 6) if nf == 3 else (Bf, 3)
+        B, Ci = (2 * Bf if nf == 3 else Bf), (3 if nf == 1 else 6)
         ptrs = (ctypes.c_void_p * nf)(*[ptr(t) for t in fr])
         y = torch.empty(B, Co, Hi // 2, Wi // 2, dtype=torch.float32, device=ww.device)
         _use_precision(_lib.PREC_F32)                      # (the stem has no reduced-precision kernel: 3 / 6 input channels)
@@ -1585,7 +1608,7 @@ class _StemConv(torch.autograd.Function):
         nf = len(fr)
         Bf, _, Hi, Wi = fr[0].shape
         Co = ww.shape[0]
-        B, Ci = (2 * Bf, 6) if nf == 3 else (Bf, 3)
+        B, Ci = (2 * Bf if nf == 3 else Bf), (3 if nf == 1 else 6)
         g_c = _c(gy)
         gw = None
         if ctx.needs_input_grad[0]:
@@ -1599,9 +1622,10 @@ class _StemConv(torch.autograd.Function):
 
 
 def stem_conv(frames, weight, mean=0.45, std=0.225):
-    """conv2d((x - mean) / std, weight, stride 2, padding 3) with x = frames[0] (one frame) or, for three frames (f-1, f0, f+1),
-    the two temporal pairs cat(f-1, f0), cat(f0, f+1) stacked along the batch -- neither the normalised image nor the pair
-    tensor is materialised.  Frames are inputs (no gradient)."""
+    """conv2d((x - mean) / std, weight, stride 2, padding 3) with x = frames[0] (one frame), the pairs cat(f_a, f_b) of two
+    frame tensors (which may be overlapping views X[i:i+B], X[i+1:i+B+1] of one sequence: the evaluation layout) or, for three
+    frames (f-1, f0, f+1), the two temporal pairs cat(f-1, f0), cat(f0, f+1) stacked along the batch -- neither the normalised
+    image nor the pair tensor is materialised.  Frames are inputs (no gradient)."""
     return _StemConv.apply(weight, mean, std, *frames)
 
 

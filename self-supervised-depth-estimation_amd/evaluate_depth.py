@@ -87,7 +87,7 @@ def load_networks(opt, device):
 def evaluate(opt):
     """evaluate_depth.py:59-236.  Returns the result of depthcore.evaluate.evaluate_depth, or None when nothing is scored."""
     if opt.eval_split.startswith("odom"):
-        raise ValueError("eval_split %r is pose evaluation (evaluate_pose.py), which this project does not provide" % opt.eval_split)
+        raise ValueError("eval_split %r is pose evaluation: run evaluate_pose.py" % opt.eval_split)
     if getattr(opt, "fusion", None) or getattr(opt, "gru", None):
         raise NotImplementedError(
             "evaluating the %s front-end: the reference's evaluate_depth_fusion_v3.py concatenates the flipped stack so that "

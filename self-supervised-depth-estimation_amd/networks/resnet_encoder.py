@@ -359,6 +359,15 @@ class ResnetEncoder(nn.Module):
         pairs = torch.cat([torch.cat([f_prev, f_cur], 1), torch.cat([f_cur, f_next], 1)], 0)
         return self.forward(pairs, bn_groups=2)
 
+    def forward_pair(self, f_a, f_b):
+        """One pair group of the pose network: equals `forward(cat([f_a, f_b], 1))` (evaluate_pose.py:94-96), with the
+        concatenation and the input normalisation done by the stem kernel's loader when the shapes allow.  f_a, f_b may be
+        overlapping views X[i:i+B], X[i+1:i+B+1] of one sequence: pair b is then (frame i+b, frame i+b+1)."""
+        frames = (f_a, f_b)
+        if STEM_FUSED and _ops.stem_supported(frames, self.encoder.conv1.weight):
+            return self._trunk(_ops.stem_conv(frames, self.encoder.conv1.weight), 1)
+        return self.forward(torch.cat([f_a, f_b], 1))
+
     def forward(self, input_image, bn_groups=1):
         """networks/resnet_encoder.py:87-98.  `bn_groups` > 1: `input_image` stacks that many independent
         sub-batches along dim 0; BatchNorm statistics (and running-stat updates) are kept per sub-batch, so the
