@@ -782,6 +782,26 @@ int dc_depth_png16(const float* disp, uint16_t* out, int N, int h, int w, int Ho
  * fixed-order two-pass reduction: bitwise reproducible.  Two launches, no host synchronisation. */
 int dc_pose_ate(const float* pred, const double* gt_global, double* out, int N, int M, int track_length, void* stream);
 
+/* ------------------------------------------------------------------ disparity rendering (test_simple.py)
+ * The colour image of test_simple.py:126-145 (csrc/render.hip): the disparity upsampled to the photo's size, vmin = min,
+ * vmax = np.percentile(., q), matplotlib's Normalize and a 256-entry colour table.
+ *   disp (N,1,h,w) fp32; lut (256,3) uint8 on the device; rgb (N,Ho,Wo,3) uint8, interleaved (PIL.Image.fromarray's layout),
+ *   4-byte aligned; range (N,2) fp32 = (vmin, vmax) of every image -- each image has its own.  q in [0, 100] (95).
+ * With d the upsampled map of one image (F.interpolate(bilinear, align_corners=False), bit for bit dc_upsample_bilinear_fwd,
+ * recomputed in every pass and never stored), n = Ho*Wo and s = d sorted ascending:
+ *   vmin = s[0];  vi = (n-1) * (q/100) in fp64, lo = floor(vi), hi = min(lo+1, n-1), g = vi - lo, a = s[lo], b = s[hi],
+ *   diff = fp32(b - a), vmax = fp32(g < 0.5 ? fp64(a) + fp64(diff)*g : fp64(b) - fp64(diff)*(1-g))   (numpy's _lerp; the fp64
+ *   virtual index of numpy 1.x -- numpy 2.x forms it in the array's fp32).  s[lo], s[hi] are exact order statistics by radix
+ *   selection over order-preserving uint32 keys (three integer-histogram passes, integer minima): no sort.
+ *   vmin == vmax: every index is 0.  Otherwise x = fp32(fp64(d) - fp64(vmin)), x = fp32(fp64(x) / (fp64(vmax) - fp64(vmin))),
+ *   xa = x * 256.0f in fp32, idx = xa < 0 ? 0 : min((int)xa, 255) (above vmax: the last colour), rgb = lut[idx].
+ * Non-finite input is outside the contract (the decoder's output is a sigmoid).  No floating-point atomics: two calls give
+ * the same bytes.  Eight launches, no host synchronisation.  ws: dc_disp_render_ws_bytes(...) bytes (0 for a bad shape);
+ * DC_EWORKSPACE when ws_bytes is smaller.  N, h, w, Ho, Wo < 1, N > 65535, q outside [0, 100], null pointers: DC_EINVAL. */
+size_t dc_disp_render_ws_bytes(int N, int h, int w, int Ho, int Wo);
+int dc_disp_render(const float* disp, const uint8_t* lut, uint8_t* rgb, float* range, int N, int h, int w, int Ho, int Wo, double q,
+                   void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

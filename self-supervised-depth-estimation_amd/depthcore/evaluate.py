@@ -11,9 +11,11 @@ library calls.
                           mode, the pair formed by the stem kernel's loader (ResnetEncoder.forward_pair);
   evaluate_pose        -- evaluate_pose.py:104-125: the absolute trajectory error of every snippet (ops.pose_ate).
 
+  render_disparities   -- test_simple.py:126-145: the colour image of every disparity map at its photo's size (ops.render_disparity).
+
 Everything that touches a pixel runs on depthcore's kernels; the host sees the (N, 7) errors and (N,) ratios, or the (N,) ATEs
-with their mean and std, only.  The drop-in scripts `evaluate_depth.py` / `evaluate_pose.py` next to `trainer.py` wrap them
-with the reference's options."""
+with their mean and std, or the RGB bytes and two floats per image, only.  The drop-in scripts `evaluate_depth.py` /
+`evaluate_pose.py` / `test_simple.py` next to `trainer.py` wrap them with the reference's options."""
 import collections
 
 import numpy as np
@@ -234,3 +236,53 @@ def evaluate_pose(pred_poses, gt_global_poses, track_length=5):
     gt = gt_global_poses.to(device=dev, dtype=torch.float64).reshape(M, 3, 4)
     ates, mean, std = ops.pose_ate(pred, gt, track_length)
     return {"ates": ates.numpy(), "mean": float(mean), "std": float(std), "track_length": int(track_length)}
+
+
+def render_disparities(disps, sizes, percentile=95.0, lut=None, chunk=64):
+    """test_simple.py:126-145 for N maps -> (images, ranges): images[i] a host uint8 array (Ho_i, Wo_i, 3) -- what
+    PIL.Image.fromarray takes -- and ranges (N,2) float32 = (vmin, vmax) of every image, in input order.
+
+    disps: (N,1,h,w) (or (N,h,w)) float32 disparities -- a device tensor, or host data that is copied over.
+    sizes: N target sizes (Ho, Wo), any mix (the photos of a folder differ in size), or one (Ho, Wo) for all.
+    Images are grouped by target size and rendered `chunk` at a time: one dc_disp_render launch chain and ONE device-to-host
+    copy (bytes and ranges together) per chunk.  The upsampled fp32 maps never exist, on either side."""
+    if not torch.is_tensor(disps):
+        disps = torch.from_numpy(np.ascontiguousarray(disps, np.float32))
+    if disps.dim() == 3:
+        disps = disps.unsqueeze(1)
+    if not disps.is_cuda:
+        disps = disps.to(torch.device("cuda", torch.cuda.current_device()))
+    if disps.dtype != torch.float32 or disps.dim() != 4 or disps.shape[1] != 1:
+        raise _lib.DepthcoreError("render_disparities: disps must be (N,1,h,w) float32, got %s %s" % (tuple(disps.shape), disps.dtype))
+    if chunk <= 0:
+        raise ValueError("chunk must be positive")
+    d = disps if disps.is_contiguous() else disps.contiguous()
+    N = d.shape[0]
+    if len(sizes) == 2 and all(isinstance(v, (int, np.integer)) for v in sizes):
+        sizes = [sizes] * N
+    if len(sizes) != N:
+        raise ValueError("render_disparities: %d maps for %d sizes" % (N, len(sizes)))
+    if lut is not None and not torch.is_tensor(lut):
+        lut = torch.from_numpy(np.ascontiguousarray(lut, np.uint8))
+    if lut is not None:
+        lut = lut.to(d.device)
+    groups = collections.OrderedDict()
+    for i in range(N):
+        groups.setdefault((int(sizes[i][0]), int(sizes[i][1])), []).append(i)
+    images = [None] * N
+    ranges = np.empty((N, 2), np.float32)
+    for (Ho, Wo), idx in groups.items():
+        for c0 in range(0, len(idx), chunk):
+            ids = idx[c0:c0 + chunk]
+            if ids[-1] - ids[0] == len(ids) - 1:
+                x = d[ids[0]:ids[-1] + 1]
+            else:
+                x = ops.stack_frames([[d[i:i + 1] for i in ids]])[0]
+            _, _, buf = ops._render_disparity(x, (Ho, Wo), percentile, lut)
+            host = buf.cpu().numpy()
+            G, nb = len(ids), Ho * Wo * 3
+            rgb = host[:G * nb].reshape(G, Ho, Wo, 3)
+            ranges[ids] = host[(G * nb + 3) & ~3:].view(np.float32).reshape(G, 2)
+            for k, i in enumerate(ids):
+                images[i] = rgb[k]
+    return images, ranges

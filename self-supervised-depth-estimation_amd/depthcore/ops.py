@@ -1181,6 +1181,75 @@ def depth_png16(disp, size=BENCHMARK_SIZE, scale=STEREO_SCALE_FACTOR):
 
 
 # ----------------------------------------------------------------------------------------------
+# single-image inference: the colour image of test_simple.py:126-145
+# ----------------------------------------------------------------------------------------------
+_MAGMA = {}
+
+
+def magma_lut(device=None):
+    """matplotlib's 256-entry magma quantised as test_simple.py:141 does, (lut[:256, :3] * 255).astype(uint8): a (256,3) uint8
+    tensor from the literal in depthcore/_magma.py (matplotlib is not a dependency).  device=None: on the host."""
+    if "host" not in _MAGMA:
+        from ._magma import MAGMA_LUT8_HEX
+        raw = bytes.fromhex(MAGMA_LUT8_HEX)
+        if len(raw) != 768:
+            raise DepthcoreError("depthcore/_magma.py: expected 768 bytes, got %d" % len(raw))
+        _MAGMA["host"] = torch.frombuffer(bytearray(raw), dtype=torch.uint8).view(256, 3)
+    if device is None:
+        return _MAGMA["host"]
+    device = torch.device(device)
+    if device not in _MAGMA:
+        _MAGMA[device] = _MAGMA["host"].to(device)
+    return _MAGMA[device]
+
+
+def _render_disparity(disp, size, percentile, lut, buf=None):
+    """dc_disp_render into `buf`, a uint8 device tensor laid out [rgb (N*Ho*Wo*3) | pad to 4 | range (N*2 fp32)] (allocated when
+    None) -> (rgb, range, buf): views of it, so that a caller brings both to the host with one copy."""
+    L = _lib.lib()
+    d = _c(disp.detach())
+    if d.dim() != 4 or d.shape[1] != 1:
+        raise DepthcoreError("render_disparity: (N,1,h,w), got %s" % (tuple(d.shape),))
+    N, _, h, w = d.shape
+    Ho, Wo = int(size[0]), int(size[1])
+    q = float(percentile)
+    if N < 1 or h < 1 or w < 1 or Ho < 1 or Wo < 1:
+        raise DepthcoreError("render_disparity: empty input %s or target size %s" % (tuple(d.shape), (Ho, Wo)))
+    if not 0.0 <= q <= 100.0:
+        raise DepthcoreError("render_disparity: percentile must be in [0, 100], got %r" % (percentile,))
+    if lut is None:
+        lut = magma_lut(d.device)
+    if tuple(lut.shape) != (256, 3) or lut.dtype != torch.uint8 or lut.device != d.device:
+        raise DepthcoreError("render_disparity: lut must be a (256,3) uint8 tensor on %s, got %s %s on %s"
+                             % (d.device, tuple(lut.shape), lut.dtype, lut.device))
+    nrgb = N * Ho * Wo * 3
+    roff = (nrgb + 3) & ~3
+    if buf is None:
+        buf = torch.empty(roff + N * 8, dtype=torch.uint8, device=d.device)
+    rgb = buf[:nrgb].view(N, Ho, Wo, 3)
+    rng = buf[roff:roff + N * 8].view(torch.float32).view(N, 2)
+    nws = L.dc_disp_render_ws_bytes(N, h, w, Ho, Wo)
+    if nws == 0:
+        raise DepthcoreError("render_disparity: unsupported shape %s -> %s" % (tuple(d.shape), (Ho, Wo)))
+    ws = torch.empty(nws, dtype=torch.uint8, device=d.device)
+    check(L.dc_disp_render(ptr(d), ptr(_c(lut), torch.uint8), ptr(rgb, torch.uint8), ptr(rng), N, h, w, Ho, Wo, q, ws.data_ptr(),
+                           nws, stream(d)), "dc_disp_render")
+    return rgb, rng, buf
+
+
+def render_disparity(disp, size, percentile=95.0, lut=None):
+    """The colour image of test_simple.py:126-145 (dc_disp_render): disp (N,1,h,w) -> (rgb (N,Ho,Wo,3) uint8 -- interleaved, what
+    PIL.Image.fromarray takes -- and range (N,2) float32 = (vmin, vmax) of every image), device tensors on the current stream.
+    Each image is upsampled to size = (Ho, Wo) by F.interpolate(bilinear, align_corners=False)'s expression (bit for bit
+    ops.upsample_bilinear's, never stored), normalised between its own minimum and its own `percentile` (numpy's linear
+    interpolation between two exact order statistics, found by radix selection) as matplotlib's Normalize does, and looked up
+    in `lut`, a (256,3) uint8 device tensor (default: magma).  Values above the percentile take the last colour; a constant
+    image takes the first.  Non-finite input is outside the contract.  Bitwise reproducible.  No gradient."""
+    rgb, rng, _ = _render_disparity(disp, size, percentile, lut)
+    return rgb, rng
+
+
+# ----------------------------------------------------------------------------------------------
 # a1 nn.MaxPool2d(3, 2, 1) of the ResNet stem
 # ----------------------------------------------------------------------------------------------
 class _MaxPool(torch.autograd.Function):
