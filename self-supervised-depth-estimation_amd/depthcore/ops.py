@@ -621,18 +621,25 @@ def upsample_bilinear(x, Ho, Wo):
 # ----------------------------------------------------------------------------------------------
 # a3  upsample(x): nearest x2                                          (reference layers.py:196-199)
 # ----------------------------------------------------------------------------------------------
+def _aligned8(t):
+    """The nearest x2 kernels move the doubled rows as float2 (the input of the forward is read float by float): an upstream
+    gradient that is a contiguous view at an odd float offset of its storage (a slice of a flat buffer, say) is copied to a
+    buffer of its own."""
+    return t.clone() if t.data_ptr() & 7 else t
+
+
 class _UpsampleNearest2x(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         xx = _c(x.detach())
         B, C, h, w = xx.shape
-        out = torch.empty(B, C, 2 * h, 2 * w, dtype=torch.float32, device=xx.device)
+        out = torch.empty(B, C, 2 * h, 2 * w, dtype=torch.float32, device=xx.device)   # the allocator's own alignment
         check(_lib.lib().dc_upsample_nearest2x_fwd(ptr(xx), ptr(out), B * C, h, w, stream(xx)), "dc_upsample_nearest2x_fwd")
         return out
 
     @staticmethod
     def backward(ctx, go):
-        g = _c(go)
+        g = _aligned8(_c(go))
         B, C, H2, W2 = g.shape
         dx = torch.empty(B, C, H2 // 2, W2 // 2, dtype=torch.float32, device=g.device)
         check(_lib.lib().dc_upsample_nearest2x_bwd(ptr(g), ptr(dx), B * C, H2 // 2, W2 // 2, stream(g)), "dc_upsample_nearest2x_bwd")
