@@ -441,8 +441,8 @@ int dc_conv1x1_wgrad_bn(const float* x, const float* gy, float* dweight, void* w
  * (pixels per image a multiple of 16, reduction extent a multiple of 32, >= 64 output rows; the data gradient at stride 1);
  * ws = dc_gemm1x1x3_workspace(Ci, Co) bytes, 16-byte aligned (the split weights of the launch; weights registered with the
  * per-step weight cache, dc_wino_cache_*, are split once per step by its refresh instead).  dc_set_gemm_split (default 1; env
- * DC_G1_X3): whether callers that can supply the workspace (depthcore/ops.py, depthcore/bnfold.py) take this path where it
- * applies; 0 keeps the fp32-MFMA kernels (the A/B); 3 = 1 + the forward and weight gradient of the 3x3 / 2 trunk convolutions
+ * DC_G1_X3): whether dc_pointwise_* (below) takes this path where it applies; 0 keeps the fp32-MFMA kernels (the A/B); 3 = 1 +
+ * the forward and weight gradient of the 3x3 / 2 trunk convolutions
  * (dc_convs2_*) on the same kernels with gather loaders -- an experiment: more accurate, slower on most shapes, not the default.
  * Accumulation: each 32-deep chunk's six products are summed from zero inside the matrix pipe and enter the fp32 accumulator through
  * ONE round-to-nearest add, with alternating operand signs per chunk -- v_mfma_f32_16x16x32_bf16 truncates its fp32 result toward
@@ -456,24 +456,39 @@ int dc_gemm1x1x3_fwd(const float* x, const float* weight, const float* bias, flo
                      int stride, int act, void* stream);
 int dc_gemm1x1x3_dgrad(const float* gy, const float* weight, float* dx, void* ws, const float* addend, const float* addend2, int B,
                        int Ci, int Co, int Hi, int Wi, int stride, void* stream);
-/* ... with a BatchNorm folded in (dc_bn_fold; `bn` nullable): the contract of dc_conv1x1_*_bn on the split kernels -- loader
- * relu(scale x + shift) in the forward and the weight gradient, statistics epilogue of the forward, BatchNorm-backward epilogue of
- * the data gradient; the *_parts queries size the partial buffers for THESE kernels' tiles. */
-int dc_gemm1x1x3_bn_ok(int B, int Ci, int Co, int Hi, int Wi);
+/* partials per channel of the statistics / BatchNorm-backward epilogues on THESE kernels' tiles (0 = not on this shape / group
+ * layout): what dc_pointwise_stat_parts / dc_pointwise_bwd_parts return when this family takes the pass */
 int dc_gemm1x1x3_stat_parts(int B, int Ci, int Co, int Hi, int Wi, int stride, int groups, int* ppg);
 int dc_gemm1x1x3_bwd_parts(int B, int Ci, int Co, int Hi, int Wi, int groups, int* ppg);
-int dc_gemm1x1x3_fwd_bn(const float* x, const float* weight, const float* bias, float* y, void* ws, int B, int Ci, int Co, int Hi, int Wi,
-                        int stride, int act, const dc_bn_fold* bn, void* stream);
-int dc_gemm1x1x3_dgrad_bn(const float* gy, const float* weight, float* dx, void* ws, const float* addend, const float* addend2, int B,
-                          int Ci, int Co, int Hi, int Wi, int stride, const dc_bn_fold* bn, void* stream);
-int dc_gemm1x1x3_wgrad_bn(const float* x, const float* gy, float* dweight, void* ws, int B, int Ci, int Co, int Hi, int Wi, int stride,
-                          const dc_bn_fold* bn, void* stream);
 /* weight gradient: both operands split while staging, reduction split over blocks into fp32 slabs (ws = dc_gemm1x1x3_wgrad_workspace
  * bytes, 16-byte aligned), summed in fixed order: deterministic */
 int dc_gemm1x1x3_wgrad_ok(int B, int Ci, int Co, int Hi, int Wi, int stride);
 size_t dc_gemm1x1x3_wgrad_workspace(int B, int Ci, int Co, int Hi, int Wi, int stride);
 int dc_gemm1x1x3_wgrad(const float* x, const float* gy, float* dweight, void* ws, int B, int Ci, int Co, int Hi, int Wi, int stride,
                        void* stream);
+
+/* THE 1x1 convolution as the Python side calls it: every pass goes to one of the three kernel families -- split bf16
+ * (dc_gemm1x1x3_*) where dc_get_gemm_split() != 0 and the family takes the pass, else fp32-MFMA tiled, else the general kernels
+ * (dc_conv1x1_*: those two) -- chosen by ONE function, which the queries and the launches below all call: a workspace or
+ * partial count taken here always fits the launch that follows with the same arguments.  The split mode is read PER CALL: do not
+ * change it between a query and its launch, or between a forward and its backward.  dc_conv1x1_* / dc_gemm1x1x3_* stay
+ * pinned to their families for A/B comparisons.
+ *   pass: DC_PASS_*.  bn (nullable): the fold, as in dc_conv1x1_*_bn; a fold that is asked for (in_scale / stat_part in the
+ *   forward, bwd_part in the data gradient at stride 1, in_scale in the weight gradient) needs a tiled family: DC_EINVAL otherwise.
+ *   ws: dc_pointwise_workspace(pass, bn, ...) bytes (never below 16), 16-byte aligned: the split weights or the weight-gradient
+ *   slabs of the family that takes the pass.  *_parts: partials per channel of the forward's statistics epilogue / the data
+ *   gradient's BatchNorm epilogue for `groups` (0 = no family has the epilogue on this shape); ppg (nullable): per group.
+ *   fwd: y = act(conv1x1(x) + bias) (bias nullable).  dgrad: dx = data gradient + addend + addend2 (both nullable). */
+enum { DC_PASS_FWD = 0, DC_PASS_DGRAD = 1, DC_PASS_WGRAD = 2 };
+size_t dc_pointwise_workspace(int pass, const dc_bn_fold* bn, int B, int Ci, int Co, int Hi, int Wi, int stride);
+int dc_pointwise_stat_parts(int B, int Ci, int Co, int Hi, int Wi, int stride, int groups, int* ppg);
+int dc_pointwise_bwd_parts(int B, int Ci, int Co, int Hi, int Wi, int stride, int groups, int* ppg);
+int dc_pointwise_fwd(const float* x, const float* weight, const float* bias, float* y, void* ws, int B, int Ci, int Co, int Hi, int Wi,
+                     int stride, int act, const dc_bn_fold* bn, void* stream);
+int dc_pointwise_dgrad(const float* gy, const float* weight, float* dx, void* ws, const float* addend, const float* addend2, int B,
+                       int Ci, int Co, int Hi, int Wi, int stride, const dc_bn_fold* bn, void* stream);
+int dc_pointwise_wgrad(const float* x, const float* gy, float* dweight, void* ws, int B, int Ci, int Co, int Hi, int Wi, int stride,
+                       const dc_bn_fold* bn, void* stream);
 
 /* The same convolution with bias and activation fused into the epilogue: y = act(conv1x1(x) + bias), act as in
  * dc_conv3x3_fwd (0 none, 1 ELU, 2 sigmoid, 3 ReLU, 4 tanh); bias may be NULL.  This is `relu(squeeze(f))` and the final

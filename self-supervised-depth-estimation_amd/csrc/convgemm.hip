@@ -993,10 +993,6 @@ static int cg_wsplits(int tiles, int chunks) {
     const int s = std::max(1, std::min({chunks, ceil_div(768, tiles), 512}));
     return ceil_div(chunks, ceil_div(chunks, s));
 }
-template <typename K>
-static bool cg_set_lds(K kernel, size_t bytes) {
-    return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
-}
 
 // the patch-staged stem kernels: 7x7 / 2, 64 output channels, 3 or 6 input channels (DC_STEM_PATCH=0: gather kernels, A/B)
 static bool stem_enabled() {
@@ -1033,7 +1029,7 @@ static int stem_fwd_x3_launch(StemArgs& sa, void* ws, hipStream_t st) {
     hipLaunchKernelGGL(stem_x3_prep_kernel, dim3(ceil_div(64 * (sa.Kp / 4), 256)), dim3(256), 0, st, (const float*)ws, wa, sa.Kp);
     DC_CHECK_LAUNCH();
     const size_t lds = stem_lds_fwd_x3(sa.Ci, sa.Kp);
-    static const bool attr = cg_set_lds(stem_fwd_x3_kernel<FR>, stem_lds_fwd_x3(6, 320));
+    static const bool attr = set_max_dynamic_lds(stem_fwd_x3_kernel<FR>, stem_lds_fwd_x3(6, 320));
     if (!attr) return DC_ELAUNCH;
     hipLaunchKernelGGL(stem_fwd_x3_kernel<FR>, dim3(sa.ntiles, 1), dim3(256), lds, st, sa, (const unsigned short*)wa);
     return DC_OK;
@@ -1128,7 +1124,7 @@ extern "C" int dc_convs2_fwd(const float* x, const float* weight, float* y, void
         if (sp > 1) a.out = (float*)ws;            // (Kp == K for the 3x3: the workspace holds nothing else on this path)
         a.mtiles = ceil_div(Co, 64); a.ntiles = ceil_div(N, 32 * t.nt);
         const size_t lds3 = ((size_t)64 * (96 + RP) + (size_t)96 * (t.nt == 4 ? 128 : 80)) * sizeof(float);
-        static const bool attr3 = cg_set_lds(cg_fwd3_kernel<2, 4>, ((size_t)64 * (96 + RP) + (size_t)96 * 128) * sizeof(float));
+        static const bool attr3 = set_max_dynamic_lds(cg_fwd3_kernel<2, 4>, ((size_t)64 * (96 + RP) + (size_t)96 * 128) * sizeof(float));
         if (!attr3) return DC_ELAUNCH;
         const dim3 grid(a.mtiles * a.ntiles, sp);
         // 2 MAC of the convolution; executed = the padded 64 x (32 nt) tiles over the whole reduction
@@ -1149,7 +1145,7 @@ extern "C" int dc_convs2_fwd(const float* x, const float* weight, float* y, void
     a.mtiles = ceil_div(Co, 32 * t.mt); a.ntiles = ceil_div(N, 32 * t.nt);
     const dim3 grid(a.mtiles * a.ntiles);
     const size_t lds = cg_lds_fwd(t);
-    static const bool attr = cg_set_lds(cg_fwd_kernel<4, 4, 3>, cg_lds_fwd({4, 4})) && cg_set_lds(cg_fwd_kernel<4, 4, 7>, cg_lds_fwd({4, 4}));
+    static const bool attr = set_max_dynamic_lds(cg_fwd_kernel<4, 4, 3>, cg_lds_fwd({4, 4})) && set_max_dynamic_lds(cg_fwd_kernel<4, 4, 7>, cg_lds_fwd({4, 4}));
     if (!attr) return DC_ELAUNCH;
 #define CG_FWD(KS)                                                                                  \
     do {                                                                                            \

@@ -105,6 +105,12 @@ __device__ __forceinline__ Bilin bilin_setup(float x, float y, int H, int W) {
 }
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// raise a kernel's dynamic-LDS limit to `bytes` (above the 64 KB default); the launchers call it once, from a static initialiser
+template <typename K>
+static bool set_max_dynamic_lds(K kernel, size_t bytes) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+}
 __device__ __forceinline__ int ceil_div_dev(int a, int b) { return (a + b - 1) / b; }
 
 // ---- XCD-aware block order ---------------------------------------------------------------------------

@@ -647,11 +647,6 @@ static int g1_wsplits(int M, int K, int chunks, G1Tile t) {
     return ceil_div(chunks, ceil_div(chunks, s));        // no empty split: every slab gets written
 }
 
-template <typename K>
-static bool g1_set_lds(K kernel, size_t bytes) {
-    return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
-}
-
 }  // namespace dc
 
 using namespace dc;
@@ -683,23 +678,15 @@ static void g1_fill(G1Args& a, int B, int Ci, int Co, int Hi, int Wi, int stride
 }
 
 // partials per channel of the forward's statistics epilogue / the data gradient's BatchNorm epilogue (0: not on this shape):
-// one per wave column of 16 NT pixels; a group boundary must not fall inside one
-static int g1_parts(int rows, int B, int P, int groups, size_t (*lds)(G1Tile), int* ppg) {
-    if (groups < 1 || B % groups) return 0;
-    const int N = B * P;
-    const G1Tile t = g1_pick(rows, N, lds);
-    const int cover = 16 * t.nt;
-    if (groups > 1 && (N / groups) % cover) return 0;
-    if (ppg) *ppg = (N / groups) / cover;
-    return ceil_div(N, 32 * t.nt) * 2;
-}
+// gemm_parts (gemm_tiles.h) with this family's tile choice
 extern "C" int dc_gemm1x1_stat_parts(int B, int Ci, int Co, int Hi, int Wi, int stride, int groups, int* ppg) {
     if (!dc_gemm1x1_fwd_ok(B, Ci, Co, Hi, Wi, stride)) return 0;
-    return g1_parts(Co, B, (Hi / stride) * (Wi / stride), groups, g1_lds_fwd, ppg);
+    const int P = (Hi / stride) * (Wi / stride);
+    return gemm_parts(g1_pick(Co, B * P, g1_lds_fwd).nt, B, P, groups, ppg);
 }
 extern "C" int dc_gemm1x1_bwd_parts(int B, int Ci, int Co, int Hi, int Wi, int stride, int groups, int* ppg) {
     if (stride != 1 || !dc_gemm1x1_dgrad_ok(B, Ci, Co, Hi, Wi, stride)) return 0;
-    return g1_parts(Ci, B, Hi * Wi, groups, g1_lds_dgrad, ppg);
+    return gemm_parts(g1_pick(Ci, B * Hi * Wi, g1_lds_dgrad).nt, B, Hi * Wi, groups, ppg);
 }
 
 extern "C" int dc_gemm1x1_fwd(const float* x, const float* weight, const float* bias, float* y, int B, int Ci, int Co, int Hi, int Wi,
@@ -727,11 +714,11 @@ extern "C" int dc_gemm1x1_fwd(const float* x, const float* weight, const float* 
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = g1_lds_fwd(t);
     const bool epi = bias || act != ACT_NONE;
-    static const bool attr = g1_set_lds(g1_fwd_kernel<4, 4, false, 1>, g1_lds_fwd({4, 4})) &&
-                             g1_set_lds(g1_fwd_kernel<4, 4, true, 1>, g1_lds_fwd({4, 4})) &&
-                             g1_set_lds(g1_fwd_kernel<4, 4, false, 2>, g1_lds_fwd({4, 4})) &&
-                             g1_set_lds(g1_fwd_kernel<4, 4, true, 2>, g1_lds_fwd({4, 4})) &&
-                             g1_set_lds(g1_fwd_kernel<4, 4, false, 1, true>, g1_lds_fwd({4, 4}));
+    static const bool attr = set_max_dynamic_lds(g1_fwd_kernel<4, 4, false, 1>, g1_lds_fwd({4, 4})) &&
+                             set_max_dynamic_lds(g1_fwd_kernel<4, 4, true, 1>, g1_lds_fwd({4, 4})) &&
+                             set_max_dynamic_lds(g1_fwd_kernel<4, 4, false, 2>, g1_lds_fwd({4, 4})) &&
+                             set_max_dynamic_lds(g1_fwd_kernel<4, 4, true, 2>, g1_lds_fwd({4, 4})) &&
+                             set_max_dynamic_lds(g1_fwd_kernel<4, 4, false, 1, true>, g1_lds_fwd({4, 4}));
     if (!attr) return DC_ELAUNCH;
     hipEvent_t pe = conv_prof_begin(4, 2.0 * (double)B * Co * Ci * a.Ho * a.Wo, 2.0 * (double)grid.x * (32.0 * t.mt) * (32.0 * t.nt) * Ci, 4.0 * ((double)B * Ci * a.Ho * a.Wo + (double)B * Co * a.Ho * a.Wo + (double)Co * Ci), st);
 #define G1_FWD(MT, NT)                                                                            \
@@ -778,9 +765,9 @@ extern "C" int dc_gemm1x1_dgrad(const float* gy, const float* weight, float* dx,
     const dim3 grid(a.mtiles * a.ntiles);
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = g1_lds_dgrad(t);
-    static const bool attr = g1_set_lds(g1_dgrad_kernel<4, 4>, g1_lds_dgrad({4, 4})) && g1_set_lds(g1_dgrad_kernel<4, 4, 1>, g1_lds_dgrad({4, 4})) &&
-                             g1_set_lds(g1_dgrad_kernel<4, 4, 2>, g1_lds_dgrad({4, 4})) && g1_set_lds(g1_dgrad_kernel<4, 4, 0, 2>, g1_lds_dgrad({4, 4})) &&
-                             g1_set_lds(g1_dgrad_kernel<4, 4, 0, 3>, g1_lds_dgrad({4, 4}));
+    static const bool attr = set_max_dynamic_lds(g1_dgrad_kernel<4, 4>, g1_lds_dgrad({4, 4})) && set_max_dynamic_lds(g1_dgrad_kernel<4, 4, 1>, g1_lds_dgrad({4, 4})) &&
+                             set_max_dynamic_lds(g1_dgrad_kernel<4, 4, 2>, g1_lds_dgrad({4, 4})) && set_max_dynamic_lds(g1_dgrad_kernel<4, 4, 0, 2>, g1_lds_dgrad({4, 4})) &&
+                             set_max_dynamic_lds(g1_dgrad_kernel<4, 4, 0, 3>, g1_lds_dgrad({4, 4}));
     if (!attr) return DC_ELAUNCH;
     hipEvent_t pe = conv_prof_begin(4, 2.0 * (double)B * Co * Ci * a.Ho * a.Wo, 2.0 * (double)grid.x * (32.0 * t.mt) * (32.0 * t.nt) * Co, 4.0 * ((double)B * Ci * a.Ho * a.Wo + (double)B * Co * a.Ho * a.Wo + (double)Co * Ci), st);
 #define G1_DGRAD(BNE, SD)                                                                                  \
@@ -829,8 +816,8 @@ extern "C" int dc_gemm1x1_wgrad(const float* x, const float* gy, float* dweight,
     const dim3 grid(a.mtiles * a.ntiles, a.splits);
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = g1_lds_wgrad(t);
-    static const bool attr = g1_set_lds(g1_wgrad_kernel<4, 4, 1>, g1_lds_wgrad({4, 4})) && g1_set_lds(g1_wgrad_kernel<4, 4, 2>, g1_lds_wgrad({4, 4})) &&
-                             g1_set_lds(g1_wgrad_kernel<4, 4, 1, true>, g1_lds_wgrad({4, 4}));
+    static const bool attr = set_max_dynamic_lds(g1_wgrad_kernel<4, 4, 1>, g1_lds_wgrad({4, 4})) && set_max_dynamic_lds(g1_wgrad_kernel<4, 4, 2>, g1_lds_wgrad({4, 4})) &&
+                             set_max_dynamic_lds(g1_wgrad_kernel<4, 4, 1, true>, g1_lds_wgrad({4, 4}));
     if (!attr) return DC_ELAUNCH;
     hipEvent_t pe = conv_prof_begin(4, 2.0 * (double)B * Co * Ci * a.Ho * a.Wo, 2.0 * (double)grid.x * (32.0 * t.mt) * (32.0 * t.nt) * (double)a.chunks * GKC, 4.0 * ((double)B * Ci * a.Ho * a.Wo + (double)B * Co * a.Ho * a.Wo + (double)Co * Ci), st);
     if (bnin) {

@@ -44,6 +44,15 @@ __device__ __forceinline__ void g1x3_prep_item(const float* __restrict__ w, unsi
 }
 #endif
 
+// the 1 x 1 passes with a BatchNorm folded in (bn nullable; dc_bn_fold in depthcore.h): the contract of dc_conv1x1_*_bn on the split
+// kernels, partials laid out for THESE kernels' tiles (dc_gemm1x1x3_stat_parts / _bwd_parts).  Behind dc_pointwise_* (pointwise.hip)
+int g1x3_fwd(const float* x, const float* weight, const float* bias, float* y, void* ws, int B, int Ci, int Co, int Hi, int Wi, int stride,
+             int act, const dc_bn_fold* bn, void* stream);
+int g1x3_dgrad(const float* gy, const float* weight, float* dx, void* ws, const float* addend, const float* addend2, int B, int Ci, int Co,
+               int Hi, int Wi, int stride, const dc_bn_fold* bn, void* stream);
+int g1x3_wgrad(const float* x, const float* gy, float* dweight, void* ws, int B, int Ci, int Co, int Hi, int Wi, int stride,
+               const dc_bn_fold* bn, void* stream);
+
 // the 3 x 3 / 2 trunk convolutions on the split-operand kernels (forward, weight gradient): eligibility, workspace bytes, launches
 bool g1x3_conv3s2_ok(int B, int Ci, int Co, int Hi, int Wi);
 bool g1x3_conv3s2_wgrad_ok(int B, int Ci, int Co, int Hi, int Wi);

@@ -32,6 +32,7 @@
 #include "dc_common.h"
 #include "gemm1x1.h"
 #include "gemm1x1_x3.h"
+#include "gemm_tiles.h"
 #include "wino.h"
 
 #include <algorithm>
@@ -642,34 +643,10 @@ __global__ __launch_bounds__(256, (X3T<MT, NT>::PER_CU)) void g1x3_wgrad_kernel(
             }
 }
 
-// fixed-order slab sum (the float4 form of gemm_tiles.h's slab_reduce16_kernel)
-__global__ __launch_bounds__(256) void g1x3_slabsum_kernel(const x3f4* __restrict__ slab, x3f4* __restrict__ out, int splits, int n4) {
-    __shared__ x3f4 sm[256];
-    const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
-    const int i = blockIdx.x * 16 + l;
-    const int per = (splits + 15) / 16, s0 = g * per, s1 = min(s0 + per, splits);
-    x3f4 t = {0.f, 0.f, 0.f, 0.f};
-    if (i < n4)
-        for (int s = s0; s < s1; ++s) t += slab[(size_t)s * n4 + i];
-    sm[threadIdx.x] = t;
-    __syncthreads();
-    if (g == 0 && i < n4) {
-        x3f4 r = sm[l];
-#pragma unroll
-        for (int k = 1; k < 16; ++k) r += sm[k * 16 + l];
-        out[i] = r;
-    }
-}
-
 // default ON (env DC_G1_X3=0 / dc_set_gemm_split(0): the fp32-MFMA kernels of gemm1x1.hip, the A/B): the gate of VERDICT round 5 item 1
 // -- error vs fp64 no worse than the fp32-MFMA kernels', every fp64-calibrated test green with unchanged thresholds -- is met
 // (tests/test_conv1x1_gpu.py, tests/test_encoder_gpu.py, tests/test_train_gpu.py under this default)
 static int g_g1x3 = [] { const char* f = getenv("DC_G1_X3"); return f ? atoi(f) : 1; }();
-
-template <typename K>
-static bool x3_set_lds(K kernel, size_t bytes) {
-    return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
-}
 
 // ---- tile choice: the largest tile whose grid still fills the chip's resident slots (a 128 x 128 tile amortises the operand split and
 // the LDS traffic best, but 80 blocks of it on 256 CUs lose to 320 blocks of 64 x 64: the layer4 shapes of BASELINE configs[2])
@@ -698,6 +675,16 @@ static X3Tile x3_pick(int M, int N, int stride) {
         if (score > best) { best = score; pick = cand[i]; }
     }
     return pick;
+}
+
+// f(tag) with the tile as compile-time constants tag.mt, tag.nt: the one place the four instantiated tiles are listed
+template <int MT, int NT> struct X3Tag { static constexpr int mt = MT, nt = NT; };
+template <class F>
+static int x3_with_tile(X3Tile t, F&& f) {
+    if (t.mt == 4 && t.nt == 4) return f(X3Tag<4, 4>{});
+    if (t.mt == 2 && t.nt == 4) return f(X3Tag<2, 4>{});
+    if (t.mt == 4) return f(X3Tag<4, 2>{});
+    return f(X3Tag<2, 2>{});
 }
 
 }  // namespace dc
@@ -733,16 +720,10 @@ extern "C" size_t dc_gemm1x1x3_workspace(int Ci, int Co) {
     return std::max(a, b) * 3 * 2 + 256;
 }
 
-// partials per channel of the forward's statistics epilogue / the data gradient's BatchNorm epilogue (0: not on this shape): one per
-// wave column of 16 NT pixels; a group boundary must not fall inside one (csrc/gemm1x1.hip g1_parts, with THIS file's tile choice)
+// partials per channel of the forward's statistics epilogue / the data gradient's BatchNorm epilogue (0: not on this shape):
+// gemm_parts (gemm_tiles.h) with THIS file's tile choice
 static int g1x3_parts(int rows, int B, int P, int stride, int groups, int* ppg) {
-    if (groups < 1 || B % groups) return 0;
-    const int N = B * P;
-    const X3Tile t = x3_pick(rows, N, stride);
-    const int cover = 16 * t.nt;
-    if (groups > 1 && (N / groups) % cover) return 0;
-    if (ppg) *ppg = (N / groups) / cover;
-    return ceil_div(N, 32 * t.nt) * 2;
+    return gemm_parts(x3_pick(rows, B * P, stride).nt, B, P, groups, ppg);
 }
 extern "C" int dc_gemm1x1x3_stat_parts(int B, int Ci, int Co, int Hi, int Wi, int stride, int groups, int* ppg) {
     if (!dc_gemm1x1x3_fwd_ok(B, Ci, Co, Hi, Wi, stride)) return 0;
@@ -753,21 +734,22 @@ extern "C" int dc_gemm1x1x3_bwd_parts(int B, int Ci, int Co, int Hi, int Wi, int
     return g1x3_parts(Ci, B, Hi * Wi, 1, groups, ppg);
 }
 
+// S: the loader -- 1 / 2 = the 1 x 1 convolution's stride, 3 = the 3 x 3 / 2 gather
 template <int MT, int NT>
-static int g1x3_go(const G1x3Args& a, dim3 grid, int stride, bool epi, int mode, hipStream_t st) {
+static int g1x3_go(const G1x3Args& a, dim3 grid, int S, bool epi, int mode, hipStream_t st) {
     using T = X3T<MT, NT>;
-    static const bool attr = x3_set_lds(g1x3_kernel<MT, NT, 1, false>, T::LDS) && x3_set_lds(g1x3_kernel<MT, NT, 1, true>, T::LDS) &&
-                             x3_set_lds(g1x3_kernel<MT, NT, 2, false>, T::LDS) && x3_set_lds(g1x3_kernel<MT, NT, 2, true>, T::LDS) &&
-                             x3_set_lds(g1x3_kernel<MT, NT, 1, false, 1>, T::LDS) && x3_set_lds(g1x3_kernel<MT, NT, 1, false, 2>, T::LDS) &&
-                             x3_set_lds(g1x3_kernel<MT, NT, 1, false, 3>, T::LDS) && x3_set_lds(g1x3_kernel<MT, NT, 1, false, 4>, T::LDS) &&
-                             x3_set_lds(g1x3_kernel<MT, NT, 3, false>, T::LDS);
+    static const bool attr = set_max_dynamic_lds(g1x3_kernel<MT, NT, 1, false>, T::LDS) && set_max_dynamic_lds(g1x3_kernel<MT, NT, 1, true>, T::LDS) &&
+                             set_max_dynamic_lds(g1x3_kernel<MT, NT, 2, false>, T::LDS) && set_max_dynamic_lds(g1x3_kernel<MT, NT, 2, true>, T::LDS) &&
+                             set_max_dynamic_lds(g1x3_kernel<MT, NT, 1, false, 1>, T::LDS) && set_max_dynamic_lds(g1x3_kernel<MT, NT, 1, false, 2>, T::LDS) &&
+                             set_max_dynamic_lds(g1x3_kernel<MT, NT, 1, false, 3>, T::LDS) && set_max_dynamic_lds(g1x3_kernel<MT, NT, 1, false, 4>, T::LDS) &&
+                             set_max_dynamic_lds(g1x3_kernel<MT, NT, 3, false>, T::LDS);
     if (!attr) return DC_ELAUNCH;
-    if (stride == 3) hipLaunchKernelGGL((g1x3_kernel<MT, NT, 3, false>), grid, dim3(256), T::LDS, st, a);
+    if (S == 3) hipLaunchKernelGGL((g1x3_kernel<MT, NT, 3, false>), grid, dim3(256), T::LDS, st, a);
     else if (mode == 4) hipLaunchKernelGGL((g1x3_kernel<MT, NT, 1, false, 4>), grid, dim3(256), T::LDS, st, a);
     else if (mode == 1) hipLaunchKernelGGL((g1x3_kernel<MT, NT, 1, false, 1>), grid, dim3(256), T::LDS, st, a);
     else if (mode == 2) hipLaunchKernelGGL((g1x3_kernel<MT, NT, 1, false, 2>), grid, dim3(256), T::LDS, st, a);
     else if (mode == 3) hipLaunchKernelGGL((g1x3_kernel<MT, NT, 1, false, 3>), grid, dim3(256), T::LDS, st, a);
-    else if (stride == 1) {
+    else if (S == 1) {
         if (epi) hipLaunchKernelGGL((g1x3_kernel<MT, NT, 1, true>), grid, dim3(256), T::LDS, st, a);
         else hipLaunchKernelGGL((g1x3_kernel<MT, NT, 1, false>), grid, dim3(256), T::LDS, st, a);
     } else {
@@ -777,14 +759,17 @@ static int g1x3_go(const G1x3Args& a, dim3 grid, int stride, bool epi, int mode,
     return DC_OK;
 }
 
-// dgrad: M = Ci rows, K = Co, src = gy; forward: M = Co, K = Ci, src = x.  bn (nullable): the fold, validated by the entry points
+// Fill the arguments, prepare or look up the split weights, profile, launch.  dgrad: M = Ci rows, K = Co, src = gy; forward: M = Co,
+// K = Ci, src = x; S = 3 (the 3 x 3 / 2 forward): K = 9 Ci.  S = -2: the data gradient of a stride-2 convolution, (Hi, Wi) is the
+// OUTPUT map.  bn (nullable): the fold, validated by the entry points
 static int g1x3_launch(const float* src, const float* weight, float* out, void* ws, const float* bias, int act, const float* addend,
-                       const float* addend2, int B, int M, int K, int Co, int Ci, int tr, int Hi, int Wi, int stride, const dc_bn_fold* bn,
+                       const float* addend2, int B, int M, int K, int Co, int Ci, int tr, int Hi, int Wi, int S, const dc_bn_fold* bn,
                        hipStream_t st) {
     if (((size_t)ws & 15) || ((size_t)src & 15) || ((size_t)out & 15)) return DC_EINVAL;
     G1x3Args a{};
-    const bool scatter = stride == -2;            // data gradient of a stride-2 convolution: (Hi, Wi) is the OUTPUT map here
-    if (scatter) stride = 1;
+    const bool scatter = S == -2;
+    if (scatter) S = 1;
+    const int stride = S == 3 ? 2 : S;
     a.Mp = ceil_div(M, 128) * 128;
     a.wa = (unsigned short*)ws; a.x = src; a.out = out; a.bias = bias; a.addend = addend; a.addend2 = addend2; a.act = act;
     a.B = B; a.M = M; a.K = K; a.Hi = Hi; a.Wi = Wi; a.Ho = Hi / stride; a.Wo = Wi / stride;
@@ -826,31 +811,28 @@ static int g1x3_launch(const float* src, const float* weight, float* out, void* 
     const dim3 grid(a.mtiles * a.ntiles);
     if (scatter) { a.Hi = 2 * Hi; a.Wi = 2 * Wi; }          // (the loads use Ho x Wo = the gy map; the scatter epilogue the input map)
     const bool epi = mode == 0 && (bias || act != ACT_NONE || addend || addend2);
-    // family 7: algorithmic = 2 MAC of the GEMM; executed = the six bf16 products of every padded tile (bf16 matrix FLOPs)
+    // family 7: algorithmic = 2 MAC of the GEMM; executed = the six bf16 products of every padded tile (bf16 matrix FLOPs);
+    // bytes: the operand as the loader reads it (S = 3: the input map once, not its nine taps)
+    const double src_elems = S == 3 ? (double)B * Ci * Hi * Wi : (double)N * K;
     hipEvent_t pe = conv_prof_begin(7, 2.0 * (double)N * M * K, 12.0 * (double)grid.x * (32.0 * t.mt) * (32.0 * t.nt) * K,
-                                    4.0 * ((double)N * K + (double)N * M + (double)M * K), st);
-    int rc;
-    if (t.mt == 4 && t.nt == 4) rc = g1x3_go<4, 4>(a, grid, stride, epi, mode, st);
-    else if (t.mt == 2 && t.nt == 4) rc = g1x3_go<2, 4>(a, grid, stride, epi, mode, st);
-    else if (t.mt == 4) rc = g1x3_go<4, 2>(a, grid, stride, epi, mode, st);
-    else rc = g1x3_go<2, 2>(a, grid, stride, epi, mode, st);
+                                    4.0 * (src_elems + (double)N * M + (double)M * K), st);
+    const int rc = x3_with_tile(t, [&](auto tg) { return g1x3_go<decltype(tg)::mt, decltype(tg)::nt>(a, grid, S, epi, mode, st); });
     conv_prof_end(pe, st);
     if (rc != DC_OK) return rc;
     DC_CHECK_LAUNCH();
     return DC_OK;
 }
 
-extern "C" int dc_gemm1x1x3_fwd_bn(const float* x, const float* weight, const float* bias, float* y, void* ws, int B, int Ci, int Co, int Hi,
-                                   int Wi, int stride, int act, const dc_bn_fold* bn, void* stream) {
+// ---- the 1 x 1 passes with the nullable fold (the contract of dc_conv1x1_*_bn on these kernels): dc_pointwise_* (pointwise.hip) and
+// the family-pinned dc_gemm1x1x3_* entries below
+namespace dc {
+int g1x3_fwd(const float* x, const float* weight, const float* bias, float* y, void* ws, int B, int Ci, int Co, int Hi, int Wi, int stride,
+             int act, const dc_bn_fold* bn, void* stream) {
     if (!x || !weight || !y || !ws || !dc_gemm1x1x3_fwd_ok(B, Ci, Co, Hi, Wi, stride) || act < 0 || act > ACT_LAST) return DC_EINVAL;
     return g1x3_launch(x, weight, y, ws, bias, act, nullptr, nullptr, B, Co, Ci, Co, Ci, 0, Hi, Wi, stride, bn, (hipStream_t)stream);
 }
-extern "C" int dc_gemm1x1x3_fwd(const float* x, const float* weight, const float* bias, float* y, void* ws, int B, int Ci, int Co, int Hi,
-                                int Wi, int stride, int act, void* stream) {
-    return dc_gemm1x1x3_fwd_bn(x, weight, bias, y, ws, B, Ci, Co, Hi, Wi, stride, act, nullptr, stream);
-}
-extern "C" int dc_gemm1x1x3_dgrad_bn(const float* gy, const float* weight, float* dx, void* ws, const float* addend, const float* addend2,
-                                     int B, int Ci, int Co, int Hi, int Wi, int stride, const dc_bn_fold* bn, void* stream) {
+int g1x3_dgrad(const float* gy, const float* weight, float* dx, void* ws, const float* addend, const float* addend2, int B, int Ci, int Co,
+               int Hi, int Wi, int stride, const dc_bn_fold* bn, void* stream) {
     if (!gy || !weight || !dx || !ws || !dc_gemm1x1x3_dgrad_ok(B, Ci, Co, Hi, Wi, stride)) return DC_EINVAL;
     if (stride == 2) {
         // the GEMM runs over the OUTPUT pixels (Hi/2 x Wi/2, stride 1); the scatter epilogue knows the input map through args_s2
@@ -859,83 +841,92 @@ extern "C" int dc_gemm1x1x3_dgrad_bn(const float* gy, const float* weight, float
     }
     return g1x3_launch(gy, weight, dx, ws, nullptr, ACT_NONE, addend, addend2, B, Ci, Co, Co, Ci, 1, Hi, Wi, 1, bn, (hipStream_t)stream);
 }
+}  // namespace dc
+extern "C" int dc_gemm1x1x3_fwd(const float* x, const float* weight, const float* bias, float* y, void* ws, int B, int Ci, int Co, int Hi,
+                                int Wi, int stride, int act, void* stream) {
+    return g1x3_fwd(x, weight, bias, y, ws, B, Ci, Co, Hi, Wi, stride, act, nullptr, stream);
+}
 extern "C" int dc_gemm1x1x3_dgrad(const float* gy, const float* weight, float* dx, void* ws, const float* addend, const float* addend2, int B,
                                   int Ci, int Co, int Hi, int Wi, int stride, void* stream) {
-    return dc_gemm1x1x3_dgrad_bn(gy, weight, dx, ws, addend, addend2, B, Ci, Co, Hi, Wi, stride, nullptr, stream);
+    return g1x3_dgrad(gy, weight, dx, ws, addend, addend2, B, Ci, Co, Hi, Wi, stride, nullptr, stream);
 }
 
-// ---- weight gradient
-static X3Tile x3_wpick(int Co, int Ci) { return {Co >= 128 ? 4 : 2, Ci >= 128 ? 4 : 2}; }
-static int g1x3_wsplits(int tiles, int chunks, X3Tile t) {
-    const int target = 256 * (t.mt * t.nt >= 16 ? 2 : (t.mt * t.nt >= 8 ? 3 : 4));     // the resident slots of the tile's kernel
-    int s = std::max(1, std::min({chunks, ceil_div(target, tiles), 512}));
-    return ceil_div(chunks, ceil_div(chunks, s));                            // no empty split: every slab gets written
+// ---- weight gradient: dw (Co x Kc) over npx = B Ho Wo pixels; Kc = Ci (1 x 1) or 9 Ci (S = 3, the 3 x 3 / 2 gather)
+struct X3WPlan { X3Tile t; int chunks, mtiles, ntiles, splits; };
+static X3WPlan g1x3_wplan(int npx, int Co, int Kc) {
+    X3WPlan p;
+    p.chunks = npx / X3_KC;
+    p.t = {Co >= 128 ? 4 : 2, Kc >= 128 ? 4 : 2};
+    p.mtiles = ceil_div(Co, 32 * p.t.mt); p.ntiles = ceil_div(Kc, 32 * p.t.nt);
+    const int target = 256 * (p.t.mt * p.t.nt >= 16 ? 2 : (p.t.mt * p.t.nt >= 8 ? 3 : 4));     // the resident slots of the tile's kernel
+    const int s = std::max(1, std::min({p.chunks, ceil_div(target, p.mtiles * p.ntiles), 512}));
+    p.splits = ceil_div(p.chunks, ceil_div(p.chunks, s));                      // no empty split: every slab gets written
+    return p;
+}
+static size_t g1x3_wslabs(int npx, int Co, int Kc) {
+    const int splits = g1x3_wplan(npx, Co, Kc).splits;
+    return splits > 1 ? (size_t)splits * Co * Kc * sizeof(float) : 16;
 }
 extern "C" int dc_gemm1x1x3_wgrad_ok(int B, int Ci, int Co, int Hi, int Wi, int stride) {
     return g1x3_common(B, Ci, Co, Hi, Wi, stride) && Ci % 4 == 0 && Co >= 32 && Ci >= 32 && ((size_t)B * (Hi / stride) * (Wi / stride)) % 32 == 0;
 }
 extern "C" size_t dc_gemm1x1x3_wgrad_workspace(int B, int Ci, int Co, int Hi, int Wi, int stride) {
     if (!dc_gemm1x1x3_wgrad_ok(B, Ci, Co, Hi, Wi, stride)) return 0;
-    const int chunks = B * (Hi / stride) * (Wi / stride) / X3_KC;
-    const X3Tile t = x3_wpick(Co, Ci);
-    const int splits = g1x3_wsplits(ceil_div(Co, 32 * t.mt) * ceil_div(Ci, 32 * t.nt), chunks, t);
-    return splits > 1 ? (size_t)splits * Co * Ci * sizeof(float) : 16;
+    return g1x3_wslabs(B * (Hi / stride) * (Wi / stride), Co, Ci);
 }
 template <int MT, int NT>
-static int g1x3_wgo(const G1x3WArgs& a, dim3 grid, int stride, bool bnin, hipStream_t st) {
+static int g1x3_wgo(const G1x3WArgs& a, dim3 grid, int S, bool bnin, hipStream_t st) {
     using T = X3T<MT, NT>;
-    static const bool attr = x3_set_lds(g1x3_wgrad_kernel<MT, NT, 1>, T::LDSW) && x3_set_lds(g1x3_wgrad_kernel<MT, NT, 2>, T::LDSW) &&
-                             x3_set_lds(g1x3_wgrad_kernel<MT, NT, 1, true>, T::LDSW) && x3_set_lds(g1x3_wgrad_kernel<MT, NT, 3>, T::LDSW);
+    static const bool attr = set_max_dynamic_lds(g1x3_wgrad_kernel<MT, NT, 1>, T::LDSW) && set_max_dynamic_lds(g1x3_wgrad_kernel<MT, NT, 2>, T::LDSW) &&
+                             set_max_dynamic_lds(g1x3_wgrad_kernel<MT, NT, 1, true>, T::LDSW) && set_max_dynamic_lds(g1x3_wgrad_kernel<MT, NT, 3>, T::LDSW);
     if (!attr) return DC_ELAUNCH;
-    if (stride == 3) hipLaunchKernelGGL((g1x3_wgrad_kernel<MT, NT, 3>), grid, dim3(256), T::LDSW, st, a);
+    if (S == 3) hipLaunchKernelGGL((g1x3_wgrad_kernel<MT, NT, 3>), grid, dim3(256), T::LDSW, st, a);
     else if (bnin) hipLaunchKernelGGL((g1x3_wgrad_kernel<MT, NT, 1, true>), grid, dim3(256), T::LDSW, st, a);
-    else if (stride == 1) hipLaunchKernelGGL((g1x3_wgrad_kernel<MT, NT, 1>), grid, dim3(256), T::LDSW, st, a);
+    else if (S == 1) hipLaunchKernelGGL((g1x3_wgrad_kernel<MT, NT, 1>), grid, dim3(256), T::LDSW, st, a);
     else hipLaunchKernelGGL((g1x3_wgrad_kernel<MT, NT, 2>), grid, dim3(256), T::LDSW, st, a);
     return DC_OK;
 }
-extern "C" int dc_gemm1x1x3_wgrad_bn(const float* x, const float* gy, float* dweight, void* ws, int B, int Ci, int Co, int Hi, int Wi,
-                                     int stride, const dc_bn_fold* bn, void* stream) {
-    if (!x || !gy || !dweight || !ws || !dc_gemm1x1x3_wgrad_ok(B, Ci, Co, Hi, Wi, stride)) return DC_EINVAL;
+// fill the arguments, profile, launch, reduce the slabs; the shape is validated by the callers
+static int g1x3_wlaunch(const float* x, const float* gy, float* dweight, void* ws, int B, int Ci, int Co, int Hi, int Wi, int S,
+                        const dc_bn_fold* bn, hipStream_t st) {
     if (((size_t)x & 15) || ((size_t)gy & 15) || ((size_t)ws & 15) || ((size_t)dweight & 15)) return DC_EINVAL;
+    const int stride = S == 3 ? 2 : S, Kc = S == 3 ? 9 * Ci : Ci;
     G1x3WArgs a{};
-    a.gy = gy; a.x = x; a.B = B; a.Co = Co; a.Ci = Ci; a.Hi = Hi; a.Wi = Wi; a.Ho = Hi / stride; a.Wo = Wi / stride;
+    a.gy = gy; a.x = x; a.B = B; a.Co = Co; a.Ci = Kc; a.Hi = Hi; a.Wi = Wi; a.Ho = Hi / stride; a.Wo = Wi / stride;
     const bool bnin = bn && bn->in_scale;
     if (bnin) {
-        if (!bn->in_shift || stride != 1 || bn->groups < 1 || B % bn->groups) return DC_EINVAL;
+        if (!bn->in_shift || S != 1 || bn->groups < 1 || B % bn->groups) return DC_EINVAL;
         a.npg = B / bn->groups; a.in_scale = bn->in_scale; a.in_shift = bn->in_shift;
     }
-    a.chunks = B * a.Ho * a.Wo / X3_KC;
-    const X3Tile t = x3_wpick(Co, Ci);
-    a.mtiles = ceil_div(Co, 32 * t.mt); a.ntiles = ceil_div(Ci, 32 * t.nt);
-    a.splits = g1x3_wsplits(a.mtiles * a.ntiles, a.chunks, t);
+    const X3WPlan p = g1x3_wplan(B * a.Ho * a.Wo, Co, Kc);
+    a.chunks = p.chunks; a.mtiles = p.mtiles; a.ntiles = p.ntiles; a.splits = p.splits;
     a.out = a.splits > 1 ? (float*)ws : dweight;
-    hipStream_t st = (hipStream_t)stream;
     const dim3 grid(a.mtiles * a.ntiles, a.splits);
     const double npx = (double)B * a.Ho * a.Wo;
-    hipEvent_t pe = conv_prof_begin(7, 2.0 * npx * Co * Ci, 12.0 * npx * (double)a.mtiles * (32.0 * t.mt) * (double)a.ntiles * (32.0 * t.nt),
-                                    4.0 * (npx * Ci + npx * Co + (double)Co * Ci), st);
-    int rc;
-    if (t.mt == 4 && t.nt == 4) rc = g1x3_wgo<4, 4>(a, grid, stride, bnin, st);
-    else if (t.mt == 2 && t.nt == 4) rc = g1x3_wgo<2, 4>(a, grid, stride, bnin, st);
-    else if (t.mt == 4) rc = g1x3_wgo<4, 2>(a, grid, stride, bnin, st);
-    else rc = g1x3_wgo<2, 2>(a, grid, stride, bnin, st);
+    const double x_elems = S == 3 ? (double)B * Ci * Hi * Wi : npx * Kc;       // (as in g1x3_launch: the input map once)
+    hipEvent_t pe = conv_prof_begin(7, 2.0 * npx * Co * Kc, 12.0 * npx * (double)a.mtiles * (32.0 * p.t.mt) * (double)a.ntiles * (32.0 * p.t.nt),
+                                    4.0 * (x_elems + npx * Co + (double)Co * Kc), st);
+    const int rc = x3_with_tile(p.t, [&](auto tg) { return g1x3_wgo<decltype(tg)::mt, decltype(tg)::nt>(a, grid, S, bnin, st); });
     conv_prof_end(pe, st);
     if (rc != DC_OK) return rc;
     DC_CHECK_LAUNCH();
     if (a.splits > 1) {
-        const int n4 = Co * Ci / 4;
-        hipLaunchKernelGGL(g1x3_slabsum_kernel, dim3(ceil_div(n4, 16)), dim3(256), 0, st, (const x3f4*)ws, (x3f4*)dweight, a.splits, n4);
+        const int n4 = Co * Kc / 4;
+        hipLaunchKernelGGL(slab_reduce16_kernel<gf4>, dim3(ceil_div(n4, 16)), dim3(256), 0, st, (const gf4*)ws, (gf4*)dweight, a.splits, n4);
         DC_CHECK_LAUNCH();
     }
     return DC_OK;
 }
+namespace dc {
+int g1x3_wgrad(const float* x, const float* gy, float* dweight, void* ws, int B, int Ci, int Co, int Hi, int Wi, int stride,
+               const dc_bn_fold* bn, void* stream) {
+    if (!x || !gy || !dweight || !ws || !dc_gemm1x1x3_wgrad_ok(B, Ci, Co, Hi, Wi, stride)) return DC_EINVAL;
+    return g1x3_wlaunch(x, gy, dweight, ws, B, Ci, Co, Hi, Wi, stride, bn, (hipStream_t)stream);
+}
+}  // namespace dc
 extern "C" int dc_gemm1x1x3_wgrad(const float* x, const float* gy, float* dweight, void* ws, int B, int Ci, int Co, int Hi, int Wi,
                                   int stride, void* stream) {
-    return dc_gemm1x1x3_wgrad_bn(x, gy, dweight, ws, B, Ci, Co, Hi, Wi, stride, nullptr, stream);
-}
-/* all three passes of a stride-1 shape take the fold on the split kernels */
-extern "C" int dc_gemm1x1x3_bn_ok(int B, int Ci, int Co, int Hi, int Wi) {
-    return dc_gemm1x1x3_fwd_ok(B, Ci, Co, Hi, Wi, 1) && dc_gemm1x1x3_dgrad_ok(B, Ci, Co, Hi, Wi, 1) && dc_gemm1x1x3_wgrad_ok(B, Ci, Co, Hi, Wi, 1);
+    return g1x3_wgrad(x, gy, dweight, ws, B, Ci, Co, Hi, Wi, stride, nullptr, stream);
 }
 
 // ---- the 3 x 3 / stride 2 / padding 1 convolutions of the trunks on the same kernels (S = 3 loaders): forward and weight gradient.  Called by
@@ -953,72 +944,13 @@ bool g1x3_conv3s2_ok(int B, int Ci, int Co, int Hi, int Wi) {
 }
 size_t g1x3_conv3s2_fwd_ws(int Ci, int Co) { return (size_t)ceil_div(Co, 128) * 128 * 9 * Ci * 6 + 512; }
 int g1x3_conv3s2_fwd(const float* x, const float* weight, float* y, void* ws, int B, int Ci, int Co, int Hi, int Wi, hipStream_t st) {
-    if (((size_t)ws & 15) || ((size_t)x & 15) || ((size_t)y & 15)) return DC_EINVAL;
-    G1x3Args a{};
-    const int M = Co, K = 9 * Ci;
-    a.Mp = ceil_div(M, 128) * 128;
-    a.wa = (unsigned short*)ws; a.x = x; a.out = y; a.act = ACT_NONE;
-    a.B = B; a.M = M; a.K = K; a.Hi = Hi; a.Wi = Wi; a.Ho = Hi / 2; a.Wo = Wi / 2;
-    const int N = B * a.Ho * a.Wo;
-    const X3Tile t = x3_pick(M, N, 2);
-    a.mtiles = ceil_div(M, 32 * t.mt); a.ntiles = ceil_div(N, 32 * t.nt);
-    if (const void* cached = wc_lookup_x3(weight, Ci, Co, 0, a.Mp, K, st)) {
-        a.wa = (const unsigned short*)cached;
-    } else {
-        hipLaunchKernelGGL(g1x3_prep_kernel, dim3(ceil_div(a.Mp * (K / 4), 256)), dim3(256), 0, st, weight, (unsigned short*)ws, 0, M, a.Mp, K);
-        DC_CHECK_LAUNCH();
-    }
-    const dim3 grid(a.mtiles * a.ntiles);
-    hipEvent_t pe = conv_prof_begin(7, 2.0 * (double)N * M * K, 12.0 * (double)grid.x * (32.0 * t.mt) * (32.0 * t.nt) * K,
-                                    4.0 * ((double)B * Ci * Hi * Wi + (double)N * M + (double)M * K), st);
-    int rc;
-    if (t.mt == 4 && t.nt == 4) rc = g1x3_go<4, 4>(a, grid, 3, false, 0, st);
-    else if (t.mt == 2 && t.nt == 4) rc = g1x3_go<2, 4>(a, grid, 3, false, 0, st);
-    else if (t.mt == 4) rc = g1x3_go<4, 2>(a, grid, 3, false, 0, st);
-    else rc = g1x3_go<2, 2>(a, grid, 3, false, 0, st);
-    conv_prof_end(pe, st);
-    if (rc != DC_OK) return rc;
-    DC_CHECK_LAUNCH();
-    return DC_OK;
+    return g1x3_launch(x, weight, y, ws, nullptr, ACT_NONE, nullptr, nullptr, B, Co, 9 * Ci, Co, Ci, 0, Hi, Wi, 3, nullptr, st);
 }
-static void g1x3_conv3s2_wplan(int B, int Ci, int Co, int Hi, int Wi, X3Tile& t, int& chunks, int& mtiles, int& ntiles, int& splits) {
-    chunks = B * (Hi / 2) * (Wi / 2) / X3_KC;
-    t = x3_wpick(Co, 9 * Ci);
-    mtiles = ceil_div(Co, 32 * t.mt); ntiles = ceil_div(9 * Ci, 32 * t.nt);
-    splits = g1x3_wsplits(mtiles * ntiles, chunks, t);
-}
-size_t g1x3_conv3s2_wgrad_ws(int B, int Ci, int Co, int Hi, int Wi) {
-    X3Tile t; int chunks, mt, nt, splits;
-    g1x3_conv3s2_wplan(B, Ci, Co, Hi, Wi, t, chunks, mt, nt, splits);
-    return splits > 1 ? (size_t)splits * Co * 9 * Ci * sizeof(float) : 16;
-}
+size_t g1x3_conv3s2_wgrad_ws(int B, int Ci, int Co, int Hi, int Wi) { return g1x3_wslabs(B * (Hi / 2) * (Wi / 2), Co, 9 * Ci); }
 bool g1x3_conv3s2_wgrad_ok(int B, int Ci, int Co, int Hi, int Wi) {
     return g1x3_conv3s2_ok(B, Ci, Co, Hi, Wi) && ((size_t)B * (Hi / 2) * (Wi / 2)) % 32 == 0;
 }
 int g1x3_conv3s2_wgrad(const float* x, const float* gy, float* dweight, void* ws, int B, int Ci, int Co, int Hi, int Wi, hipStream_t st) {
-    if (((size_t)x & 15) || ((size_t)gy & 15) || ((size_t)ws & 15) || ((size_t)dweight & 15)) return DC_EINVAL;
-    G1x3WArgs a{};
-    a.gy = gy; a.x = x; a.B = B; a.Co = Co; a.Ci = 9 * Ci; a.Hi = Hi; a.Wi = Wi; a.Ho = Hi / 2; a.Wo = Wi / 2;
-    X3Tile t;
-    g1x3_conv3s2_wplan(B, Ci, Co, Hi, Wi, t, a.chunks, a.mtiles, a.ntiles, a.splits);
-    a.out = a.splits > 1 ? (float*)ws : dweight;
-    const dim3 grid(a.mtiles * a.ntiles, a.splits);
-    const double npx = (double)B * a.Ho * a.Wo;
-    hipEvent_t pe = conv_prof_begin(7, 2.0 * npx * Co * 9.0 * Ci, 12.0 * npx * (double)a.mtiles * (32.0 * t.mt) * (double)a.ntiles * (32.0 * t.nt),
-                                    4.0 * ((double)B * Ci * Hi * Wi + npx * Co + 9.0 * Co * Ci), st);
-    int rc;
-    if (t.mt == 4 && t.nt == 4) rc = g1x3_wgo<4, 4>(a, grid, 3, false, st);
-    else if (t.mt == 2 && t.nt == 4) rc = g1x3_wgo<2, 4>(a, grid, 3, false, st);
-    else if (t.mt == 4) rc = g1x3_wgo<4, 2>(a, grid, 3, false, st);
-    else rc = g1x3_wgo<2, 2>(a, grid, 3, false, st);
-    conv_prof_end(pe, st);
-    if (rc != DC_OK) return rc;
-    DC_CHECK_LAUNCH();
-    if (a.splits > 1) {
-        const int n4 = Co * 9 * Ci / 4;
-        hipLaunchKernelGGL(g1x3_slabsum_kernel, dim3(ceil_div(n4, 16)), dim3(256), 0, st, (const x3f4*)ws, (x3f4*)dweight, a.splits, n4);
-        DC_CHECK_LAUNCH();
-    }
-    return DC_OK;
+    return g1x3_wlaunch(x, gy, dweight, ws, B, Ci, Co, Hi, Wi, 3, nullptr, st);
 }
 }  // namespace dc

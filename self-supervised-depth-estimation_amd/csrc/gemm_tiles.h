@@ -85,6 +85,18 @@ __device__ __forceinline__ void mma_chunk32(RA&& ra, RB&& rb, gf4 (&acc)[MT][NT]
     mma_octet<MT, NT>(a1, b1, acc);
 }
 
+// Partials per channel of the forward's statistics epilogue / the data gradient's BatchNorm epilogue on a grid of (32 tile_nt)-column
+// tiles over B images of P pixels (0: not with this group layout): one per wave column of 16 tile_nt pixels; a group boundary must
+// not fall inside one.  Each kernel family passes its own tile pick.  ppg (nullable): partials per group.
+inline int gemm_parts(int tile_nt, int B, int P, int groups, int* ppg) {
+    if (groups < 1 || B % groups) return 0;
+    const int N = B * P;
+    const int cover = 16 * tile_nt;
+    if (groups > 1 && (N / groups) % cover) return 0;
+    if (ppg) *ppg = (N / groups) / cover;
+    return ceil_div(N, 32 * tile_nt) * 2;
+}
+
 extern __shared__ float g1_smem[];
 
 // Sum of `splits` slabs of n elements in a fixed order, 16 split groups x 16 lanes per block: a group adds a contiguous

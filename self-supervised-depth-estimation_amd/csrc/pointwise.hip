@@ -5,14 +5,19 @@
 // gradient (with its zeros) and the split reduction of the weight gradient are part of the kernels.
 //   forward        y[b,m,p]          = sum_k w[m,k] * x[b,k,s*py,s*px]
 //   data gradient  dx[b,k,s*py,s*px] = sum_m w[m,k] * gy[b,m,p]      (0 at the positions the stride skips)
-//   weight grad    dw[m,k]           = sum_{b,p} gy[b,m,p] * x[b,k,s*py,s*px]   split over blocks, fixed-order reduce
+//   weight grad    dw[m,k]           = sum_{b,p} gy[b,m,p] * x[b,k,s*py,s*px]   split over blocks, fixed-order reduce (slab_reduce16_kernel)
 // v_mfma_f32_16x16x4_f32, block = 4 waves = 64 outputs x 64 columns, reduction staged through LDS in chunks of 16.
 //
-// These are the GENERAL kernels (any shape, scalar staging).  Shapes whose pixel count and channel count allow 16-byte
-// staging -- every Bottleneck / downsample / pose-decoder convolution at the BASELINE sizes -- are dispatched to the tiled
-// kernels of gemm1x1.hip by the entry points at the bottom of this file.
+// These are the GENERAL kernels (any shape, scalar staging), and below them the routing of every 1x1 convolution.  Three kernel
+// families: the split-operand bf16 GEMMs of gemm1x1_x3.hip (the default, dc_set_gemm_split) and the fp32-MFMA tiled GEMMs of
+// gemm1x1.hip -- shapes whose pixel count and channel count allow 16-byte staging: every Bottleneck / downsample / pose-decoder
+// convolution at the BASELINE sizes -- and these kernels for the rest.  pw_family() picks one per pass; dc_pointwise_* (queries and
+// launches: what depthcore/ops.py and depthcore/bnfold.py call) all go through it.  dc_conv1x1_* stay pinned to fp32-MFMA / general
+// and dc_gemm1x1x3_* to the split kernels, for A/B comparisons.
 #include "dc_common.h"
 #include "gemm1x1.h"
+#include "gemm1x1_x3.h"
+#include "gemm_tiles.h"
 
 #include <algorithm>
 
@@ -191,66 +196,12 @@ __global__ __launch_bounds__(256) void pw_wgrad_kernel(PwArgs a) {
         }
 }
 
-// dw = sum of the slabs, fixed order: 16 split groups x 16 outputs per block, groups combined in order through LDS
-__global__ __launch_bounds__(256) void pw_wreduce_kernel(const float* __restrict__ slab, float* __restrict__ dw, int splits, int n) {
-    __shared__ float sm[16][17];
-    const int o = threadIdx.x & 15, grp = threadIdx.x >> 4;
-    const int i = blockIdx.x * 16 + o;
-    const int per = (splits + 15) / 16;
-    float v = 0.f;
-    if (i < n) {
-        const int s1 = min(splits, (grp + 1) * per);
-        for (int s = grp * per; s < s1; ++s) v += slab[(size_t)s * n + i];
-    }
-    sm[grp][o] = v;
-    __syncthreads();
-    if (grp == 0 && i < n) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) t += sm[k][o];
-        dw[i] = t;
-    }
-}
-
 static int pw_splits(int B, int Ho, int Wo, int M, int K) {
     const int nchunks = B * ceil_div(Ho * Wo, PK);
     const int outer = ceil_div(M, PT) * ceil_div(K, PT);
     return std::max(1, std::min({nchunks / 4 + 1, ceil_div(1024, outer), 256}));
 }
 
-}  // namespace dc
-
-using namespace dc;
-
-static bool pw_shape_ok(int B, int Ci, int Co, int Hi, int Wi, int s) {
-    return B > 0 && Ci > 0 && Co > 0 && Hi > 0 && Wi > 0 && (s == 1 || (s == 2 && !(Hi & 1) && !(Wi & 1)));
-}
-
-extern "C" size_t dc_conv1x1_wgrad_workspace(int B, int Ci, int Co, int Hi, int Wi, int stride) {
-    if (!pw_shape_ok(B, Ci, Co, Hi, Wi, stride)) return 0;
-    if (dc_gemm1x1_wgrad_ok(B, Ci, Co, Hi, Wi, stride)) return dc_gemm1x1_wgrad_workspace(B, Ci, Co, Hi, Wi, stride);
-    return (size_t)pw_splits(B, Hi / stride, Wi / stride, Co, Ci) * Co * Ci * sizeof(float);
-}
-
-extern "C" int dc_conv1x1_bias_act_fwd(const float* x, const float* weight, const float* bias, float* y, int B, int Ci, int Co, int Hi,
-                                       int Wi, int stride, int act, void* stream) {
-    if (!x || !weight || !y || !pw_shape_ok(B, Ci, Co, Hi, Wi, stride) || act < 0 || act > ACT_LAST) return DC_EINVAL;
-    if (dc_gemm1x1_fwd_ok(B, Ci, Co, Hi, Wi, stride))
-        return dc_gemm1x1_fwd(x, weight, bias, y, B, Ci, Co, Hi, Wi, stride, act, nullptr, stream);
-    PwArgs a{};
-    a.bias = bias; a.act = act;
-    a.a = weight; a.b = x; a.out = y; a.B = B; a.M = Co; a.K = Ci; a.Hi = Hi; a.Wi = Wi; a.Ho = Hi / stride; a.Wo = Wi / stride; a.s = stride;
-    hipLaunchKernelGGL(pw_fwd_kernel, dim3(ceil_div(a.Ho * a.Wo, PT), ceil_div(Co, PT), B), dim3(256), 0, (hipStream_t)stream, a);
-    DC_CHECK_LAUNCH();
-    return DC_OK;
-}
-
-extern "C" int dc_conv1x1_fwd(const float* x, const float* weight, float* y, int B, int Ci, int Co, int Hi, int Wi, int stride,
-                              void* stream) {
-    return dc_conv1x1_bias_act_fwd(x, weight, nullptr, y, B, Ci, Co, Hi, Wi, stride, ACT_NONE, stream);
-}
-
-namespace dc {
 __global__ __launch_bounds__(256) void add_inplace_kernel(float* __restrict__ y, const float* __restrict__ a, size_t n) {
     const size_t n4 = n / 4;
     for (size_t i = blockIdx.x * 256ull + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256ull) {
@@ -267,45 +218,207 @@ int add_inplace(float* y, const float* a, size_t n, hipStream_t st) {
     DC_CHECK_LAUNCH();
     return DC_OK;
 }
+
 }  // namespace dc
 
-extern "C" int dc_conv1x1_dgrad_add(const float* gy, const float* weight, float* dx, const float* addend, int B, int Ci, int Co, int Hi,
-                                    int Wi, int stride, void* stream) {
-    if (!gy || !weight || !dx || !pw_shape_ok(B, Ci, Co, Hi, Wi, stride)) return DC_EINVAL;
-    if (dc_gemm1x1_dgrad_ok(B, Ci, Co, Hi, Wi, stride)) {
-        // the tiled GEMM adds it in its store epilogue (every element of dx is written once, densely, at either stride)
-        return dc_gemm1x1_dgrad(gy, weight, dx, addend, nullptr, B, Ci, Co, Hi, Wi, stride, nullptr, stream);
-    }
+using namespace dc;
+
+static bool pw_shape_ok(int B, int Ci, int Co, int Hi, int Wi, int s) {
+    return B > 0 && Ci > 0 && Co > 0 && Hi > 0 && Wi > 0 && (s == 1 || (s == 2 && !(Hi & 1) && !(Wi & 1)));
+}
+
+// ---- launches of the general kernels (any shape that passes pw_shape_ok) ---------------------------------------------------------
+static PwArgs pw_args(const float* a_, const float* b_, float* out, int B, int Ci, int Co, int Hi, int Wi, int stride) {
     PwArgs a{};
-    a.a = weight; a.b = gy; a.out = dx; a.B = B; a.M = Co; a.K = Ci; a.Hi = Hi; a.Wi = Wi; a.Ho = Hi / stride; a.Wo = Wi / stride; a.s = stride;
-    hipLaunchKernelGGL(pw_dgrad_kernel, dim3(ceil_div(a.Ho * a.Wo, PT), ceil_div(Ci, PT), B), dim3(256), 0, (hipStream_t)stream, a);
+    a.a = a_; a.b = b_; a.out = out; a.B = B; a.M = Co; a.K = Ci; a.Hi = Hi; a.Wi = Wi; a.Ho = Hi / stride; a.Wo = Wi / stride; a.s = stride;
+    return a;
+}
+static int pw_fwd(const float* x, const float* weight, const float* bias, float* y, int B, int Ci, int Co, int Hi, int Wi, int stride,
+                  int act, hipStream_t st) {
+    if (!x || !weight || !y || act < 0 || act > ACT_LAST) return DC_EINVAL;
+    PwArgs a = pw_args(weight, x, y, B, Ci, Co, Hi, Wi, stride);
+    a.bias = bias; a.act = act;
+    hipLaunchKernelGGL(pw_fwd_kernel, dim3(ceil_div(a.Ho * a.Wo, PT), ceil_div(Co, PT), B), dim3(256), 0, st, a);
     DC_CHECK_LAUNCH();
-    return addend ? add_inplace(dx, addend, (size_t)B * Ci * Hi * Wi, (hipStream_t)stream) : DC_OK;
+    return DC_OK;
 }
-
-extern "C" int dc_conv1x1_dgrad(const float* gy, const float* weight, float* dx, int B, int Ci, int Co, int Hi, int Wi, int stride,
-                                void* stream) {
-    return dc_conv1x1_dgrad_add(gy, weight, dx, nullptr, B, Ci, Co, Hi, Wi, stride, stream);
+// the addends (nullable) take a pass each: these kernels' scatter epilogue cannot add
+static int pw_dgrad(const float* gy, const float* weight, float* dx, const float* addend, const float* addend2, int B, int Ci, int Co,
+                    int Hi, int Wi, int stride, hipStream_t st) {
+    if (!gy || !weight || !dx) return DC_EINVAL;
+    const PwArgs a = pw_args(weight, gy, dx, B, Ci, Co, Hi, Wi, stride);
+    hipLaunchKernelGGL(pw_dgrad_kernel, dim3(ceil_div(a.Ho * a.Wo, PT), ceil_div(Ci, PT), B), dim3(256), 0, st, a);
+    DC_CHECK_LAUNCH();
+    const size_t n = (size_t)B * Ci * Hi * Wi;
+    int rc = addend ? add_inplace(dx, addend, n, st) : DC_OK;
+    if (rc == DC_OK && addend2) rc = add_inplace(dx, addend2, n, st);
+    return rc;
 }
-
-extern "C" int dc_conv1x1_wgrad(const float* x, const float* gy, float* dweight, void* ws, int B, int Ci, int Co, int Hi, int Wi,
-                                int stride, void* stream) {
-    if (!x || !gy || !dweight || !ws || !pw_shape_ok(B, Ci, Co, Hi, Wi, stride)) return DC_EINVAL;
-    if (dc_gemm1x1_wgrad_ok(B, Ci, Co, Hi, Wi, stride))
-        return dc_gemm1x1_wgrad(x, gy, dweight, ws, B, Ci, Co, Hi, Wi, stride, nullptr, stream);
-    PwArgs a{};
-    a.a = gy; a.b = x; a.out = (float*)ws; a.B = B; a.M = Co; a.K = Ci; a.Hi = Hi; a.Wi = Wi; a.Ho = Hi / stride; a.Wo = Wi / stride; a.s = stride;
+static size_t pw_wgrad_workspace(int B, int Ci, int Co, int Hi, int Wi, int stride) {
+    return (size_t)pw_splits(B, Hi / stride, Wi / stride, Co, Ci) * Co * Ci * sizeof(float);
+}
+static int pw_wgrad(const float* x, const float* gy, float* dweight, void* ws, int B, int Ci, int Co, int Hi, int Wi, int stride,
+                    hipStream_t st) {
+    if (!x || !gy || !dweight || !ws) return DC_EINVAL;
+    PwArgs a = pw_args(gy, x, (float*)ws, B, Ci, Co, Hi, Wi, stride);
     a.splits = pw_splits(B, a.Ho, a.Wo, Co, Ci);
-    hipLaunchKernelGGL(pw_wgrad_kernel, dim3(a.splits, ceil_div(Co, PT), ceil_div(Ci, PT)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(pw_wgrad_kernel, dim3(a.splits, ceil_div(Co, PT), ceil_div(Ci, PT)), dim3(256), 0, st, a);
     DC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(pw_wreduce_kernel, dim3(ceil_div(Co * Ci, 16)), dim3(256), 0, (hipStream_t)stream, (const float*)ws, dweight,
-                       a.splits, Co * Ci);
+    hipLaunchKernelGGL(slab_reduce16_kernel<float>, dim3(ceil_div(Co * Ci, 16)), dim3(256), 0, st, (const float*)ws, dweight, a.splits, Co * Ci);
     DC_CHECK_LAUNCH();
     return DC_OK;
 }
 
-// ---- the 1x1 convolutions with a BatchNorm folded in (dc_bn_fold): tiled kernels only ----------------------------------------
+// =====================================================================================================================
+// The dispatcher: which kernel family takes a pass.  Every dc_pointwise_* entry -- the workspace and partial-count queries and
+// the three launches -- asks THIS function, so a query and its launch cannot disagree (the partial layouts of the BatchNorm
+// epilogues follow each family's own tiles: a count taken for the wrong family is an out-of-bounds epilogue write).  The split
+// mode (dc_get_gemm_split) is read on every call.
+// =====================================================================================================================
+enum PwFamily { FAM_NONE, FAM_X3, FAM_G1, FAM_PW };      // no family takes it (DC_EINVAL) / split bf16 / fp32-MFMA tiled / general
+
 static bool bn_active(const dc_bn_fold* bn) { return bn && (bn->in_scale || bn->stat_part || bn->bwd_part); }
+
+static PwFamily pw_family(int pass, const dc_bn_fold* bn, int B, int Ci, int Co, int Hi, int Wi, int s) {
+    if (!pw_shape_ok(B, Ci, Co, Hi, Wi, s)) return FAM_NONE;
+    const bool split = dc_get_gemm_split() != 0;
+    bool x3, g1, need_g1;      // the split kernels take it / the fp32-MFMA kernels can / nothing else can (the fold has no general kernel)
+    switch (pass) {
+    case DC_PASS_FWD:
+        // With a fold struct the split family is gated on its statistics layout for bn->groups EVEN WHEN no statistics (or nothing at
+        // all: every pointer null) are asked for: that is how the folded path has always chosen, and gating on dc_gemm1x1x3_fwd_ok
+        // instead would move the shapes whose group boundary falls inside a wave column to the other family.
+        x3 = bn ? dc_gemm1x1x3_stat_parts(B, Ci, Co, Hi, Wi, s, bn->groups, nullptr) > 0 : dc_gemm1x1x3_fwd_ok(B, Ci, Co, Hi, Wi, s) != 0;
+        g1 = dc_gemm1x1_fwd_ok(B, Ci, Co, Hi, Wi, s);
+        need_g1 = bn_active(bn);
+        break;
+    case DC_PASS_DGRAD:
+        need_g1 = bn && bn->bwd_part;      // the BatchNorm-backward epilogue: stride 1, the family the partials were counted for
+        x3 = need_g1 ? s == 1 && dc_gemm1x1x3_bwd_parts(B, Ci, Co, Hi, Wi, bn->groups, nullptr) > 0 : dc_gemm1x1x3_dgrad_ok(B, Ci, Co, Hi, Wi, s) != 0;
+        g1 = dc_gemm1x1_dgrad_ok(B, Ci, Co, Hi, Wi, s) && !(need_g1 && s != 1);
+        break;
+    case DC_PASS_WGRAD:
+        x3 = dc_gemm1x1x3_wgrad_ok(B, Ci, Co, Hi, Wi, s);
+        g1 = dc_gemm1x1_wgrad_ok(B, Ci, Co, Hi, Wi, s);
+        need_g1 = bn && bn->in_scale;
+        break;
+    default:
+        return FAM_NONE;
+    }
+    if (split && x3) return FAM_X3;
+    if (g1) return FAM_G1;
+    return need_g1 ? FAM_NONE : FAM_PW;
+}
+
+// a fold that asks for the partials of one epilogue, for the queries (the pointer is only tested, never followed)
+static dc_bn_fold pw_probe_fold(int groups, bool stat, bool bwd) {
+    static float mark;
+    dc_bn_fold f{};
+    f.groups = groups;
+    if (stat) f.stat_part = &mark;
+    if (bwd) f.bwd_part = &mark;
+    return f;
+}
+
+extern "C" size_t dc_pointwise_workspace(int pass, const dc_bn_fold* bn, int B, int Ci, int Co, int Hi, int Wi, int stride) {
+    size_t n = 0;
+    const bool wgrad = pass == DC_PASS_WGRAD;
+    switch (pw_family(pass, bn, B, Ci, Co, Hi, Wi, stride)) {
+    case FAM_X3: n = wgrad ? dc_gemm1x1x3_wgrad_workspace(B, Ci, Co, Hi, Wi, stride) : dc_gemm1x1x3_workspace(Ci, Co); break;
+    case FAM_G1: n = wgrad ? dc_gemm1x1_wgrad_workspace(B, Ci, Co, Hi, Wi, stride) : 0; break;
+    case FAM_PW: n = wgrad ? pw_wgrad_workspace(B, Ci, Co, Hi, Wi, stride) : 0; break;
+    case FAM_NONE: break;
+    }
+    return std::max<size_t>(n, 16);
+}
+extern "C" int dc_pointwise_stat_parts(int B, int Ci, int Co, int Hi, int Wi, int stride, int groups, int* ppg) {
+    const dc_bn_fold f = pw_probe_fold(groups, true, false);
+    switch (pw_family(DC_PASS_FWD, &f, B, Ci, Co, Hi, Wi, stride)) {
+    case FAM_X3: return dc_gemm1x1x3_stat_parts(B, Ci, Co, Hi, Wi, stride, groups, ppg);
+    case FAM_G1: return dc_gemm1x1_stat_parts(B, Ci, Co, Hi, Wi, stride, groups, ppg);
+    default: return 0;
+    }
+}
+extern "C" int dc_pointwise_bwd_parts(int B, int Ci, int Co, int Hi, int Wi, int stride, int groups, int* ppg) {
+    const dc_bn_fold f = pw_probe_fold(groups, false, true);
+    switch (pw_family(DC_PASS_DGRAD, &f, B, Ci, Co, Hi, Wi, stride)) {
+    case FAM_X3: return dc_gemm1x1x3_bwd_parts(B, Ci, Co, Hi, Wi, groups, ppg);
+    case FAM_G1: return dc_gemm1x1_bwd_parts(B, Ci, Co, Hi, Wi, stride, groups, ppg);
+    default: return 0;
+    }
+}
+extern "C" int dc_pointwise_fwd(const float* x, const float* weight, const float* bias, float* y, void* ws, int B, int Ci, int Co, int Hi,
+                                int Wi, int stride, int act, const dc_bn_fold* bn, void* stream) {
+    switch (pw_family(DC_PASS_FWD, bn, B, Ci, Co, Hi, Wi, stride)) {
+    case FAM_X3: return g1x3_fwd(x, weight, bias, y, ws, B, Ci, Co, Hi, Wi, stride, act, bn, stream);
+    case FAM_G1: return dc_gemm1x1_fwd(x, weight, bias, y, B, Ci, Co, Hi, Wi, stride, act, bn_active(bn) ? bn : nullptr, stream);
+    case FAM_PW: return pw_fwd(x, weight, bias, y, B, Ci, Co, Hi, Wi, stride, act, (hipStream_t)stream);
+    default: return DC_EINVAL;
+    }
+}
+extern "C" int dc_pointwise_dgrad(const float* gy, const float* weight, float* dx, void* ws, const float* addend, const float* addend2,
+                                  int B, int Ci, int Co, int Hi, int Wi, int stride, const dc_bn_fold* bn, void* stream) {
+    if (!(bn && bn->bwd_part)) bn = nullptr;      // only the BatchNorm-backward epilogue concerns this pass
+    switch (pw_family(DC_PASS_DGRAD, bn, B, Ci, Co, Hi, Wi, stride)) {
+    case FAM_X3: return g1x3_dgrad(gy, weight, dx, ws, addend, addend2, B, Ci, Co, Hi, Wi, stride, bn, stream);
+    case FAM_G1: return dc_gemm1x1_dgrad(gy, weight, dx, addend, addend2, B, Ci, Co, Hi, Wi, stride, bn, stream);
+    case FAM_PW: return pw_dgrad(gy, weight, dx, addend, addend2, B, Ci, Co, Hi, Wi, stride, (hipStream_t)stream);
+    default: return DC_EINVAL;
+    }
+}
+extern "C" int dc_pointwise_wgrad(const float* x, const float* gy, float* dweight, void* ws, int B, int Ci, int Co, int Hi, int Wi,
+                                  int stride, const dc_bn_fold* bn, void* stream) {
+    switch (pw_family(DC_PASS_WGRAD, bn, B, Ci, Co, Hi, Wi, stride)) {
+    case FAM_X3: return g1x3_wgrad(x, gy, dweight, ws, B, Ci, Co, Hi, Wi, stride, bn, stream);
+    case FAM_G1: return dc_gemm1x1_wgrad(x, gy, dweight, ws, B, Ci, Co, Hi, Wi, stride, bn && bn->in_scale ? bn : nullptr, stream);
+    case FAM_PW: return pw_wgrad(x, gy, dweight, ws, B, Ci, Co, Hi, Wi, stride, (hipStream_t)stream);
+    default: return DC_EINVAL;
+    }
+}
+
+// ---- the family-pinned entries (A/B comparisons in tests/ and tools/): fp32-MFMA where the shape allows, else general; never split ----
+extern "C" size_t dc_conv1x1_wgrad_workspace(int B, int Ci, int Co, int Hi, int Wi, int stride) {
+    if (!pw_shape_ok(B, Ci, Co, Hi, Wi, stride)) return 0;
+    if (dc_gemm1x1_wgrad_ok(B, Ci, Co, Hi, Wi, stride)) return dc_gemm1x1_wgrad_workspace(B, Ci, Co, Hi, Wi, stride);
+    return pw_wgrad_workspace(B, Ci, Co, Hi, Wi, stride);
+}
+extern "C" int dc_conv1x1_bias_act_fwd(const float* x, const float* weight, const float* bias, float* y, int B, int Ci, int Co, int Hi,
+                                       int Wi, int stride, int act, void* stream) {
+    if (!pw_shape_ok(B, Ci, Co, Hi, Wi, stride)) return DC_EINVAL;
+    if (dc_gemm1x1_fwd_ok(B, Ci, Co, Hi, Wi, stride))
+        return dc_gemm1x1_fwd(x, weight, bias, y, B, Ci, Co, Hi, Wi, stride, act, nullptr, stream);
+    return pw_fwd(x, weight, bias, y, B, Ci, Co, Hi, Wi, stride, act, (hipStream_t)stream);
+}
+extern "C" int dc_conv1x1_fwd(const float* x, const float* weight, float* y, int B, int Ci, int Co, int Hi, int Wi, int stride,
+                              void* stream) {
+    return dc_conv1x1_bias_act_fwd(x, weight, nullptr, y, B, Ci, Co, Hi, Wi, stride, ACT_NONE, stream);
+}
+// dx = data gradient + addend + addend2 (both nullable): an input with up to three consumers; the tiled GEMM sums them in its store
+// epilogue (every element of dx is written once, densely, at either stride)
+extern "C" int dc_conv1x1_dgrad_add2(const float* gy, const float* weight, float* dx, const float* addend, const float* addend2, int B,
+                                     int Ci, int Co, int Hi, int Wi, int stride, void* stream) {
+    if (!pw_shape_ok(B, Ci, Co, Hi, Wi, stride)) return DC_EINVAL;
+    if (dc_gemm1x1_dgrad_ok(B, Ci, Co, Hi, Wi, stride))
+        return dc_gemm1x1_dgrad(gy, weight, dx, addend, addend2, B, Ci, Co, Hi, Wi, stride, nullptr, stream);
+    return pw_dgrad(gy, weight, dx, addend, addend2, B, Ci, Co, Hi, Wi, stride, (hipStream_t)stream);
+}
+extern "C" int dc_conv1x1_dgrad_add(const float* gy, const float* weight, float* dx, const float* addend, int B, int Ci, int Co, int Hi,
+                                    int Wi, int stride, void* stream) {
+    return dc_conv1x1_dgrad_add2(gy, weight, dx, addend, nullptr, B, Ci, Co, Hi, Wi, stride, stream);
+}
+extern "C" int dc_conv1x1_dgrad(const float* gy, const float* weight, float* dx, int B, int Ci, int Co, int Hi, int Wi, int stride,
+                                void* stream) {
+    return dc_conv1x1_dgrad_add2(gy, weight, dx, nullptr, nullptr, B, Ci, Co, Hi, Wi, stride, stream);
+}
+extern "C" int dc_conv1x1_wgrad(const float* x, const float* gy, float* dweight, void* ws, int B, int Ci, int Co, int Hi, int Wi,
+                                int stride, void* stream) {
+    if (!pw_shape_ok(B, Ci, Co, Hi, Wi, stride)) return DC_EINVAL;
+    if (dc_gemm1x1_wgrad_ok(B, Ci, Co, Hi, Wi, stride))
+        return dc_gemm1x1_wgrad(x, gy, dweight, ws, B, Ci, Co, Hi, Wi, stride, nullptr, stream);
+    return pw_wgrad(x, gy, dweight, ws, B, Ci, Co, Hi, Wi, stride, (hipStream_t)stream);
+}
+
+// ... with a BatchNorm folded in (dc_bn_fold): the fp32-MFMA kernels only
 extern "C" int dc_conv1x1_bn_ok(int B, int Ci, int Co, int Hi, int Wi) {
     return dc_gemm1x1_fwd_ok(B, Ci, Co, Hi, Wi, 1) && dc_gemm1x1_dgrad_ok(B, Ci, Co, Hi, Wi, 1) && dc_gemm1x1_wgrad_ok(B, Ci, Co, Hi, Wi, 1);
 }
@@ -326,17 +439,6 @@ extern "C" int dc_conv1x1_dgrad_bn(const float* gy, const float* weight, float* 
     if (!bn || !bn->bwd_part) return dc_conv1x1_dgrad_add(gy, weight, dx, addend, B, Ci, Co, Hi, Wi, stride, stream);
     if (stride != 1 || !dc_gemm1x1_dgrad_ok(B, Ci, Co, Hi, Wi, stride)) return DC_EINVAL;
     return dc_gemm1x1_dgrad(gy, weight, dx, addend, nullptr, B, Ci, Co, Hi, Wi, stride, bn, stream);
-}
-
-// dx = data gradient + addend + addend2 (both nullable): an input with up to three consumers, summed in one store epilogue
-extern "C" int dc_conv1x1_dgrad_add2(const float* gy, const float* weight, float* dx, const float* addend, const float* addend2, int B,
-                                     int Ci, int Co, int Hi, int Wi, int stride, void* stream) {
-    if (!addend2) return dc_conv1x1_dgrad_add(gy, weight, dx, addend, B, Ci, Co, Hi, Wi, stride, stream);
-    if (!gy || !weight || !dx || !pw_shape_ok(B, Ci, Co, Hi, Wi, stride)) return DC_EINVAL;
-    if (dc_gemm1x1_dgrad_ok(B, Ci, Co, Hi, Wi, stride))
-        return dc_gemm1x1_dgrad(gy, weight, dx, addend, addend2, B, Ci, Co, Hi, Wi, stride, nullptr, stream);
-    const int rc = dc_conv1x1_dgrad_add(gy, weight, dx, addend, B, Ci, Co, Hi, Wi, stride, stream);
-    return rc != DC_OK ? rc : add_inplace(dx, addend2, (size_t)B * Ci * Hi * Wi, (hipStream_t)stream);
 }
 extern "C" int dc_conv1x1_wgrad_bn(const float* x, const float* gy, float* dweight, void* ws, int B, int Ci, int Co, int Hi, int Wi,
                                    int stride, const dc_bn_fold* bn, void* stream) {

@@ -455,10 +455,6 @@ __global__ __launch_bounds__(64 * WR_GROUPS) void wino_wreduce_col_kernel(const 
 }
 
 static inline size_t wg_lds(int mr, int ng) { return (size_t)ng * (2 * 16 * mr * WG_GPS + 2 * WG_KT * WG_XPS) * sizeof(float); }
-template <typename K>
-static bool wg_set_lds(K kernel, size_t bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
-}
 
 struct WgPlan { int RH, RW, GRS, XRS, regs_x, regs_y, nsub, mblocks, kblocks, splits, mr, ng; };
 
@@ -528,13 +524,13 @@ static int wg_launch(const float* x0, int C0, int up0, const float* x1, int C1, 
     hipEvent_t pe = conv_prof_begin(1, 2.0 * B * (double)Co * Ci * 9.0 * H * W,
                                     2.0 * 16.0 * (double)p.nsub * 16.0 * (double)(p.mblocks * 16 * p.mr) * (p.kblocks * WG_KT),
                                     (double)b0 + (double)b1 + (double)gb + 36.0 * Co * Ci, st);
-    static const bool attr = wg_set_lds(wino_wgrad_kernel<true, 4, 1>, wg_lds(4, 1)) && wg_set_lds(wino_wgrad_kernel<false, 4, 1>, wg_lds(4, 1)) &&
-                             wg_set_lds(wino_wgrad_kernel<true, 4, 2>, wg_lds(4, 2)) && wg_set_lds(wino_wgrad_kernel<false, 4, 2>, wg_lds(4, 2)) &&
-                             wg_set_lds(wino_wgrad_kernel<true, 2, 1>, wg_lds(2, 1)) && wg_set_lds(wino_wgrad_kernel<false, 2, 1>, wg_lds(2, 1)) &&
-                             wg_set_lds(wino_wgrad_kernel<false, 4, 1, 1>, wg_lds(4, 1)) && wg_set_lds(wino_wgrad_kernel<false, 4, 2, 1>, wg_lds(4, 2)) &&
-                             wg_set_lds(wino_wgrad_kernel<false, 2, 1, 1>, wg_lds(2, 1)) &&
-                             wg_set_lds(wino_wgrad_kernel<false, 4, 1, 2>, wg_lds(4, 1)) && wg_set_lds(wino_wgrad_kernel<false, 4, 2, 2>, wg_lds(4, 2)) &&
-                             wg_set_lds(wino_wgrad_kernel<false, 2, 1, 2>, wg_lds(2, 1));
+    static const bool attr = set_max_dynamic_lds(wino_wgrad_kernel<true, 4, 1>, wg_lds(4, 1)) && set_max_dynamic_lds(wino_wgrad_kernel<false, 4, 1>, wg_lds(4, 1)) &&
+                             set_max_dynamic_lds(wino_wgrad_kernel<true, 4, 2>, wg_lds(4, 2)) && set_max_dynamic_lds(wino_wgrad_kernel<false, 4, 2>, wg_lds(4, 2)) &&
+                             set_max_dynamic_lds(wino_wgrad_kernel<true, 2, 1>, wg_lds(2, 1)) && set_max_dynamic_lds(wino_wgrad_kernel<false, 2, 1>, wg_lds(2, 1)) &&
+                             set_max_dynamic_lds(wino_wgrad_kernel<false, 4, 1, 1>, wg_lds(4, 1)) && set_max_dynamic_lds(wino_wgrad_kernel<false, 4, 2, 1>, wg_lds(4, 2)) &&
+                             set_max_dynamic_lds(wino_wgrad_kernel<false, 2, 1, 1>, wg_lds(2, 1)) &&
+                             set_max_dynamic_lds(wino_wgrad_kernel<false, 4, 1, 2>, wg_lds(4, 1)) && set_max_dynamic_lds(wino_wgrad_kernel<false, 4, 2, 2>, wg_lds(4, 2)) &&
+                             set_max_dynamic_lds(wino_wgrad_kernel<false, 2, 1, 2>, wg_lds(2, 1));
     if (!attr) return DC_ELAUNCH;
     const dim3 grid(p.splits * nmk);
     const size_t lds = wg_lds(p.mr, p.ng);

@@ -27,6 +27,7 @@ OPT_NO_GRAD = 16
 OPT_PRED_MASK = 32
 OPT_PHOTO_SPLIT, OPT_PHOTO_FULL = 64, 128
 PREC_F32, PREC_BF16 = 0, 1
+PASS_FWD, PASS_DGRAD, PASS_WGRAD = 0, 1, 2      # dc_pointwise_workspace
 
 _ERR = {-1: "DC_EINVAL (bad shape / null pointer / unsupported option)",
         -2: "DC_ELAUNCH (hip launch failed)",
@@ -219,15 +220,17 @@ def _sig(lib):
         "dc_gemm1x1x3_workspace": (c_size_t, [i, i]),
         "dc_gemm1x1x3_fwd": (i, [p, p, p, p, p, i, i, i, i, i, i, i, p]),
         "dc_gemm1x1x3_dgrad": (i, [p, p, p, p, p, p, i, i, i, i, i, i, p]),
-        "dc_gemm1x1x3_bn_ok": (i, [i, i, i, i, i]),
         "dc_gemm1x1x3_stat_parts": (i, [i, i, i, i, i, i, i, POINTER(c_int)]),
         "dc_gemm1x1x3_bwd_parts": (i, [i, i, i, i, i, i, POINTER(c_int)]),
-        "dc_gemm1x1x3_fwd_bn": (i, [p, p, p, p, p, i, i, i, i, i, i, i, POINTER(BnFold), p]),
-        "dc_gemm1x1x3_dgrad_bn": (i, [p, p, p, p, p, p, i, i, i, i, i, i, POINTER(BnFold), p]),
-        "dc_gemm1x1x3_wgrad_bn": (i, [p, p, p, p, i, i, i, i, i, i, POINTER(BnFold), p]),
         "dc_gemm1x1x3_wgrad_ok": (i, [i, i, i, i, i, i]),
         "dc_gemm1x1x3_wgrad_workspace": (c_size_t, [i, i, i, i, i, i]),
         "dc_gemm1x1x3_wgrad": (i, [p, p, p, p, i, i, i, i, i, i, p]),
+        "dc_pointwise_workspace": (c_size_t, [i, POINTER(BnFold), i, i, i, i, i, i]),
+        "dc_pointwise_stat_parts": (i, [i, i, i, i, i, i, i, POINTER(c_int)]),
+        "dc_pointwise_bwd_parts": (i, [i, i, i, i, i, i, i, POINTER(c_int)]),
+        "dc_pointwise_fwd": (i, [p, p, p, p, p, i, i, i, i, i, i, i, POINTER(BnFold), p]),
+        "dc_pointwise_dgrad": (i, [p, p, p, p, p, p, i, i, i, i, i, i, POINTER(BnFold), p]),
+        "dc_pointwise_wgrad": (i, [p, p, p, p, i, i, i, i, i, i, POINTER(BnFold), p]),
         "dc_set_photo_full": (i, [i]),
         "dc_get_photo_full": (i, []),
         "dc_set_wino_f4": (i, [i]),
