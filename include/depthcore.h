@@ -250,6 +250,32 @@ int dc_conv3x3_bwd(const float* x0, int C0, int up0, const float* x1, int C1, co
 int dc_conv3x3_bwd_add(const float* x0, int C0, int up0, const float* x1, int C1, const float* weight,
                        const float* y, const float* gy, float* dx0, float* dx1, const float* addend0, const float* addend1,
                        float* dweight, float* dbias, void* ws, int B, int Co, int H, int W, int act, int pad_mode, void* stream);
+/* What the two launches above run for one block, decided by the function they call themselves (csrc/conv3x3.hip: conv_plan), under
+ * the calling thread's matrix precision, dc_set_dgrad_split's mode and the DC_* environment of the process.  `want`: the results
+ * whose pointers the backward gets non-null.  DC_EINVAL for the shape / act / pad_mode combinations the launches refuse (or a
+ * NULL plan); touches no device memory and makes no HIP call.  Tests and diagnostics; the launches need no query. */
+enum { DC_C3_WANT_DX0 = 1, DC_C3_WANT_DX1 = 2, DC_C3_WANT_DWEIGHT = 4, DC_C3_WANT_DBIAS = 8 };
+enum { DC_C3_FWD_HEAD = 0, DC_C3_FWD_BF16, DC_C3_FWD_WINO, DC_C3_FWD_DIRECT };   /* dispconv.hip / conv_bf16.hip / wino.hip / conv_gemm*_kernel */
+/* g' = gy act'(y): nobody reads it / no activation: gy itself / formed by the consuming kernel / conv_gprime_kernel / conv_gprime_dbias_kernel */
+enum { DC_C3_GP_UNUSED = 0, DC_C3_GP_GY, DC_C3_GP_ON_THE_FLY, DC_C3_GP_KERNEL, DC_C3_GP_DBIAS_KERNEL };
+/* head kernel / bf16 straight to dx0 (zero pad, one source, no upsample) / bf16 over the padded domain + fold / Winograd split store /
+ * Winograd full correlation + fold / conv_gemm*_kernel<., true> + fold */
+enum { DC_C3_DX_NONE = 0, DC_C3_DX_HEAD, DC_C3_DX_BF16, DC_C3_DX_BF16_FOLD, DC_C3_DX_WINO_SPLIT, DC_C3_DX_WINO_FOLD, DC_C3_DX_DIRECT_FOLD };
+enum { DC_C3_DW_NONE = 0, DC_C3_DW_HEAD, DC_C3_DW_BF16, DC_C3_DW_WINO, DC_C3_DW_DIRECT };                /* DIRECT: conv_wgrad*_kernel */
+/* the weight-gradient kernel's own slabs / the partials of conv_gprime_dbias_kernel / conv_dbias_kernel */
+enum { DC_C3_DB_NONE = 0, DC_C3_DB_SLABS, DC_C3_DB_GPRIME, DC_C3_DB_KERNEL };
+typedef struct dc_conv3x3_plan {
+    int32_t fwd;               /* DC_C3_FWD_* */
+    int32_t fwd_v2, fwd_mr;    /* DC_C3_FWD_DIRECT: conv_gemm_v2_kernel (1) or conv_gemm_kernel (0) <fwd_mr, false>; 0 otherwise */
+    int32_t gprime;            /* DC_C3_GP_* */
+    int32_t dx;                /* DC_C3_DX_* */
+    int32_t ring;              /* DC_C3_DX_WINO_SPLIT under ReflectionPad: conv_ring_strips_kernel + conv_ring_kernel follow */
+    int32_t dw, db;            /* DC_C3_DW_*, DC_C3_DB_* */
+    int32_t bwd_v2;            /* the backward's direct kernels are the v2 ones (full 16-wide tiles, concat on a 16-channel chunk) */
+    int32_t dx_mr, dw_mr;      /* DC_C3_DX_DIRECT_FOLD: <dx_mr, true>; DC_C3_DW_DIRECT: conv_wgrad*_kernel<dw_mr>; 0 otherwise */
+    int32_t split;             /* weight-gradient slabs of DC_C3_DW_DIRECT / DC_C3_DW_BF16 (the head and Winograd kernels choose their own: 0) */
+} dc_conv3x3_plan;
+int dc_conv3x3_plan_query(int C0, int up0, int C1, int B, int Co, int H, int W, int act, int pad_mode, int want, dc_conv3x3_plan* plan);
 
 /* ------------------------------------------------------------------ a1 BatchNorm + residual + ReLU */
 /* Training-mode nn.BatchNorm2d fused with the residual add and ReLU of torchvision's BasicBlock / Bottleneck

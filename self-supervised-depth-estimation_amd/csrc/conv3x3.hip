@@ -1187,70 +1187,248 @@ static inline bool bf16_path(int C0, int C1, int up0, int H, int W) {
     return matrix_precision() == DC_PREC_BF16 && c3b_eligible(C0, C1, up0, H, W, 1);
 }
 
+// ---- one fused block on the host: its shape, what is refused, the backward's workspace layout, the plan ------------------------------
+// bwd_layout() is behind dc_conv3x3_bwd_workspace AND the pointers of dc_conv3x3_bwd_add, conv_plan() behind both launches AND
+// dc_conv3x3_plan_query, so a query and its launch cannot disagree (a scratch region the launch assumes and the query left out is an
+// out-of-bounds write).
+struct Block { int B, C0, up0, C1, Co, H, W, Cin; };      // up0 is 0 / 1 here, whatever the caller passed
+static inline Block block(int B, int C0, int up0, int C1, int Co, int H, int W) { return {B, C0, up0 ? 1 : 0, C1, Co, H, W, C0 + C1}; }
+// what both launches and the plan query accept, whatever the pointers are
+static bool block_ok(const Block& s, int act, int pad) {
+    return s.C0 > 0 && s.C1 >= 0 && s.B > 0 && s.Co > 0 && s.H >= 2 && s.W >= 2 && !(s.up0 && ((s.H | s.W) & 1)) && act >= 0 &&
+           act <= ACT_LAST && pad >= 0 && pad <= 1;
+}
+
+// Byte offsets into the backward's workspace.  A function of the shape alone -- the query knows neither act, the pad mode nor which
+// gradients will be asked for: the Winograd scratch is there whenever the shape can take a Winograd gradient under SOME activation
+// (wino_dx / wino_dw with ACT_NONE), while conv_plan() routes with the launch's own act.
+struct BwdLayout {
+    size_t wd;                      // prepared weights: fp32 [9][Co][Cin] with flipped taps, or the bf16 kernels' packing
+    size_t dxpad;                   // data gradient over the padded domain; else the ring's strips / the head's weight-gradient slabs
+    size_t part, pbias, gp;         // weight and bias slabs of the direct and the bf16 weight gradient; g' (B,Co,H,W)
+    size_t wino_dx, wino_dw, pb2;   // Winograd data / weight gradient scratch, conv_dbias_kernel's partials behind the latter
+    size_t pbd, total;              // conv_gprime_dbias_kernel's partials; the end
+    size_t dxpad_bytes() const { return part - dxpad; }
+};
+static BwdLayout bwd_layout(const Block& s) {
+    const size_t nW = (size_t)s.Co * s.Cin * 9;
+    const int split = std::max(pick_split(s.B, s.H, s.W, s.Co, s.Cin), c3b_wgrad_split(s.B, s.H, s.W, s.Co, s.Cin, 1));
+    const bool wdx = wino_dx(s.C0, s.C1, s.B, s.Co, s.H, s.W, ACT_NONE), wdw = wino_dw(s.C0, s.C1, s.B, s.Co, s.H, s.W, ACT_NONE);
+    BwdLayout L;
+    size_t o = 0;
+    L.wd = o;      o += std::max(al256(nW * 4), c3b_weights_bytes(s.Cin, s.Co));
+    L.dxpad = o;   o += al256((size_t)s.B * s.Cin * (s.H + 2) * (s.W + 5) * 4);
+    L.part = o;    o += al256((size_t)split * nW * 4);
+    L.pbias = o;   o += al256((size_t)std::max(split, DB_SPLIT) * s.Co * 4);
+    L.gp = o;      o += al256((size_t)s.B * s.Co * s.H * s.W * 4);
+    L.wino_dx = o; o += wdx ? al256(wino_conv_ws_bytes(s.B, s.Cin, s.Co, s.H, s.W)) : 0;
+    L.wino_dw = o; o += wdw ? al256(wino_wgrad_ws_bytes(s.B, s.Cin, s.Co, s.H, s.W)) : 0;
+    L.pb2 = o;     o += wdw ? al256((size_t)DB_SPLIT * s.Co * 4) : 0;
+    L.pbd = o;     o += al256((size_t)256 * s.Co * 4);
+    L.total = o;
+    return L;
+}
+
+// Which kernels the two launches run.  `want`: DC_C3_WANT_* of the results the backward is asked for (0: the forward alone).  Reads the
+// calling thread's matrix precision, dc_set_dgrad_split's mode and the DC_* environment statics.
+static void conv_plan(const Block& s, int act, int pad, unsigned want, dc_conv3x3_plan* p) {
+    const int B = s.B, C0 = s.C0, up0 = s.up0, C1 = s.C1, Co = s.Co, H = s.H, W = s.W, Cin = s.Cin;
+    const bool dx0 = want & DC_C3_WANT_DX0, dx_any = want & (DC_C3_WANT_DX0 | DC_C3_WANT_DX1);
+    const bool dweight = want & DC_C3_WANT_DWEIGHT, dbias = want & DC_C3_WANT_DBIAS, dw_any = dweight || dbias;
+    *p = dc_conv3x3_plan{};
+    // ---- forward: the single-channel heads (plain FMAs, dispconv.hip) first, then the reduced-precision policy (bf16 matrix cores,
+    // conv_bf16.hip), then the fused Winograd F(2x2,3x3) on even widths (wino.hip), else the direct implicit GEMM of this file
+    const bool head = wino_enabled() && dispconv_eligible(C0, C1, up0, Co, H, W);
+    const bool b16_shape = bf16_path(C0, C1, up0, H, W);
+    p->fwd = head ? DC_C3_FWD_HEAD : b16_shape ? DC_C3_FWD_BF16 : wino_fwd(C0, C1, B, Co, H, W) ? DC_C3_FWD_WINO : DC_C3_FWD_DIRECT;
+    if (p->fwd == DC_C3_FWD_DIRECT) { p->fwd_v2 = (W % 16 == 0) && (C1 == 0 || C0 % CK == 0); p->fwd_mr = pick_mr(Co); }
+    // ---- backward: the head checks again before the bf16 and Winograd ones
+    const bool b16 = b16_shape && wino_gp_ok(B, Co, H, W, act);
+    // (the bf16 weight-gradient kernel tiles 64 output channels; a quarter- or half-filled tile still beats the fp32 direct
+    // kernel on the thin 16 / 32-channel levels -- 879 -> 328 us for 96 -> 32 at 96 x 320, B = 36 -- DC_B16_DW_MIN restores 64 for A/Bs;
+    // below it the weight gradient takes the direct fp32 kernel, fed by conv_gprime_kernel, not Winograd)
+    static const int b16_dw_min = std::getenv("DC_B16_DW_MIN") ? atoi(std::getenv("DC_B16_DW_MIN")) : 16;
+    const bool b16_dw = b16 && Co >= b16_dw_min;
+    const bool w_dx = !b16 && dx_any && wino_dx(C0, C1, B, Co, H, W, act);
+    const bool w_dw = !b16 && dweight && wino_dw(C0, C1, B, Co, H, W, act);
+    // bias gradient from the same pass that forms g' (whole float4s per channel plane)
+    const bool fused_db = dbias && (w_dw || b16_dw) && (H * W) % 4 == 0;
+    // fast path (v2 kernels): full 16-wide tiles, 16-byte aligned rows, chunks that do not straddle the concat -- CK channels in the
+    // data gradient as in the forward, CW in the weight gradient: one clause more than the forward's
+    const bool fast = (W % 16 == 0) && (C1 == 0 || C0 % CK == 0) && (C1 == 0 || C0 % CW == 0);
+    // the thin single-channel heads have their own plain-FMA gradients (dispconv.hip), which form g' on the fly; the weight
+    // gradient's slabs borrow the padded-domain buffer
+    const bool head_dx = dx0 && head;
+    const bool head_dw = dw_any && wino_enabled() && dispconv_wgrad_eligible(C0, C1, up0, Co, H, W) &&
+                         dispconv_wgrad_scratch(B, C0, H, W) <= bwd_layout(s).dxpad_bytes();
+    const bool gp_unused = (head_dx || !dx_any) && (head_dw || !dw_any);
+    p->bwd_v2 = fast;
+    if (gp_unused) p->gprime = DC_C3_GP_UNUSED;
+    else if (fused_db) p->gprime = DC_C3_GP_DBIAS_KERNEL;
+    else if ((fast || w_dx || w_dw || b16) && act != ACT_NONE && ((size_t)B * Co * H * W) % 4 == 0) p->gprime = DC_C3_GP_KERNEL;
+    else p->gprime = act != ACT_NONE ? DC_C3_GP_ON_THE_FLY : DC_C3_GP_GY;
+    // Winograd without the padded-domain scratch: dc_set_dgrad_split; the ring only where it pays (the comment on g_dgrad_split_min_pixels)
+    const bool split_store = !head_dx && w_dx && g_dgrad_split && wino_dgrad_split_ok(B, C0, C1, up0, Co, H, W) &&
+                             (pad == PAD_ZERO || (Co <= RING_MAXCO && (g_dgrad_split == 2 || (H * W >= g_dgrad_split_min_pixels &&
+                                                                                            (size_t)B * Cin * H * W >= ((size_t)4 << 20)))));
+    // (bf16: a zero-padded single-source block gets its data gradient directly; reflection / upsample / concat go through the padded domain)
+    p->dx = head_dx ? DC_C3_DX_HEAD : (b16 && dx_any) ? ((pad == PAD_ZERO && !up0 && C1 == 0) ? DC_C3_DX_BF16 : DC_C3_DX_BF16_FOLD)
+            : split_store ? DC_C3_DX_WINO_SPLIT : w_dx ? DC_C3_DX_WINO_FOLD : dx_any ? DC_C3_DX_DIRECT_FOLD : DC_C3_DX_NONE;
+    p->ring = p->dx == DC_C3_DX_WINO_SPLIT && pad == PAD_REFLECT;
+    if (p->dx == DC_C3_DX_DIRECT_FOLD) p->dx_mr = pick_mr(Cin);
+    const int db_slabs = dbias ? DC_C3_DB_SLABS : DC_C3_DB_NONE;       // (the direct kernel runs for them with dweight == nullptr too)
+    const int db_gp = !dbias ? DC_C3_DB_NONE : fused_db ? DC_C3_DB_GPRIME : DC_C3_DB_KERNEL;
+    if (head_dw) { p->dw = DC_C3_DW_HEAD; p->db = db_slabs; }
+    else if (b16_dw && dw_any) { p->dw = dweight ? DC_C3_DW_BF16 : DC_C3_DW_NONE; p->db = db_gp; p->split = dweight ? c3b_wgrad_split(B, H, W, Co, Cin, 1) : 0; }
+    else if (w_dw) { p->dw = DC_C3_DW_WINO; p->db = db_gp; }
+    else if (dw_any) { p->dw = DC_C3_DW_DIRECT; p->db = db_slabs; p->dw_mr = pick_mr_w(Co); p->split = pick_split(B, H, W, Co, Cin); }
+}
+
+// ---- the launches of the plan -------------------------------------------------------------------------------------------------------
+// conv_gemm_kernel / conv_gemm_v2_kernel<mr, DGRAD> over M output rows (forward: Co; data gradient: Cin, over the padded domain)
+template <bool DGRAD>
+static int launch_gemm(const ConvArgs& a, int M, int mr, bool v2, hipStream_t st) {
+    void (*const k)(ConvArgs) = mr == 4   ? (v2 ? conv_gemm_v2_kernel<4, DGRAD> : conv_gemm_kernel<4, DGRAD>)
+                                : mr == 2 ? (v2 ? conv_gemm_v2_kernel<2, DGRAD> : conv_gemm_kernel<2, DGRAD>)
+                                          : (v2 ? conv_gemm_v2_kernel<1, DGRAD> : conv_gemm_kernel<1, DGRAD>);
+    hipLaunchKernelGGL(k, dim3(a.tiles_x * a.tiles_y, ceil_div(M, 16 * mr), a.B), dim3(256), 0, st, a);
+    DC_CHECK_LAUNCH();
+    return DC_OK;
+}
+
+// one dc_conv3x3_bwd_add: the block, its plan, its operands, its workspace regions (BwdLayout) and the steps the plan chooses from
+struct BwdCall : Block {
+    int act, pad; dc_conv3x3_plan p;
+    const float *x0, *x1, *weight, *y, *gy, *add0, *add1;
+    float *dx0, *dx1, *dweight, *dbias, *wd, *dxpad, *part, *pbias, *gpbuf, *pb2, *pbd;
+    void *wws, *gws;
+    const float* gp;        // g' as the gradient kernels read it: gy until a g' kernel has filled gpbuf
+    hipStream_t st;
+
+    // g' into gpbuf by conv_gprime_kernel, or by conv_gprime_dbias_kernel together with the bias gradient's partials (without an
+    // activation that launch is there for the partials alone, and gp stays gy)
+    int form_gprime(bool with_dbias) {
+        const size_t n4 = (size_t)B * Co * H * W / 4;
+        if (with_dbias)
+            hipLaunchKernelGGL(conv_gprime_dbias_kernel, dim3(Co, gpd_split(Co)), dim3(256), 0, st, gy, y, gpbuf, pbd, B, Co, H * W / 4, act,
+                               gpd_split(Co));
+        else
+            hipLaunchKernelGGL(conv_gprime_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 4096)), dim3(256), 0, st, gy, y, gpbuf, n4, act);
+        DC_CHECK_LAUNCH();
+        if (act != ACT_NONE) gp = gpbuf;
+        return DC_OK;
+    }
+    int fold(int pitch) const { return conv_fold(dxpad, dx0, dx1, B, C0, C1, up0, H, W, pad, pitch, add0, add1, st); }
+    // bf16 matrix cores: convolution of g' with the rotated, transposed filter, straight into dx0 or over the padded domain + fold
+    int dx_bf16(bool padded) const {
+        const int rc = c3b_conv(gp, Co, 0, nullptr, 0, weight, Co, Cin, 1, padded, nullptr, padded ? dxpad : dx0, wd, B, H, W, ACT_NONE, PAD_ZERO,
+                                1, st, padded ? nullptr : add0);
+        return rc != DC_OK || !padded ? rc : fold(c3b_dpad_pitch(W));
+    }
+    // the interior of the correlation written straight to dx0 / dx1 (concat split, 2 x 2 sums of the upsampled half and the addends in
+    // the Winograd kernel's store epilogue), then the few ring terms ReflectionPad folds back: no padded-domain scratch (B x Cin x (H+2)
+    // x (W+2) written and read again) and no fold pass
+    int dx_wino_split() const {
+        const int rc = wino_conv_dgrad_split(gp, weight, dx0, dx1, add0, add1, wws, B, C0, C1, up0, Co, H, W, st);
+        if (rc != DC_OK || !p.ring) return rc;
+        // (scratch: the padded-domain buffer, which this path does not use -- 4 strips of max(H, W) + 2 floats per plane)
+        const int LP = std::max(H, W) + 2;
+        const int segs = ceil_div(LP, RING_SEG), nchunk = ceil_div(Cin, RING_CB);
+        const int cgroups = std::max(1, std::min(nchunk, ceil_div(512, segs * 4 * B)));       // ~two blocks per CU
+        hipLaunchKernelGGL(conv_ring_strips_kernel, dim3(segs, 4 * cgroups, B), dim3(256),
+                           (size_t)(Co * (RING_SEG + 4) + Co * RING_CB * 3) * sizeof(float), st, gp, weight, dxpad, Cin, Co, H, W, LP, cgroups);
+        DC_CHECK_LAUNCH();
+        hipLaunchKernelGGL(conv_ring_kernel, dim3(ceil_div(2 * W + 2 * H, 256), Cin, B), dim3(256), 0, st, (const float*)dxpad, dx0, dx1, C0, C1,
+                           up0, H, W, LP);
+        DC_CHECK_LAUNCH();
+        return DC_OK;
+    }
+    // full correlation of g' with the rotated weights in the Winograd domain, then the same fold as behind the direct kernel
+    int dx_wino_fold() const {
+        const int rc = wino_conv_full_dgrad(gp, weight, dxpad, wws, B, Cin, Co, H, W, st);
+        return rc != DC_OK ? rc : fold(W + 2);
+    }
+    int dx_direct_fold() const {
+        hipLaunchKernelGGL(conv_wprep_kernel, dim3(ceil_div(Co * Cin * 9, 256)), dim3(256), 0, st, weight, (float*)nullptr, wd, Co, Cin);
+        DC_CHECK_LAUNCH();
+        ConvArgs a{};
+        a.C0 = C0; a.C1 = C1; a.up0 = up0; a.wt = wd; a.y = y; a.gy = gy; a.gp = gp; a.out = dxpad;
+        a.B = B; a.Co = Co; a.H = H; a.W = W; a.act = act; a.pad = pad;
+        a.tiles_x = ceil_div(W + 2, CT); a.tiles_y = ceil_div(H + 2, CT);
+        const int rc = launch_gemm<true>(a, Cin, p.dx_mr, p.bwd_v2, st);
+        return rc != DC_OK ? rc : fold(W + 2);
+    }
+    int dw_bf16() const {
+        const int rc = c3b_wgrad(x0, C0, up0, x1, C1, gp, part, p.split, B, Co, H, W, pad, 1, st);
+        return rc != DC_OK ? rc : conv_wreduce(part, nullptr, dweight, nullptr, p.split, Co * Cin * 9, 0, st);
+    }
+    // conv_wgrad_kernel / conv_wgrad_v2_kernel<mr>: split-K slabs of the weight AND the bias gradient, then one reduction of both
+    // (either output may be null)
+    int dw_direct() const {
+        WgradArgs g{};
+        g.x0 = x0; g.C0 = C0; g.up0 = up0; g.x1 = x1; g.C1 = C1; g.y = y; g.gy = gy; g.gp = gp; g.part = part; g.pbias = pbias;
+        g.B = B; g.Co = Co; g.H = H; g.W = W; g.act = act; g.pad = pad;
+        g.tiles_x = ceil_div(W, CT); g.tiles_y = ceil_div(H, CT); g.split = p.split;
+        void (*const k)(WgradArgs) = p.dw_mr == 2 ? (p.bwd_v2 ? conv_wgrad_v2_kernel<2> : conv_wgrad_kernel<2>)
+                                                  : (p.bwd_v2 ? conv_wgrad_v2_kernel<1> : conv_wgrad_kernel<1>);
+        hipLaunchKernelGGL(k, dim3(p.split, ceil_div(Co, 16 * p.dw_mr), ceil_div(Cin, CW)), dim3(256), 0, st, g);
+        DC_CHECK_LAUNCH();
+        return conv_wreduce(part, pbias, dweight, dbias, p.split, Co * Cin * 9, Co, st);
+    }
+    // bias gradient from g': DB_SPLIT partial sums per channel, then their reduction in order
+    int db_kernel(float* partials) const {
+        hipLaunchKernelGGL(conv_dbias_kernel, dim3(Co, DB_SPLIT), dim3(256), 0, st, gp, partials, B, Co, H * W);
+        DC_CHECK_LAUNCH();
+        return conv_wreduce(nullptr, partials, nullptr, dbias, DB_SPLIT, 0, Co, st);
+    }
+};
+
 }  // namespace dc
 
 using namespace dc;
 #define ST ((hipStream_t)stream)
 
+// (This query alone also answers for C0 == 0 with C1 > 0, which the launches and the other two queries refuse.)
 extern "C" size_t dc_conv3x3_fwd_workspace(int C0, int C1, int B, int Co, int H, int W) {
     if (C0 < 0 || C1 < 0 || C0 + C1 <= 0 || Co <= 0 || B <= 0 || H <= 0 || W <= 0) return 0;
     const size_t direct = std::max(al256((size_t)9 * (C0 + C1) * Co * sizeof(float)), c3b_weights_bytes(C0 + C1, Co));
     return wino_fwd(C0, C1, B, Co, H, W) ? std::max(direct, wino_conv_ws_bytes(B, C0 + C1, Co, H, W)) : direct;
 }
 
-extern "C" int dc_conv3x3_fwd(const float* x0, int C0, int up0, const float* x1, int C1, const float* weight,
-                              const float* bias, float* y, void* ws, int B, int Co, int H, int W, int act,
-                              int pad_mode, void* stream) {
-    if (!x0 || C0 <= 0 || (C1 > 0 && !x1) || C1 < 0 || !weight || !y || !ws || B <= 0 || Co <= 0 || H < 2 || W < 2)
-        return DC_EINVAL;
-    if (up0 && ((H | W) & 1)) return DC_EINVAL;
-    if (act < 0 || act > ACT_LAST || pad_mode < 0 || pad_mode > 1) return DC_EINVAL;
-    const int Cin = C0 + C1;
-    // single-channel heads: plain-FMA kernels (dispconv.hip)
-    if (wino_enabled() && dispconv_eligible(C0, C1, up0 ? 1 : 0, Co, H, W))
-        return dispconv_fwd(x0, weight, bias, y, B, C0, H, W, act, pad_mode, ST);
-    // reduced-precision policy: direct implicit GEMM on the bf16 matrix cores (conv_bf16.hip)
-    if (bf16_path(C0, C1, up0 ? 1 : 0, H, W))
-        return c3b_conv(x0, C0, up0 ? 1 : 0, x1, C1, weight, Co, Cin, 0, 0, bias, y, ws, B, H, W, act, pad_mode, 1, ST);
-    // even widths: fused Winograd F(2x2,3x3) (wino.hip); otherwise the direct implicit GEMM below
-    if (wino_fwd(C0, C1, B, Co, H, W))
-        return wino_conv_fused_fwd(x0, C0, up0 ? 1 : 0, x1, C1, weight, bias, y, ws, B, Co, H, W, act, pad_mode, ST);
-    float* wf = (float*)ws;
-    hipLaunchKernelGGL(conv_wprep_kernel, dim3(ceil_div(Co * Cin * 9, 256)), dim3(256), 0, ST, weight, wf,
-                       (float*)nullptr, Co, Cin);
-    DC_CHECK_LAUNCH();
-    ConvArgs a{};
-    a.x0 = x0; a.C0 = C0; a.up0 = up0 ? 1 : 0; a.x1 = x1; a.C1 = C1; a.wt = wf; a.bias = bias; a.out = y;
-    a.B = B; a.Co = Co; a.H = H; a.W = W; a.act = act; a.pad = pad_mode;
-    a.tiles_x = ceil_div(W, CT); a.tiles_y = ceil_div(H, CT);
-    const int mr = pick_mr(Co);
-    const dim3 grid(a.tiles_x * a.tiles_y, ceil_div(Co, 16 * mr), B);
-    const bool fast = (W % 16 == 0) && (C1 == 0 || C0 % CK == 0);
-    if (fast) {
-        if (mr == 4) hipLaunchKernelGGL((conv_gemm_v2_kernel<4, false>), grid, dim3(256), 0, ST, a);
-        else if (mr == 2) hipLaunchKernelGGL((conv_gemm_v2_kernel<2, false>), grid, dim3(256), 0, ST, a);
-        else hipLaunchKernelGGL((conv_gemm_v2_kernel<1, false>), grid, dim3(256), 0, ST, a);
-    } else {
-        if (mr == 4) hipLaunchKernelGGL((conv_gemm_kernel<4, false>), grid, dim3(256), 0, ST, a);
-        else if (mr == 2) hipLaunchKernelGGL((conv_gemm_kernel<2, false>), grid, dim3(256), 0, ST, a);
-        else hipLaunchKernelGGL((conv_gemm_kernel<1, false>), grid, dim3(256), 0, ST, a);
-    }
-    DC_CHECK_LAUNCH();
+extern "C" size_t dc_conv3x3_bwd_workspace(int C0, int C1, int B, int Co, int H, int W) {
+    if (C0 <= 0 || C1 < 0 || B <= 0 || Co <= 0 || H <= 0 || W <= 0) return 0;
+    return bwd_layout(block(B, C0, 0, C1, Co, H, W)).total;
+}
+
+extern "C" int dc_conv3x3_plan_query(int C0, int up0, int C1, int B, int Co, int H, int W, int act, int pad_mode, int want,
+                                     dc_conv3x3_plan* plan) {
+    const Block s = block(B, C0, up0, C1, Co, H, W);
+    if (!plan || !block_ok(s, act, pad_mode)) return DC_EINVAL;
+    conv_plan(s, act, pad_mode, (unsigned)want, plan);
     return DC_OK;
 }
 
-extern "C" size_t dc_conv3x3_bwd_workspace(int C0, int C1, int B, int Co, int H, int W) {
-    if (C0 <= 0 || C1 < 0 || B <= 0 || Co <= 0 || H <= 0 || W <= 0) return 0;
-    const int Cin = C0 + C1;
-    const size_t nW = (size_t)Co * Cin * 9;
-    const int split = std::max(pick_split(B, H, W, Co, Cin), c3b_wgrad_split(B, H, W, Co, Cin, 1));
-    const size_t direct = std::max(al256(nW * 4), c3b_weights_bytes(Cin, Co)) + al256((size_t)B * Cin * (H + 2) * (W + 5) * 4) +
-                          al256((size_t)split * nW * 4) + al256((size_t)std::max(split, DB_SPLIT) * Co * 4) + al256((size_t)B * Co * H * W * 4);
-    // the Winograd passes keep their scratch behind the direct layout (dxpad and g' are shared)
-    size_t extra = 0;
-    if (wino_dx(C0, C1, B, Co, H, W, ACT_NONE)) extra += al256(wino_conv_ws_bytes(B, Cin, Co, H, W));
-    if (wino_dw(C0, C1, B, Co, H, W, ACT_NONE)) extra += al256(wino_wgrad_ws_bytes(B, Cin, Co, H, W)) + al256((size_t)DB_SPLIT * Co * 4);
-    return direct + extra + al256((size_t)256 * Co * 4);        // + the bias-gradient partials of conv_gprime_dbias_kernel
+extern "C" int dc_conv3x3_fwd(const float* x0, int C0, int up0, const float* x1, int C1, const float* weight,
+                              const float* bias, float* y, void* ws, int B, int Co, int H, int W, int act,
+                              int pad_mode, void* stream) {
+    const Block s = block(B, C0, up0, C1, Co, H, W);
+    if (!block_ok(s, act, pad_mode) || !x0 || (C1 > 0 && !x1) || !weight || !y || !ws) return DC_EINVAL;
+    dc_conv3x3_plan p;
+    conv_plan(s, act, pad_mode, 0, &p);
+    switch (p.fwd) {
+    case DC_C3_FWD_HEAD: return dispconv_fwd(x0, weight, bias, y, B, C0, H, W, act, pad_mode, ST);
+    case DC_C3_FWD_BF16: return c3b_conv(x0, C0, s.up0, x1, C1, weight, Co, s.Cin, 0, 0, bias, y, ws, B, H, W, act, pad_mode, 1, ST);
+    case DC_C3_FWD_WINO: return wino_conv_fused_fwd(x0, C0, s.up0, x1, C1, weight, bias, y, ws, B, Co, H, W, act, pad_mode, ST);
+    default: break;
+    }
+    float* wf = (float*)ws;
+    hipLaunchKernelGGL(conv_wprep_kernel, dim3(ceil_div(Co * s.Cin * 9, 256)), dim3(256), 0, ST, weight, wf, (float*)nullptr, Co, s.Cin);
+    DC_CHECK_LAUNCH();
+    ConvArgs a{};
+    a.x0 = x0; a.C0 = C0; a.up0 = s.up0; a.x1 = x1; a.C1 = C1; a.wt = wf; a.bias = bias; a.out = y;
+    a.B = B; a.Co = Co; a.H = H; a.W = W; a.act = act; a.pad = pad_mode;
+    a.tiles_x = ceil_div(W, CT); a.tiles_y = ceil_div(H, CT);
+    return launch_gemm<false>(a, Co, p.fwd_mr, p.fwd_v2, ST);
 }
 
 extern "C" int dc_conv3x3_bwd(const float* x0, int C0, int up0, const float* x1, int C1, const float* weight,
@@ -1264,181 +1442,47 @@ extern "C" int dc_conv3x3_bwd_add(const float* x0, int C0, int up0, const float*
                                   const float* y, const float* gy, float* dx0, float* dx1, const float* addend0, const float* addend1,
                                   float* dweight, float* dbias, void* ws, int B, int Co, int H, int W, int act, int pad_mode,
                                   void* stream) {
-    if ((addend0 && !dx0) || (addend1 && !dx1)) return DC_EINVAL;
-    if (!x0 || C0 <= 0 || (C1 > 0 && !x1) || C1 < 0 || !weight || !y || !gy || !ws || B <= 0 || Co <= 0 || H < 2 || W < 2)
+    const Block s = block(B, C0, up0, C1, Co, H, W);
+    if (!block_ok(s, act, pad_mode) || !x0 || (C1 > 0 && !x1) || !weight || !y || !gy || !ws || (addend0 && !dx0) || (addend1 && !dx1))
         return DC_EINVAL;
-    if (up0 && ((H | W) & 1)) return DC_EINVAL;
-    if (act < 0 || act > ACT_LAST || pad_mode < 0 || pad_mode > 1) return DC_EINVAL;
-    const int Cin = C0 + C1;
-    const size_t nW = (size_t)Co * Cin * 9;
-    const int split = pick_split(B, H, W, Co, Cin);
-    const int split_ws = std::max(split, c3b_wgrad_split(B, H, W, Co, Cin, 1));      // (the layout of dc_conv3x3_bwd_workspace)
-    char* p = (char*)ws;
-    float* wd = (float*)p; p += std::max(al256(nW * 4), c3b_weights_bytes(Cin, Co));
-    float* dxpad = (float*)p; p += al256((size_t)B * Cin * (H + 2) * (W + 5) * 4);
-    float* part = (float*)p; p += al256((size_t)split_ws * nW * 4);
-    float* pbias = (float*)p; p += al256((size_t)std::max(split_ws, DB_SPLIT) * Co * 4);
-    float* gpbuf = (float*)p; p += al256((size_t)B * Co * H * W * 4);
-    const bool b16 = bf16_path(C0, C1, up0 ? 1 : 0, H, W) && wino_gp_ok(B, Co, H, W, act);
-    // (the bf16 weight-gradient kernel tiles 64 output channels; a quarter- or half-filled tile still beats the fp32 direct
-    // kernel on the thin 16 / 32-channel levels -- 879 -> 328 us for 96 -> 32 at 96 x 320, B = 36 -- DC_B16_DW_MIN restores 64 for A/Bs)
-    static const int b16_dw_min = std::getenv("DC_B16_DW_MIN") ? atoi(std::getenv("DC_B16_DW_MIN")) : 16;
-    const bool b16_dw = b16 && Co >= b16_dw_min;
-    const bool w_dx = !b16 && (dx0 || dx1) && wino_dx(C0, C1, B, Co, H, W, act);
-    const bool w_dw = !b16 && dweight && wino_dw(C0, C1, B, Co, H, W, act);
-    // bias gradient from the same pass that forms g' (whole float4s per channel plane)
-    const bool fused_db = dbias && (w_dw || b16_dw) && (H * W) % 4 == 0;
-    void* wws = p; if (wino_dx(C0, C1, B, Co, H, W, ACT_NONE)) p += al256(wino_conv_ws_bytes(B, Cin, Co, H, W));
-    void* gws = p; if (wino_dw(C0, C1, B, Co, H, W, ACT_NONE)) p += al256(wino_wgrad_ws_bytes(B, Cin, Co, H, W));
-    float* pb2 = (float*)p; if (wino_dw(C0, C1, B, Co, H, W, ACT_NONE)) p += al256((size_t)DB_SPLIT * Co * 4);
-    float* pbd = (float*)p;
-    const int tiles_x = ceil_div(W, CT), tiles_y = ceil_div(H, CT);
-    // fast path (v2 kernels): full 16-wide tiles, 16-byte aligned rows, chunks that do not straddle the concat
-    const bool fast = (W % 16 == 0) && (C1 == 0 || C0 % CK == 0) && (C1 == 0 || C0 % CW == 0);
-    // the thin single-channel heads have their own plain-FMA gradients (dispconv.hip), which form g' on the fly
-    const bool head_dx = dx0 && wino_enabled() && dispconv_eligible(C0, C1, up0 ? 1 : 0, Co, H, W);
-    const bool head_dw = (dweight || dbias) && wino_enabled() && dispconv_wgrad_eligible(C0, C1, up0 ? 1 : 0, Co, H, W) &&
-                         dispconv_wgrad_scratch(B, C0, H, W) <= al256((size_t)B * Cin * (H + 2) * (W + 5) * 4);
-    const bool gp_unused = (head_dx || !(dx0 || dx1)) && (head_dw || !(dweight || dbias));
-    const float* gp = gy;
-    if (gp_unused) {
-    } else if (fused_db) {
-        hipLaunchKernelGGL(conv_gprime_dbias_kernel, dim3(Co, gpd_split(Co)), dim3(256), 0, ST, gy, y, gpbuf, pbd, B, Co, H * W / 4, act,
-                           gpd_split(Co));
-        DC_CHECK_LAUNCH();
-        if (act != ACT_NONE) gp = gpbuf;
-    } else if ((fast || w_dx || w_dw || b16) && act != ACT_NONE && ((size_t)B * Co * H * W) % 4 == 0) {
-        const size_t n4 = (size_t)B * Co * H * W / 4;
-        hipLaunchKernelGGL(conv_gprime_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 4096)), dim3(256), 0, ST, gy, y,
-                           gpbuf, n4, act);
-        DC_CHECK_LAUNCH();
-        gp = gpbuf;
+    const BwdLayout L = bwd_layout(s);
+    const auto at = [ws](size_t off) { return (float*)((char*)ws + off); };
+    BwdCall c{s, act, pad_mode, {}, x0, x1, weight, y, gy, addend0, addend1, dx0, dx1, dweight, dbias, at(L.wd), at(L.dxpad), at(L.part),
+              at(L.pbias), at(L.gp), at(L.pb2), at(L.pbd), at(L.wino_dx), at(L.wino_dw), gy, ST};
+    conv_plan(s, act, pad_mode, (dx0 ? DC_C3_WANT_DX0 : 0) | (dx1 ? DC_C3_WANT_DX1 : 0) | (dweight ? DC_C3_WANT_DWEIGHT : 0) |
+                                    (dbias ? DC_C3_WANT_DBIAS : 0), &c.p);
+    int rc = DC_OK;
+    switch (c.p.gprime) {
+    case DC_C3_GP_DBIAS_KERNEL: rc = c.form_gprime(true); break;
+    case DC_C3_GP_KERNEL: rc = c.form_gprime(false); break;
+    default: break;       // nobody reads it, or c.gp stays gy: no activation, or the consuming kernel applies act'(y) itself
     }
-    if (head_dx) {
-        // thin single-channel head: folded-window data gradient, no padded scratch / fold pass (dispconv.hip)
-        const int rc = dispconv_dx(weight, y, gy, dx0, addend0, B, C0, H, W, act, pad_mode, ST);
-        if (rc != DC_OK) return rc;
-    } else if (b16 && (dx0 || dx1)) {
-        // bf16 matrix cores: a zero-padded single-source block gets its data gradient directly (convolution of g' with the
-        // rotated, transposed filter); reflection / upsample / concat go through the padded domain and the fold below
-        if (pad_mode == PAD_ZERO && !up0 && C1 == 0) {
-            const int rc = c3b_conv(gp, Co, 0, nullptr, 0, weight, Co, Cin, 1, 0, nullptr, dx0, wd, B, H, W, ACT_NONE, PAD_ZERO, 1, ST, addend0);
-            if (rc != DC_OK) return rc;
-        } else {
-            const int rc = c3b_conv(gp, Co, 0, nullptr, 0, weight, Co, Cin, 1, 1, nullptr, dxpad, wd, B, H, W, ACT_NONE, PAD_ZERO, 1, ST);
-            if (rc != DC_OK) return rc;
-            const int rcf = conv_fold(dxpad, dx0, dx1, B, C0, C1, up0 ? 1 : 0, H, W, pad_mode, c3b_dpad_pitch(W), addend0, addend1, ST);
-            if (rcf != DC_OK) return rcf;
-        }
-    } else if (w_dx && g_dgrad_split && wino_dgrad_split_ok(B, C0, C1, up0 ? 1 : 0, Co, H, W) &&
-               (pad_mode == PAD_ZERO || (Co <= RING_MAXCO && (g_dgrad_split == 2 || (H * W >= g_dgrad_split_min_pixels &&
-                                                                                  (size_t)B * Cin * H * W >= ((size_t)4 << 20)))))) {
-        // the interior of the correlation written straight to dx0 / dx1 (concat split, 2 x 2 sums of the upsampled half and the
-        // addends in the Winograd kernel's store epilogue), then the few ring terms ReflectionPad folds back: no padded-domain
-        // scratch (B x Cin x (H+2) x (W+2) written and read again) and no fold pass
-        const int rc = wino_conv_dgrad_split(gp, weight, dx0, dx1, addend0, addend1, wws, B, C0, C1, up0 ? 1 : 0, Co, H, W, ST);
-        if (rc != DC_OK) return rc;
-        if (pad_mode == PAD_REFLECT) {
-            // (scratch: the padded-domain buffer, which this path does not use -- 4 strips of max(H, W) + 2 floats per plane)
-            const int LP = std::max(H, W) + 2;
-            const int segs = ceil_div(LP, RING_SEG), nchunk = ceil_div(Cin, RING_CB);
-            const int cgroups = std::max(1, std::min(nchunk, ceil_div(512, segs * 4 * B)));       // ~two blocks per CU
-            hipLaunchKernelGGL(conv_ring_strips_kernel, dim3(segs, 4 * cgroups, B), dim3(256),
-                               (size_t)(Co * (RING_SEG + 4) + Co * RING_CB * 3) * sizeof(float), ST, gp, weight, dxpad, Cin, Co, H, W, LP, cgroups);
-            DC_CHECK_LAUNCH();
-            hipLaunchKernelGGL(conv_ring_kernel, dim3(ceil_div(2 * W + 2 * H, 256), Cin, B), dim3(256), 0, ST, (const float*)dxpad, dx0, dx1,
-                               C0, C1, up0 ? 1 : 0, H, W, LP);
-            DC_CHECK_LAUNCH();
-        }
-    } else if (w_dx) {
-        // full correlation of g' with the rotated weights in the Winograd domain, then the same fold as below
-        const int rc = wino_conv_full_dgrad(gp, weight, dxpad, wws, B, Cin, Co, H, W, ST);
-        if (rc != DC_OK) return rc;
-        const int rcf = conv_fold(dxpad, dx0, dx1, B, C0, C1, up0 ? 1 : 0, H, W, pad_mode, W + 2, addend0, addend1, ST);
-        if (rcf != DC_OK) return rcf;
-    } else if (dx0 || dx1) {
-        hipLaunchKernelGGL(conv_wprep_kernel, dim3(ceil_div((int)nW, 256)), dim3(256), 0, ST, weight, (float*)nullptr, wd,
-                           Co, Cin);
-        DC_CHECK_LAUNCH();
-        ConvArgs a{};
-        a.C0 = C0; a.C1 = C1; a.up0 = up0 ? 1 : 0; a.wt = wd; a.y = y; a.gy = gy; a.gp = gp; a.out = dxpad;
-        a.B = B; a.Co = Co; a.H = H; a.W = W; a.act = act; a.pad = pad_mode;
-        a.tiles_x = ceil_div(W + 2, CT); a.tiles_y = ceil_div(H + 2, CT);
-        const int mr = pick_mr(Cin);
-        const dim3 grid(a.tiles_x * a.tiles_y, ceil_div(Cin, 16 * mr), B);
-        if (fast) {
-            if (mr == 4) hipLaunchKernelGGL((conv_gemm_v2_kernel<4, true>), grid, dim3(256), 0, ST, a);
-            else if (mr == 2) hipLaunchKernelGGL((conv_gemm_v2_kernel<2, true>), grid, dim3(256), 0, ST, a);
-            else hipLaunchKernelGGL((conv_gemm_v2_kernel<1, true>), grid, dim3(256), 0, ST, a);
-        } else {
-            if (mr == 4) hipLaunchKernelGGL((conv_gemm_kernel<4, true>), grid, dim3(256), 0, ST, a);
-            else if (mr == 2) hipLaunchKernelGGL((conv_gemm_kernel<2, true>), grid, dim3(256), 0, ST, a);
-            else hipLaunchKernelGGL((conv_gemm_kernel<1, true>), grid, dim3(256), 0, ST, a);
-        }
-        DC_CHECK_LAUNCH();
-        const int rcf = conv_fold(dxpad, dx0, dx1, B, C0, C1, up0 ? 1 : 0, H, W, pad_mode, W + 2, addend0, addend1, ST);
-        if (rcf != DC_OK) return rcf;
+    if (rc != DC_OK) return rc;
+    switch (c.p.dx) {
+    case DC_C3_DX_HEAD: rc = dispconv_dx(weight, y, gy, dx0, addend0, B, C0, H, W, act, pad_mode, ST); break;
+    case DC_C3_DX_BF16: rc = c.dx_bf16(false); break;
+    case DC_C3_DX_BF16_FOLD: rc = c.dx_bf16(true); break;
+    case DC_C3_DX_WINO_SPLIT: rc = c.dx_wino_split(); break;
+    case DC_C3_DX_WINO_FOLD: rc = c.dx_wino_fold(); break;
+    case DC_C3_DX_DIRECT_FOLD: rc = c.dx_direct_fold(); break;
+    default: break;
     }
-    if (head_dw) {
-        // (scratch: the padded-domain buffer -- the head's data gradient does not use it, and any other data-gradient path has
-        // finished with it in stream order)
-        const int rc = dispconv_wgrad(x0, y, gy, dweight, dbias, dxpad, B, C0, H, W, act, pad_mode, ST);
-        if (rc != DC_OK) return rc;
-    } else if (b16_dw && (dweight || dbias)) {
-        if (dweight) {
-            const int sp = c3b_wgrad_split(B, H, W, Co, Cin, 1);
-            int rc = c3b_wgrad(x0, C0, up0 ? 1 : 0, x1, C1, gp, part, sp, B, Co, H, W, pad_mode, 1, ST);
-            if (rc != DC_OK) return rc;
-            rc = conv_wreduce(part, nullptr, dweight, nullptr, sp, (int)nW, 0, ST);
-            if (rc != DC_OK) return rc;
-        }
-        if (dbias && fused_db) {
-            const int rc = conv_wreduce(nullptr, pbd, nullptr, dbias, gpd_split(Co), 0, Co, ST);
-            if (rc != DC_OK) return rc;
-        } else if (dbias) {
-            hipLaunchKernelGGL(conv_dbias_kernel, dim3(Co, DB_SPLIT), dim3(256), 0, ST, gp, pbias, B, Co, H * W);
-            DC_CHECK_LAUNCH();
-            const int rc = conv_wreduce(nullptr, pbias, nullptr, dbias, DB_SPLIT, 0, Co, ST);
-            if (rc != DC_OK) return rc;
-        }
-    } else if (w_dw) {
-        const int rc = wino_wgrad_fused(x0, C0, up0 ? 1 : 0, x1, C1, pad_mode, gp, dweight, gws, B, Co, H, W, ST);
-        if (rc != DC_OK) return rc;
-        if (dbias && fused_db) {
-            const int rc2 = conv_wreduce(nullptr, pbd, nullptr, dbias, gpd_split(Co), 0, Co, ST);
-            if (rc2 != DC_OK) return rc2;
-        } else if (dbias) {
-            hipLaunchKernelGGL(conv_dbias_kernel, dim3(Co, DB_SPLIT), dim3(256), 0, ST, gp, pb2, B, Co, H * W);
-            DC_CHECK_LAUNCH();
-            hipLaunchKernelGGL(conv_wreduce_kernel, dim3(ceil_div(Co, 16)), dim3(256), 0, ST, (const float*)nullptr, pb2,
-                               (float*)nullptr, dbias, DB_SPLIT, 0, Co);
-            DC_CHECK_LAUNCH();
-        }
-    } else if (dweight || dbias) {
-        WgradArgs g{};
-        g.x0 = x0; g.C0 = C0; g.up0 = up0 ? 1 : 0; g.x1 = x1; g.C1 = C1; g.y = y; g.gy = gy; g.gp = gp; g.part = part; g.pbias = pbias;
-        g.B = B; g.Co = Co; g.H = H; g.W = W; g.act = act; g.pad = pad_mode;
-        g.tiles_x = tiles_x; g.tiles_y = tiles_y; g.split = split;
-        const int mr = pick_mr_w(Co);
-        const dim3 grid(split, ceil_div(Co, 16 * mr), ceil_div(Cin, CW));
-        if (fast) {
-            if (mr == 2) hipLaunchKernelGGL((conv_wgrad_v2_kernel<2>), grid, dim3(256), 0, ST, g);
-            else hipLaunchKernelGGL((conv_wgrad_v2_kernel<1>), grid, dim3(256), 0, ST, g);
-        } else {
-            if (mr == 2) hipLaunchKernelGGL((conv_wgrad_kernel<2>), grid, dim3(256), 0, ST, g);
-            else hipLaunchKernelGGL((conv_wgrad_kernel<1>), grid, dim3(256), 0, ST, g);
-        }
-        DC_CHECK_LAUNCH();
-        if (dweight) {
-            const int rc = conv_wreduce(part, pbias, dweight, dbias, split, (int)nW, Co, ST);
-            if (rc != DC_OK) return rc;
-        } else {
-            hipLaunchKernelGGL(conv_wreduce_kernel, dim3(ceil_div((int)nW + Co, 16)), dim3(256), 0, ST, part, pbias, dweight,
-                               dbias, split, (int)nW, Co);
-            DC_CHECK_LAUNCH();
-        }
+    if (rc != DC_OK) return rc;
+    switch (c.p.dw) {
+    // (the head's slabs borrow the padded-domain buffer: its own data gradient does not use it, and any other data-gradient path has
+    // finished with it in stream order)
+    case DC_C3_DW_HEAD: rc = dispconv_wgrad(x0, y, gy, dweight, dbias, c.dxpad, B, C0, H, W, act, pad_mode, ST); break;
+    case DC_C3_DW_BF16: rc = c.dw_bf16(); break;
+    case DC_C3_DW_WINO: rc = wino_wgrad_fused(x0, C0, s.up0, x1, C1, pad_mode, c.gp, dweight, c.gws, B, Co, H, W, ST); break;
+    case DC_C3_DW_DIRECT: rc = c.dw_direct(); break;
+    default: break;
     }
-    return DC_OK;
+    if (rc != DC_OK) return rc;
+    switch (c.p.db) {
+    case DC_C3_DB_GPRIME: return conv_wreduce(nullptr, c.pbd, nullptr, dbias, gpd_split(Co), 0, Co, ST);
+    case DC_C3_DB_KERNEL: return c.db_kernel(c.p.dw == DC_C3_DW_WINO ? c.pb2 : c.pbias);     // (each route's own partials, as laid out)
+    default: return DC_OK;      // none, or reduced with the weight slabs above
+    }
 }
 
 extern "C" int dc_set_dgrad_split(int mode) {

@@ -93,6 +93,11 @@ class PoseGroup(Structure):
     _fields_ = [("row0", c_int32), ("rows", c_int32), ("slot", c_int32), ("invert", c_int32)]
 
 
+class Conv3x3Plan(Structure):
+    """Mirror of `dc_conv3x3_plan` (include/depthcore.h: dc_conv3x3_plan_query); the values are the DC_C3_* enums there."""
+    _fields_ = [(n, c_int32) for n in ("fwd", "fwd_v2", "fwd_mr", "gprime", "dx", "ring", "dw", "db", "bwd_v2", "dx_mr", "dw_mr", "split")]
+
+
 _lib = None
 
 
@@ -132,6 +137,7 @@ def _sig(lib):
         "dc_conv3x3_fwd": (i, [p, i, i, p, i, p, p, p, p, i, i, i, i, i, i, p]),
         "dc_conv3x3_bwd_workspace": (z, [i, i, i, i, i, i]),
         "dc_conv3x3_bwd": (i, [p, i, i, p, i, p, p, p, p, p, p, p, p, i, i, i, i, i, i, p]),
+        "dc_conv3x3_plan_query": (i, [i, i, i, i, i, i, i, i, i, i, POINTER(Conv3x3Plan)]),
         "dc_bn_workspace": (z, [i, i, i]),
         "dc_bn_mask_bytes": (z, [i, i, i]),
         "dc_bn_relu_fwd": (i, [p, p, p, p, p, p, p, p, p, p, p, i, i, i, f, f, i, i, p]),

@@ -3,8 +3,9 @@
 kernels (csrc/dispconv.hip), the fused Winograd launches (csrc/wino.hip, csrc/wino_wgrad.hip), the direct implicit GEMMs, the two
 folds, the reflection ring, the split weight-gradient reductions and the four ways g' = gy act'(y) comes about.  Shared by
 tests/test_conv_block_cases_cpu.py (no GPU: the table reaches every mechanism, route() agrees with the library's workspace
-queries, the cases are well conditioned, the refusals are host-side), tests/test_conv_block_shapes_gpu.py (the kernels against the
-statement) and tests/conv_block_direct_child.py (the same with DC_CONV_WINO=0).  DESIGN.md, "The fused 3x3 block at its dispatch
+queries and, field by field, with the plan the launches themselves follow (dc_conv3x3_plan_query), the cases are well conditioned,
+the refusals are host-side), tests/test_conv_block_shapes_gpu.py (the kernels against the statement), tests/conv_block_direct_child.py
+(the same with DC_CONV_WINO=0) and tests/conv_block_plan_child.py (the plan agreement with DC_CONV_WINO=0).  DESIGN.md, "The fused 3x3 block at its dispatch
 edges", has the table with its reasons, the predicates, the gates and the measured figures.
 
     Case                     (B, C0, up0, C1, Co, H, W, act, pad, bias, grads, add0, add1, dsplit)
@@ -13,7 +14,8 @@ edges", has the table with its reasons, the predicates, the gates and the measur
     build(case)              seeded fp32 inputs x0, x1, w, b, gy, add0, add1 and the backward's INPUT y (below)
     evaluate(case, inp, dt)  the statement in `dt`
     reference(case)          cached (inputs, fp64 results, fp32 results); nobody may modify what it returns
-    route(case, wino)        the kernels the two launches run, transcribed from the host code
+    route(case, wino)        the kernels the two launches run, transcribed from the host code (independent of the library: it never
+                             asks dc_conv3x3_plan_query, plan_mismatches() compares the two)
 
 The statement, with u = nearest x2 upsample (up0) or the identity, P = ReflectionPad2d(1) (pad 0) or ZeroPad2d(1) (pad 1):
     forward   y = act(conv2d(P(cat(u(x0), x1)), w) + b)
@@ -328,6 +330,70 @@ def output_kernels(c, wino_enabled=True):
 
 def tol(kernel):
     return WINO_TOL if kernel in WINO_KERNELS else DIRECT_TOL
+
+
+# ---- the library's own plan (include/depthcore.h: dc_conv3x3_plan, the DC_C3_* enums) against route() -------------------------------
+FWD_HEAD, FWD_BF16, FWD_WINO, FWD_DIRECT = range(4)
+GP_UNUSED, GP_GY, GP_ON_THE_FLY, GP_KERNEL, GP_DBIAS_KERNEL = range(5)
+DX_NONE, DX_HEAD, DX_BF16, DX_BF16_FOLD, DX_WINO_SPLIT, DX_WINO_FOLD, DX_DIRECT_FOLD = range(7)
+DW_NONE, DW_HEAD, DW_BF16, DW_WINO, DW_DIRECT = range(5)
+DB_NONE, DB_SLABS, DB_GPRIME, DB_KERNEL = range(4)
+WANT = {"x0": 1, "x1": 2, "w": 4, "b": 8}
+# route()'s kernel names, template arguments stripped, as plan values (the bf16 values have no name: route() is the fp32 policy)
+PLAN_FWD = {"dispconv_fwd4_kernel": FWD_HEAD, "dispconv_fwd_kernel": FWD_HEAD, "wino_conv_fused_fwd": FWD_WINO,
+            "conv_gemm_kernel": FWD_DIRECT, "conv_gemm_v2_kernel": FWD_DIRECT}
+PLAN_GP = {"unused": GP_UNUSED, "gy": GP_GY, "on the fly": GP_ON_THE_FLY, "conv_gprime_kernel": GP_KERNEL,
+           "conv_gprime_dbias_kernel": GP_DBIAS_KERNEL}
+PLAN_DX = {None: DX_NONE, "dispconv_dx_kernel": DX_HEAD, "wino_conv_dgrad_split": DX_WINO_SPLIT, "wino_conv_full_dgrad": DX_WINO_FOLD,
+           "conv_gemm_kernel": DX_DIRECT_FOLD, "conv_gemm_v2_kernel": DX_DIRECT_FOLD}
+PLAN_DW = {None: DW_NONE, "dispconv_wgrad_kernel": DW_HEAD, "wino_wgrad_fused": DW_WINO, "conv_wgrad_kernel": DW_DIRECT,
+           "conv_wgrad_v2_kernel": DW_DIRECT}
+PLAN_DB = {None: DB_NONE, "conv_gprime_dbias_kernel": DB_GPRIME, "conv_dbias_kernel": DB_KERNEL}
+
+
+def _kernel(name):
+    """(name without template arguments, first template argument or 0)"""
+    if name is None or "<" not in name:
+        return name, 0
+    return name[:name.index("<")], int(name[name.index("<") + 1:].rstrip(">").split(",")[0])
+
+
+def plan_of(r):
+    """route()'s answer as the fields of dc_conv3x3_plan.  fwd_v2 / fwd_mr, dx_mr and dw_mr are 0 unless the direct kernel of that pass
+    runs; `split` counts the direct weight gradient's slabs (the head's and Winograd's are chosen inside their own files: 0)."""
+    (fwd, fwd_mr), (dx, dx_mr), (dw, dw_mr) = _kernel(r["fwd"]), _kernel(r["dx"]), _kernel(r["dw"])
+    direct_f, direct_dx, direct_dw = PLAN_FWD[fwd] == FWD_DIRECT, PLAN_DX[dx] == DX_DIRECT_FOLD, PLAN_DW[dw] == DW_DIRECT
+    assert not direct_dx or dx.endswith("_v2_kernel") == r["fast"]
+    assert not direct_dw or dw.endswith("_v2_kernel") == r["fast"]
+    return {"fwd": PLAN_FWD[fwd], "fwd_v2": int(direct_f and fwd.endswith("_v2_kernel")), "fwd_mr": fwd_mr if direct_f else 0,
+            "gprime": PLAN_GP[r["gprime"]], "dx": PLAN_DX[dx], "ring": int(r["ring"]), "dw": PLAN_DW[dw],
+            "db": DB_SLABS if r["db"] is not None and r["db"] == r["dw"] else PLAN_DB[r["db"]], "bwd_v2": int(r["fast"]),
+            "dx_mr": dx_mr if direct_dx else 0, "dw_mr": dw_mr if direct_dw else 0, "split": r["split"] if direct_dw else 0}
+
+
+def plan_query(c, grads=None):
+    """dc_conv3x3_plan_query of the case (`grads`: another request than the case's) under the mode and precision in effect:
+    (return code, {field: value})."""
+    import ctypes
+    from depthcore import _lib
+    p = _lib.Conv3x3Plan()
+    want = sum(WANT[g] for g in (c.grads if grads is None else grads))
+    rc = host_lib().dc_conv3x3_plan_query(c.C0, c.up0, c.C1, c.B, c.Co, c.H, c.W, c.act, c.pad, want, ctypes.byref(p))
+    return rc, {n: getattr(p, n) for n, _ in p._fields_}
+
+
+def plan_mismatches(c, wino_enabled=True):
+    """[(field, the library's value, route()'s value)] of the case under its own dsplit mode -- empty when they agree."""
+    L = host_lib()
+    prev = L.dc_set_dgrad_split(c.dsplit)
+    try:
+        rc, got = plan_query(c)
+    finally:
+        L.dc_set_dgrad_split(prev)
+    assert rc == 0, rc
+    want = plan_of(route(c, wino_enabled))
+    assert set(want) == set(got)
+    return [(k, got[k], want[k]) for k in sorted(want) if got[k] != want[k]]
 
 
 def fwd_workspace(c, wino_enabled=True):

@@ -1,9 +1,13 @@
 """The cases of tests/conv_block_cases.py are fit to judge the fused 3x3 block's fp32 dispatch with: the table reaches every
 mechanism it is there for (computed by route(), the transcription of the host code in dc_conv3x3_fwd / dc_conv3x3_bwd_add, which
-is cross-checked against the library's own workspace queries for every case), every case is finite and well conditioned (torch's
+is cross-checked against the library's own workspace queries and, field by field, against the plan the launches themselves follow
+(dc_conv3x3_plan_query) for every case), every case is finite and well conditioned (torch's
 fp32 evaluation of the statement is within 1e-4 of fp64, no result is all zero, the planted ties are there) -- and the entries
 refuse what they cannot run (host-side checks: DC_EINVAL before anything is launched).  Needs no GPU."""
 import ctypes
+import os
+import subprocess
+import sys
 
 import pytest
 import torch
@@ -238,3 +242,101 @@ def test_refusals_are_host_side(name, shape, withheld):
                                 None) == CC.EINVAL, name
     assert L.dc_clear_error() == idle       # no HIP call failed on the way: nothing was attempted
     assert L.dc_set_dgrad_split(3) == CC.EINVAL
+
+
+# ---- the plan the launches follow (dc_conv3x3_plan_query) against route() -----------------------------------------------------------
+@pytest.mark.parametrize("case", CC.params(CC.CASES))
+def test_plan_agrees_with_route(case):
+    """fwd, fwd_v2, fwd_mr, gprime, dx, ring, dw, db, bwd_v2, dx_mr, dw_mr and split of the library's plan -- what dc_conv3x3_fwd and
+    dc_conv3x3_bwd_add switch on -- are what route() names, under the case's dsplit mode and with the case's gradients requested."""
+    assert CC.plan_mismatches(case) == []
+
+
+@pytest.mark.parametrize("family", sorted(CC.NULL_FAMILIES))
+def test_plan_agrees_with_route_for_every_null_pattern(family):
+    base, nulls = CC.NULL_FAMILIES[family]
+    seen = set()
+    for c in [base] + list(nulls):
+        assert CC.plan_mismatches(c) == [], CC.case_id(c)
+        seen.add(tuple(sorted(CC.plan_query(c)[1].items())))
+    assert len(seen) > 1        # the request is part of the plan: the patterns do not fall together
+    # the forward's plan is that of the shape alone
+    assert len({CC.plan_query(c)[1]["fwd"] for c in [base] + list(nulls)}) == 1
+
+
+def test_plan_agrees_with_route_with_winograd_disabled():
+    """DC_CONV_WINO is read once per process: tests/conv_block_plan_child.py compares the plan with route(case, False) for every
+    case of direct_child_cases() in a fresh process (no GPU there either)."""
+    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "conv_block_plan_child.py")
+    p = subprocess.run([sys.executable, child], env={**os.environ, "DC_CONV_WINO": "0"}, timeout=300, stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT, text=True)
+    print(p.stdout)
+    assert p.returncode == 0, p.stdout[-4000:]
+    want = {CC.case_id(c) for c in CC.direct_child_cases()}
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("conv_block_plan ")]
+    assert {ln.split()[1] for ln in lines} == want and len(lines) == len(want)
+    assert {m for ln in lines for m in (1, 2, 4) if "fwd_v2=1 fwd_mr=%d " % m in ln} == {1, 2, 4}
+    assert p.stdout.rstrip().endswith("conv_block_plan_done %d" % len(want))
+
+
+@pytest.mark.parametrize("name,shape", [pytest.param(r[0], r[1], id=r[0].replace(" ", "_")) for r in REFUSALS if not r[2]])
+def test_plan_query_refuses_what_the_launches_refuse(name, shape):
+    L = CC.host_lib()
+    assert sum(1 for r in REFUSALS if not r[2]) == 5
+    B, C0, up0, C1, Co, H, W, act, pad = shape
+    c = CC.K(B, C0, up0, C1, Co, H, W, act, pad)
+    L.dc_clear_error()
+    idle = L.dc_clear_error()
+    for grads in ((), c.grads, ("w",)):
+        assert CC.plan_query(c, grads)[0] == CC.EINVAL, name
+    assert L.dc_conv3x3_plan_query(C0, up0, C1, B, Co, H, W, act, pad, 15, None) == CC.EINVAL
+    assert L.dc_clear_error() == idle       # the query makes no HIP call
+    ok = CC.K(2, 8, 0, 8, 8, 8, 8, 1, 0)    # (the two rows that withhold an operand: their shape is fine)
+    assert CC.plan_query(ok)[0] == 0 and L.dc_conv3x3_plan_query(8, 0, 8, 2, 8, 8, 8, 1, 0, 15, None) == CC.EINVAL
+    assert L.dc_clear_error() == idle
+
+
+PREC_F32, PREC_BF16 = 0, 1
+
+
+def _plan_under(precision, c):
+    L = CC.host_lib()
+    prev = L.dc_set_matrix_precision(precision)         # (per calling thread)
+    assert prev in (PREC_F32, PREC_BF16)
+    try:
+        rc, got = CC.plan_query(c)
+    finally:
+        L.dc_set_matrix_precision(prev)
+    assert rc == 0
+    return got
+
+
+def test_plan_under_the_bf16_policy():
+    """dc_set_matrix_precision(DC_PREC_BF16) on the calling thread: the plan names the bf16 kernels where their 16-byte staging takes
+    the shape, the direct fp32 weight gradient below DC_B16_DW_MIN output channels, the head kernels before either -- and is the
+    fp32 plan where c3b_eligible refuses."""
+    ELU, SIGMOID = CC.ACT_ELU, CC.ACT_SIGMOID
+    # zero pad, single source, no upsample: the data gradient straight from the bf16 kernel; g' and the bias partials in one pass
+    p = _plan_under(PREC_BF16, CC.K(2, 16, 0, 0, 32, 8, 16, ELU, ZERO))
+    assert (p["fwd"], p["dx"], p["dw"], p["gprime"], p["db"]) == (CC.FWD_BF16, CC.DX_BF16, CC.DW_BF16, CC.GP_DBIAS_KERNEL, CC.DB_GPRIME)
+    assert p["split"] == CC.c3b_wgrad_split(2, 8, 16, 32, 16) and not p["ring"] and (p["fwd_mr"], p["dx_mr"], p["dw_mr"]) == (0, 0, 0)
+    # upsample + concat + reflect: over the padded domain, then the fold
+    p = _plan_under(PREC_BF16, CC.K(2, 32, 1, 32, 32, 8, 16, ELU, REFLECT))
+    assert (p["fwd"], p["dx"], p["dw"], p["gprime"], p["db"]) == (CC.FWD_BF16, CC.DX_BF16_FOLD, CC.DW_BF16, CC.GP_DBIAS_KERNEL, CC.DB_GPRIME)
+    # Co = 8 < DC_B16_DW_MIN: conv_wgrad_v2_kernel<1> fed by conv_gprime_kernel, not Winograd; the bias gradient from its slabs
+    c8 = CC.K(2, 16, 0, 0, 8, 8, 16, ELU, ZERO)
+    p = _plan_under(PREC_BF16, c8)
+    assert (p["fwd"], p["dx"], p["dw"], p["gprime"], p["db"]) == (CC.FWD_BF16, CC.DX_BF16, CC.DW_DIRECT, CC.GP_KERNEL, CC.DB_SLABS)
+    assert (p["bwd_v2"], p["dw_mr"], p["split"]) == (1, 1, CC.pick_split(2, 8, 16, 8, 16))
+    # the single-channel head goes first, in both passes
+    p = _plan_under(PREC_BF16, CC.K(2, 16, 0, 0, 1, 8, 16, SIGMOID, REFLECT))
+    assert (p["fwd"], p["dx"], p["dw"], p["gprime"], p["db"]) == (CC.FWD_HEAD, CC.DX_HEAD, CC.DW_HEAD, CC.GP_UNUSED, CC.DB_SLABS)
+    # W = 18: c3b_eligible refuses -- the fp32 plan, which is route()'s
+    c18 = CC.K(2, 16, 0, 0, 32, 8, 18, ELU, ZERO)
+    p = _plan_under(PREC_BF16, c18)
+    assert p == _plan_under(PREC_F32, c18) == CC.plan_of(CC.route(c18)) and p["fwd"] == CC.FWD_WINO and p["dx"] == CC.DX_WINO_SPLIT
+    # ... and each bf16 plan above differs from its fp32 one, which is route()'s
+    for c in (CC.K(2, 16, 0, 0, 32, 8, 16, ELU, ZERO), CC.K(2, 32, 1, 32, 32, 8, 16, ELU, REFLECT), c8):
+        f = _plan_under(PREC_F32, c)
+        assert f == CC.plan_of(CC.route(c)) and f != _plan_under(PREC_BF16, c)
+    assert CC.host_lib().dc_get_matrix_precision() == PREC_F32
