@@ -17,7 +17,7 @@ __device__ __forceinline__ unsigned c3b_pack_bf16(float lo, float hi) {
     return __builtin_bit_cast(unsigned, p);
 }
 // One 16-byte item of the prepared bf16 weights [m-block][chunk][tap][k-group 4][m MT][8] (conv_bf16.hip: c3b_wprep_kernel, and the
-// weight cache's batched refresh in wino.hip): forward M = Co, K = Cin, value w[m][k][tap]; data gradient M = Cin, K = Co, value
+// weight cache's batched refresh in weight_cache.hip): forward M = Co, K = Cin, value w[m][k][tap]; data gradient M = Cin, K = Co, value
 // w[k][m][8 - tap] (rotated, transposed filter).
 __device__ __forceinline__ void c3b_wprep_item(const float* __restrict__ w, uint4* __restrict__ wb, int idx, int Co, int Cin, int dgrad,
                                                int MT, int nmblk, int nchunks) {
@@ -37,10 +37,6 @@ __device__ __forceinline__ void c3b_wprep_item(const float* __restrict__ w, uint
     wb[idx] = make_uint4(c3b_pack_bf16(v[0], v[1]), c3b_pack_bf16(v[2], v[3]), c3b_pack_bf16(v[4], v[5]), c3b_pack_bf16(v[6], v[7]));
 }
 #endif
-
-// the prepared bf16 weights of (weight, pass, MT) from the per-step weight cache (wino.hip: dc_wino_cache_*), or nullptr: then the
-// caller packs them into its workspace as before.  Same rules as the Winograd variants (registered weights, fresh after a refresh).
-const void* wc_lookup_c3b(const float* w, int Ci, int Co, int dgrad, int MT, int nmblk, int nchunks, hipStream_t st);
 
 // shapes the bf16 kernels take (16-byte staging): stride 1: W % 4 == 0 (W % 8 == 0 when x0 is upsampled / dilated), concat
 // boundary on a 32-channel chunk; stride 2: W % 8 == 0, single source.  Anything else keeps the fp32 kernels.

@@ -28,7 +28,8 @@
 //     slabs, summed in fixed order by conv_wreduce_kernel (deterministic, no atomics).
 #include "dc_common.h"
 #include "conv_bf16.h"
-#include "wino.h"
+#include "conv_prof.h"
+#include "weight_cache.h"
 
 #include <algorithm>
 
@@ -540,7 +541,7 @@ int c3b_conv(const float* x0, int C0, int up0, const float* x1, int C1, const fl
     // MACs, i.e. a quarter of the positions); executed: what the matrix cores are issued; bytes: each operand and the result once
     const double macs = (double)B * M * K * 9.0 * a.OH * a.OW * ((up0 & 2) ? 0.25 : 1.0);
     const double in_elems = (double)B * ((double)C0 * (H >> (up0 & 1)) * (W >> (up0 & 1)) + (double)C1 * H * W);
-    hipEvent_t pe = conv_prof_begin(2, 2.0 * macs, 2.0 * (double)nblk * (stride == 1 ? 256 : 128) * MT * (double)(nchunks * BC) * 9.0,
+    hipEvent_t pe = conv_prof_begin(PROF_C3B_CONV, 2.0 * macs, 2.0 * (double)nblk * (stride == 1 ? 256 : 128) * MT * (double)(nchunks * BC) * 9.0,
                                     4.0 * (in_elems + (double)B * M * a.OH * a.OW) + 36.0 * Co * Cin, st);
 #define C3B_LAUNCH(MRV, SV, DP) hipLaunchKernelGGL((c3b_conv_kernel<MRV, SV, DP>), grid, dim3(512), 0, st, a)
     if (stride == 2) {
@@ -572,7 +573,7 @@ int c3b_wgrad(const float* x0, int C0, int up0, const float* x1, int C1, const f
     const dim3 grid(split, ceil_div(Co, 64), ceil_div(C0 + C1, BC));
     const int Cin = C0 + C1;
     const double in_elems = (double)B * ((double)C0 * (H >> up0) * (W >> up0) + (double)C1 * H * W);
-    hipEvent_t pe = conv_prof_begin(3, 2.0 * (double)B * Co * Cin * 9.0 * a.OH * a.OW,
+    hipEvent_t pe = conv_prof_begin(PROF_C3B_WGRAD, 2.0 * (double)B * Co * Cin * 9.0 * a.OH * a.OW,
                                     2.0 * (double)a.tiles_x * a.tiles_y * B * TH * 32.0 * (grid.y * 64.0) * (grid.z * 32.0) * 9.0,
                                     4.0 * (in_elems + (double)B * Co * a.OH * a.OW) + 36.0 * Co * Cin, st);
     if (stride == 1) hipLaunchKernelGGL((c3b_wgrad_kernel<1>), grid, dim3(512), 0, st, a);

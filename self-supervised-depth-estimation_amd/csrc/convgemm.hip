@@ -25,7 +25,7 @@
 #include "conv_bf16.h"
 #include "gemm_tiles.h"
 #include "gemm1x1_x3.h"
-#include "wino.h"
+#include "conv_prof.h"
 
 #include <stdlib.h>
 
@@ -1105,7 +1105,7 @@ extern "C" int dc_convs2_fwd(const float* x, const float* weight, float* y, void
     if (stem_ok(Ci, Co, ksize)) {
         StemArgs sa = stem_args(B, Ci, Co, Hi, Wi);
         sa.x = x; sa.w = a.w; sa.out = y;
-        hipEvent_t pe = conv_prof_begin(6, 2.0 * B * (double)Co * a.K * a.Ho * a.Wo, 2.0 * B * (double)Co * sa.Kp * a.Ho * a.Wo,
+        hipEvent_t pe = conv_prof_begin(PROF_STEM, 2.0 * B * (double)Co * a.K * a.Ho * a.Wo, 2.0 * B * (double)Co * sa.Kp * a.Ho * a.Wo,
                                         4.0 * ((double)B * Ci * Hi * Wi + (double)B * Co * a.Ho * a.Wo + (double)Co * a.K), st);
         if (stem_x3_enabled() && a.Kp != a.K) {
             const int rc = stem_fwd_x3_launch<false>(sa, ws, st);
@@ -1128,7 +1128,7 @@ extern "C" int dc_convs2_fwd(const float* x, const float* weight, float* y, void
         if (!attr3) return DC_ELAUNCH;
         const dim3 grid(a.mtiles * a.ntiles, sp);
         // 2 MAC of the convolution; executed = the padded 64 x (32 nt) tiles over the whole reduction
-        hipEvent_t pe = conv_prof_begin(5, 2.0 * (double)N * Co * a.K, 2.0 * (double)a.mtiles * 64.0 * (double)a.ntiles * 32.0 * t.nt * a.K,
+        hipEvent_t pe = conv_prof_begin(PROF_CG, 2.0 * (double)N * Co * a.K, 2.0 * (double)a.mtiles * 64.0 * (double)a.ntiles * 32.0 * t.nt * a.K,
                                         4.0 * ((double)B * Ci * Hi * Wi + (double)N * Co + (double)Co * a.K), st);
         if (t.nt == 4) hipLaunchKernelGGL((cg_fwd3_kernel<2, 4>), grid, dim3(256), lds3, st, a);
         else hipLaunchKernelGGL((cg_fwd3_kernel<2, 2>), grid, dim3(256), lds3, st, a);
@@ -1188,7 +1188,7 @@ extern "C" int dc_convs2_wgrad(const float* x, const float* gy, float* dweight, 
         StemArgs sa = stem_args(B, Ci, Co, Hi, Wi);
         sa.x = x; sa.gy = gy; sa.out = (float*)ws;
         const size_t lds = stem_lds_wgrad(Ci);
-        hipEvent_t pe = conv_prof_begin(6, 2.0 * B * (double)Co * sa.K * (Hi / 2) * (Wi / 2), 2.0 * B * (double)Co * sa.Kp * (Hi / 2) * (Wi / 2),
+        hipEvent_t pe = conv_prof_begin(PROF_STEM, 2.0 * B * (double)Co * sa.K * (Hi / 2) * (Wi / 2), 2.0 * B * (double)Co * sa.Kp * (Hi / 2) * (Wi / 2),
                                         4.0 * ((double)B * Ci * Hi * Wi + (double)B * Co * (Hi / 2) * (Wi / 2) + (double)Co * sa.K), st);
         if (Ci == 3) hipLaunchKernelGGL((stem_wgrad_kernel<5, false>), dim3(sa.nblocks), dim3(256), lds, st, sa);
         else hipLaunchKernelGGL((stem_wgrad_kernel<10, false>), dim3(sa.nblocks), dim3(256), lds, st, sa);
@@ -1209,7 +1209,7 @@ extern "C" int dc_convs2_wgrad(const float* x, const float* gy, float* dweight, 
     a.out = a.splits > 1 ? (float*)ws : dweight;
     const dim3 grid(a.mtiles * a.ntiles, a.splits);
     const size_t lds = trip ? (size_t)2 * (64 + 96) * (GKC + RP) * sizeof(float) : cg_lds_wgrad({2, 2});
-    hipEvent_t pe = ksize == 3 ? conv_prof_begin(5, 2.0 * (double)B * a.Ho * a.Wo * Co * a.K,
+    hipEvent_t pe = ksize == 3 ? conv_prof_begin(PROF_CG, 2.0 * (double)B * a.Ho * a.Wo * Co * a.K,
                                                  2.0 * (double)a.chunks * GKC * (double)a.mtiles * 64.0 * (double)a.ntiles * (trip ? 96.0 : 64.0),
                                                  4.0 * ((double)B * Ci * Hi * Wi + (double)B * a.Ho * a.Wo * Co + (double)Co * a.K), st) : nullptr;
     if (trip) hipLaunchKernelGGL(cg_wgrad3_kernel, grid, dim3(256), lds, st, a);
@@ -1256,7 +1256,7 @@ extern "C" int dc_stem_fwd(const float* const* frames, int nf, float mean, float
     DC_CHECK_LAUNCH();
     sa.w = (const float*)ws; sa.out = y;
     const double npix = (double)sa.B * (Hi / 2) * (Wi / 2);
-    hipEvent_t pe = conv_prof_begin(6, 2.0 * npix * Co * sa.K, 2.0 * npix * Co * sa.Kp,
+    hipEvent_t pe = conv_prof_begin(PROF_STEM, 2.0 * npix * Co * sa.K, 2.0 * npix * Co * sa.Kp,
                                     4.0 * ((double)sa.B * sa.Ci * Hi * Wi + npix * Co + (double)Co * sa.K), st);
     if (stem_x3_enabled()) {
         const int rc = stem_fwd_x3_launch<true>(sa, ws, st);
@@ -1277,7 +1277,7 @@ extern "C" int dc_stem_wgrad(const float* const* frames, int nf, float mean, flo
     sa.gy = gy; sa.out = (float*)ws;
     const size_t lds = stem_lds_wgrad(sa.Ci);
     const double npix = (double)sa.B * (Hi / 2) * (Wi / 2);
-    hipEvent_t pe = conv_prof_begin(6, 2.0 * npix * Co * sa.K, 2.0 * npix * Co * sa.Kp,
+    hipEvent_t pe = conv_prof_begin(PROF_STEM, 2.0 * npix * Co * sa.K, 2.0 * npix * Co * sa.Kp,
                                     4.0 * ((double)sa.B * sa.Ci * Hi * Wi + npix * Co + (double)Co * sa.K), st);
     if (sa.Ci == 3) hipLaunchKernelGGL((stem_wgrad_kernel<5, true>), dim3(sa.nblocks), dim3(256), lds, st, sa);
     else hipLaunchKernelGGL((stem_wgrad_kernel<10, true>), dim3(sa.nblocks), dim3(256), lds, st, sa);
@@ -1329,7 +1329,7 @@ extern "C" int dc_convs2_dgrad(const float* gy, const float* weight, float* dx, 
     const dim3 grid(a.mtiles * a.ntiles, 2, sp);
     const size_t lds = cg_lds_dgrad(t);
     // (split by output parity: no multiply meets a structural zero -- executed = the padded tiles of the same 2 MAC count)
-    hipEvent_t pe = conv_prof_begin(5, 2.0 * (double)N * Co * Ci * 9.0, 2.0 * (double)a.mtiles * 64.0 * (double)a.ntiles * 64.0 * Co * 9.0,
+    hipEvent_t pe = conv_prof_begin(PROF_CG, 2.0 * (double)N * Co * Ci * 9.0, 2.0 * (double)a.mtiles * 64.0 * (double)a.ntiles * 64.0 * Co * 9.0,
                                     4.0 * ((double)B * Ci * Hi * Wi + (double)N * Co + 9.0 * Co * Ci), st);
     hipLaunchKernelGGL((cg_dgrad3_kernel<2, 2>), grid, dim3(256), lds, st, a);
     conv_prof_end(pe, st);

@@ -33,7 +33,7 @@
 // tile is fetched from HBM once per XCD pass and re-served by that XCD's L2; the weights are L2-resident.
 #include "dc_common.h"
 #include "gemm1x1.h"
-#include "wino.h"
+#include "conv_prof.h"
 #include "gemm_tiles.h"
 
 #include <algorithm>
@@ -720,7 +720,7 @@ extern "C" int dc_gemm1x1_fwd(const float* x, const float* weight, const float* 
                              set_max_dynamic_lds(g1_fwd_kernel<4, 4, true, 2>, g1_lds_fwd({4, 4})) &&
                              set_max_dynamic_lds(g1_fwd_kernel<4, 4, false, 1, true>, g1_lds_fwd({4, 4}));
     if (!attr) return DC_ELAUNCH;
-    hipEvent_t pe = conv_prof_begin(4, 2.0 * (double)B * Co * Ci * a.Ho * a.Wo, 2.0 * (double)grid.x * (32.0 * t.mt) * (32.0 * t.nt) * Ci, 4.0 * ((double)B * Ci * a.Ho * a.Wo + (double)B * Co * a.Ho * a.Wo + (double)Co * Ci), st);
+    hipEvent_t pe = conv_prof_begin(PROF_G1, 2.0 * (double)B * Co * Ci * a.Ho * a.Wo, 2.0 * (double)grid.x * (32.0 * t.mt) * (32.0 * t.nt) * Ci, 4.0 * ((double)B * Ci * a.Ho * a.Wo + (double)B * Co * a.Ho * a.Wo + (double)Co * Ci), st);
 #define G1_FWD(MT, NT)                                                                            \
     do {                                                                                          \
         if (bnin) {                                                                                   \
@@ -769,7 +769,7 @@ extern "C" int dc_gemm1x1_dgrad(const float* gy, const float* weight, float* dx,
                              set_max_dynamic_lds(g1_dgrad_kernel<4, 4, 2>, g1_lds_dgrad({4, 4})) && set_max_dynamic_lds(g1_dgrad_kernel<4, 4, 0, 2>, g1_lds_dgrad({4, 4})) &&
                              set_max_dynamic_lds(g1_dgrad_kernel<4, 4, 0, 3>, g1_lds_dgrad({4, 4}));
     if (!attr) return DC_ELAUNCH;
-    hipEvent_t pe = conv_prof_begin(4, 2.0 * (double)B * Co * Ci * a.Ho * a.Wo, 2.0 * (double)grid.x * (32.0 * t.mt) * (32.0 * t.nt) * Co, 4.0 * ((double)B * Ci * a.Ho * a.Wo + (double)B * Co * a.Ho * a.Wo + (double)Co * Ci), st);
+    hipEvent_t pe = conv_prof_begin(PROF_G1, 2.0 * (double)B * Co * Ci * a.Ho * a.Wo, 2.0 * (double)grid.x * (32.0 * t.mt) * (32.0 * t.nt) * Co, 4.0 * ((double)B * Ci * a.Ho * a.Wo + (double)B * Co * a.Ho * a.Wo + (double)Co * Ci), st);
 #define G1_DGRAD(BNE, SD)                                                                                  \
     do {                                                                                                   \
         if (t.mt == 4) hipLaunchKernelGGL((g1_dgrad_kernel<4, 4, BNE, SD>), grid, dim3(256), lds, st, a);      \
@@ -819,7 +819,7 @@ extern "C" int dc_gemm1x1_wgrad(const float* x, const float* gy, float* dweight,
     static const bool attr = set_max_dynamic_lds(g1_wgrad_kernel<4, 4, 1>, g1_lds_wgrad({4, 4})) && set_max_dynamic_lds(g1_wgrad_kernel<4, 4, 2>, g1_lds_wgrad({4, 4})) &&
                              set_max_dynamic_lds(g1_wgrad_kernel<4, 4, 1, true>, g1_lds_wgrad({4, 4}));
     if (!attr) return DC_ELAUNCH;
-    hipEvent_t pe = conv_prof_begin(4, 2.0 * (double)B * Co * Ci * a.Ho * a.Wo, 2.0 * (double)grid.x * (32.0 * t.mt) * (32.0 * t.nt) * (double)a.chunks * GKC, 4.0 * ((double)B * Ci * a.Ho * a.Wo + (double)B * Co * a.Ho * a.Wo + (double)Co * Ci), st);
+    hipEvent_t pe = conv_prof_begin(PROF_G1, 2.0 * (double)B * Co * Ci * a.Ho * a.Wo, 2.0 * (double)grid.x * (32.0 * t.mt) * (32.0 * t.nt) * (double)a.chunks * GKC, 4.0 * ((double)B * Ci * a.Ho * a.Wo + (double)B * Co * a.Ho * a.Wo + (double)Co * Ci), st);
     if (bnin) {
         if (t.mt == 4) hipLaunchKernelGGL((g1_wgrad_kernel<4, 4, 1, true>), grid, dim3(256), lds, st, a);
         else hipLaunchKernelGGL((g1_wgrad_kernel<2, 2, 1, true>), grid, dim3(256), lds, st, a);

@@ -1,4 +1,4 @@
-// Split-operand 1x1 GEMMs (gemm1x1_x3.hip): what the per-step weight cache (wino.hip: dc_wino_cache_*) needs of them.
+// Split-operand 1x1 GEMMs (gemm1x1_x3.hip): what the per-step weight cache (weight_cache.hip: dc_wino_cache_*) needs of them.
 #pragma once
 #include "dc_common.h"
 
@@ -60,8 +60,5 @@ size_t g1x3_conv3s2_fwd_ws(int Ci, int Co);
 size_t g1x3_conv3s2_wgrad_ws(int B, int Ci, int Co, int Hi, int Wi);
 int g1x3_conv3s2_fwd(const float* x, const float* weight, float* y, void* ws, int B, int Ci, int Co, int Hi, int Wi, hipStream_t st);
 int g1x3_conv3s2_wgrad(const float* x, const float* gy, float* dweight, void* ws, int B, int Ci, int Co, int Hi, int Wi, hipStream_t st);
-
-// the split weights of (weight, direction) from the per-step weight cache, or nullptr (then the launch prepares them into its workspace)
-const void* wc_lookup_x3(const float* w, int Ci, int Co, int tr, int Mp, int K, hipStream_t st);
 
 }  // namespace dc

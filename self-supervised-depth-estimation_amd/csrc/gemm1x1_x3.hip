@@ -33,7 +33,8 @@
 #include "gemm1x1.h"
 #include "gemm1x1_x3.h"
 #include "gemm_tiles.h"
-#include "wino.h"
+#include "conv_prof.h"
+#include "weight_cache.h"
 
 #include <algorithm>
 #include <stdio.h>
@@ -814,7 +815,7 @@ static int g1x3_launch(const float* src, const float* weight, float* out, void* 
     // family 7: algorithmic = 2 MAC of the GEMM; executed = the six bf16 products of every padded tile (bf16 matrix FLOPs);
     // bytes: the operand as the loader reads it (S = 3: the input map once, not its nine taps)
     const double src_elems = S == 3 ? (double)B * Ci * Hi * Wi : (double)N * K;
-    hipEvent_t pe = conv_prof_begin(7, 2.0 * (double)N * M * K, 12.0 * (double)grid.x * (32.0 * t.mt) * (32.0 * t.nt) * K,
+    hipEvent_t pe = conv_prof_begin(PROF_G1X3, 2.0 * (double)N * M * K, 12.0 * (double)grid.x * (32.0 * t.mt) * (32.0 * t.nt) * K,
                                     4.0 * (src_elems + (double)N * M + (double)M * K), st);
     const int rc = x3_with_tile(t, [&](auto tg) { return g1x3_go<decltype(tg)::mt, decltype(tg)::nt>(a, grid, S, epi, mode, st); });
     conv_prof_end(pe, st);
@@ -904,7 +905,7 @@ static int g1x3_wlaunch(const float* x, const float* gy, float* dweight, void* w
     const dim3 grid(a.mtiles * a.ntiles, a.splits);
     const double npx = (double)B * a.Ho * a.Wo;
     const double x_elems = S == 3 ? (double)B * Ci * Hi * Wi : npx * Kc;       // (as in g1x3_launch: the input map once)
-    hipEvent_t pe = conv_prof_begin(7, 2.0 * npx * Co * Kc, 12.0 * npx * (double)a.mtiles * (32.0 * p.t.mt) * (double)a.ntiles * (32.0 * p.t.nt),
+    hipEvent_t pe = conv_prof_begin(PROF_G1X3, 2.0 * npx * Co * Kc, 12.0 * npx * (double)a.mtiles * (32.0 * p.t.mt) * (double)a.ntiles * (32.0 * p.t.nt),
                                     4.0 * (x_elems + npx * Co + (double)Co * Kc), st);
     const int rc = x3_with_tile(p.t, [&](auto tg) { return g1x3_wgo<decltype(tg)::mt, decltype(tg)::nt>(a, grid, S, bnin, st); });
     conv_prof_end(pe, st);

@@ -35,14 +35,13 @@
 // Requires even W (8-byte row alignment); H arbitrary.
 #include "dc_common.h"
 #include "conv_bf16.h"
+#include "conv_prof.h"
+#include "weight_cache.h"
 #include "wino.h"
 #include "wino4.h"
-#include "gemm1x1_x3.h"
 
 #include <algorithm>
 #include <cstdio>
-#include <mutex>
-#include <vector>
 
 namespace dc {
 
@@ -50,83 +49,17 @@ using f4 = __attribute__((ext_vector_type(4))) float;
 using f2w = __attribute__((ext_vector_type(2))) float;
 using wrsrc_t = __amdgpu_buffer_rsrc_t;
 
-// U = G g G^T for every (m, k), written in staging order.  grid over padded (Mp x Kp); one thread per (m, k).
-template <bool DGRAD>
-__device__ __forceinline__ void wino_weight_one(const float* __restrict__ w, float* __restrict__ uhat, int idx, int Co, int Ci, int MT,
-                                                int Mp, int Kp, int WK) {
-    // 256 consecutive threads = a 16 (m) x 16 (k) tile with m fastest: the 16-byte stores of 16 consecutive m are one
-    // 256-byte run (the staging order has m innermost), and the filter reads stay efficient -- 16 consecutive k of a row are
-    // 576 contiguous bytes (forward), 16 consecutive m are (data gradient).  With k fastest the batched launch spent 310 us
-    // on 440 MB: every store instruction scattered 16-byte pieces 256 bytes apart.
-    const int tiles_k = (Kp + 15) >> 4;
-    const int tile = idx >> 8, within = idx & 255;
-    const int m = (tile / tiles_k) * 16 + (within & 15), k = (tile % tiles_k) * 16 + (within >> 4);
-    if (m >= Mp || k >= Kp) return;
-    const int M = DGRAD ? Ci : Co, K = DGRAD ? Co : Ci;
-    float g[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            float v = 0.f;
-            if (m < M && k < K)
-                v = DGRAD ? w[((size_t)k * Ci + m) * 9 + (2 - i) * 3 + (2 - j)] : w[((size_t)m * Ci + k) * 9 + i * 3 + j];
-            g[i][j] = v;
-        }
-    float t[4][3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        t[0][j] = g[0][j];
-        t[1][j] = 0.5f * (g[0][j] + g[1][j] + g[2][j]);
-        t[2][j] = 0.5f * (g[0][j] - g[1][j] + g[2][j]);
-        t[3][j] = g[2][j];
-    }
-    float u[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        u[i][0] = t[i][0];
-        u[i][1] = 0.5f * (t[i][0] + t[i][1] + t[i][2]);
-        u[i][2] = 0.5f * (t[i][0] - t[i][1] + t[i][2]);
-        u[i][3] = t[i][2];
-    }
-    const int mb = m / MT, mi = m - mb * MT, kc = k / WK, kin = k - kc * WK;
-    const int nchunks = Kp / WK;
-    float* dst = uhat + ((((size_t)mb * nchunks + kc) * WK + kin) * 4) * MT * 4 + (size_t)mi * 4;
-#pragma unroll
-    for (int pq = 0; pq < 4; ++pq)
-        *reinterpret_cast<float4*>(dst + (size_t)pq * MT * 4) = make_float4(u[pq][0], u[pq][1], u[pq][2], u[pq][3]);
-}
+// U of one weight into the launch's workspace (weight_cache.h: wino_weight_one): a weight the cache does not hold fresh
 template <bool DGRAD>
 __global__ __launch_bounds__(256) void wino_weights_kernel(const float* __restrict__ w, float* __restrict__ uhat,
                                                            int Co, int Ci, int MT, int Mp, int Kp, int WK) {
     wino_weight_one<DGRAD>(w, uhat, blockIdx.x * 256 + threadIdx.x, Co, Ci, MT, Mp, Kp, WK);
 }
 
-// Every registered weight of a model in ONE launch (dc_wino_cache_refresh): `table` holds one descriptor per (weight,
-// dgrad, MT) variant with the first block of its range; a block finds its descriptor by binary search.
-struct WinoWDesc {
-    const float* w; float* uhat;
-    int Co, Ci, MT, Mp, Kp, dgrad, block0, kind;      // kind 1: the bf16 direct kernels' prepared weights (Mp = m-blocks, Kp = chunks)
-};
-__global__ __launch_bounds__(256) void wino_weights_batched_kernel(const WinoWDesc* __restrict__ table, const int* __restrict__ blk2desc, int WK) {
-    // (a per-block binary search over the table -- eight dependent global loads in front of every block -- made this launch
-    // 310 us for 0.5 GB; the host uploads the block -> descriptor map next to the table instead)
-    const WinoWDesc d = table[blk2desc[blockIdx.x]];
-    const int idx = ((int)blockIdx.x - d.block0) * 256 + threadIdx.x;
-    if (d.kind == 1) { c3b_wprep_item(d.w, reinterpret_cast<uint4*>(d.uhat), idx, d.Co, d.Ci, d.dgrad, d.MT, d.Mp, d.Kp); return; }
-    if (d.kind == 2) {       // split-operand 1x1 GEMMs: (Mp, Kp) = (padded rows, reduction extent) of this direction
-        g1x3_prep_item(d.w, reinterpret_cast<unsigned short*>(d.uhat), idx, d.dgrad, d.dgrad ? d.Ci : d.Co, d.Mp, d.Kp);
-        return;
-    }
-    if (d.dgrad) wino_weight_one<true>(d.w, d.uhat, idx, d.Co, d.Ci, d.MT, d.Mp, d.Kp, WK);
-    else wino_weight_one<false>(d.w, d.uhat, idx, d.Co, d.Ci, d.MT, d.Mp, d.Kp, WK);
-}
-
 // ------------------------------------------------------------------------------------------------
 // The convolution kernel (design notes at the top of the file).  MR x NR = 16-channel x 16-tile accumulator tiles
 // per wave and Winograd position; gridDim.z > 1 splits the reduction channels into slabs.
 // ------------------------------------------------------------------------------------------------
-constexpr int PSK = 8;                // reduction channels per staged chunk
 constexpr int PSUB = 256;             // floats per (channel, sub-region) plane: >= 240 (4x8 shape); 256 makes the slab pair big enough for the row exchange
 
 struct WinoPsArgs {
@@ -720,88 +653,9 @@ static void wino_ps_pick_region(int TH, int TW, int& RH, int& RW, int& RS) {
     }
 }
 
-static inline int wino_wblocks(int Mp, int Kp) { return (Mp / 16) * ((Kp + 15) / 16); }   // 16 x 16 tiles of wino_weight_one
 static inline size_t wino_uhat_bytes(int Ci, int Co) {
     const size_t a = (size_t)ceil_div(Ci, 32) * 32, b = (size_t)ceil_div(Co, 32) * 32;
     return wino_al256(a * b * 16 * sizeof(float));
-}
-
-// ---- transformed-weight cache ---------------------------------------------------------------------------------------
-// A training step uses every convolution weight twice (forward: G g G^T, data gradient: the same of the rotated,
-// transposed filter) and, in the sequence models, once per frame; the weights only change in the optimiser step.  The
-// host registers the weights of a model once (dc_wino_cache_register), calls dc_wino_cache_refresh at the start of a
-// step -- ONE launch that transforms every variant seen so far instead of one 8 us launch in front of every convolution
-// -- and dc_wino_cache_invalidate when the step's backward is done.  Between the two, wino_launch takes U from the
-// cache; a variant (dgrad, MT) it has not met yet is transformed in place as before and joins the next refresh.
-struct WcVariant { int dgrad, MT, Mp, Kp; float* buf; bool fresh, in_table; int kind; };     // kind 0 Winograd U, 1 bf16 prepared weights, 2 split 1x1 weights
-struct WcEntry { const float* w; int Ci, Co, owner; std::vector<WcVariant> v; };
-// One descriptor table PER OWNER (= per model / Trainer).  A refresh transforms -- and a captured hipGraph replays the
-// transform of -- the owner's own weights only, which the owner keeps alive; weights of another owner never enter its
-// table.  (Round 3 had one table for the whole process: a graph captured, or a refresh skipped because the stream was
-// capturing, while the table still named the weights of a model that had since been collected read freed memory -- a GPU
-// page fault, which the HSA runtime turns into abort() of the process.  See DESIGN.md "The r3s abort".)
-struct WcOwner {
-    int id;
-    bool valid = false, dirty = true;
-    WinoWDesc* table = nullptr;
-    int* b2d = nullptr;
-    int table_n = 0, blocks = 0;
-};
-static std::mutex g_wc_mu;
-static std::vector<WcEntry> g_wc;
-static std::vector<WcOwner> g_wc_owners;
-static int g_wc_next_owner = 1;
-// Device buffers a captured hipGraph may still name in its kernel arguments (descriptor tables that were outgrown, the
-// variant buffers of unregistered weights): parked here, released only by dc_wino_cache_clear().
-static std::vector<void*> g_wc_retired;
-
-static bool wc_capturing(hipStream_t st) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return cs != hipStreamCaptureStatusNone;
-}
-static WcOwner* wc_owner(int id) {
-    for (auto& o : g_wc_owners)
-        if (o.id == id) return &o;
-    return nullptr;
-}
-
-// -> cached U for this launch, or nullptr (then the caller transforms into its workspace).  Nothing is allocated while
-// `st` is being captured (hipMalloc is illegal there): an unseen variant is then transformed per launch, as before.
-static inline size_t wc_variant_bytes(int kind, int MT, int Mp, int Kp) {
-    if (kind == 2) return (size_t)Mp * Kp * 3 * 2 + 256;
-    return kind == 1 ? (size_t)Mp * Kp * 36 * MT * 16 : (size_t)Mp * Kp * 16 * sizeof(float);
-}
-static inline int wc_variant_blocks(int kind, int MT, int Mp, int Kp) {
-    if (kind == 2) return ceil_div(Mp * (Kp / 4), 256);
-    return kind == 1 ? ceil_div(Mp * Kp * 36 * MT, 256) : wino_wblocks(Mp, Kp);
-}
-static const float* wc_lookup_kind(int kind, const float* w, int Ci, int Co, bool dgrad, int MT, int Mp, int Kp, hipStream_t st) {
-    std::lock_guard<std::mutex> lk(g_wc_mu);
-    for (auto& e : g_wc) {
-        if (e.w != w) continue;
-        if (e.Ci != Ci || e.Co != Co) return nullptr;
-        WcOwner* o = wc_owner(e.owner);
-        if (!o) return nullptr;
-        for (auto& v : e.v)
-            if (v.kind == kind && v.dgrad == (int)dgrad && v.MT == MT) return (o->valid && v.fresh) ? v.buf : nullptr;
-        if (wc_capturing(st)) return nullptr;
-        WcVariant v{(int)dgrad, MT, Mp, Kp, nullptr, false, false, kind};
-        if (hipMalloc((void**)&v.buf, wc_variant_bytes(kind, MT, Mp, Kp)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        e.v.push_back(v);
-        o->dirty = true;
-        return nullptr;
-    }
-    return nullptr;
-}
-static const float* wc_lookup(const float* w, int Ci, int Co, bool dgrad, int MT, int Mp, int Kp, hipStream_t st) {
-    return wc_lookup_kind(0, w, Ci, Co, dgrad, MT, Mp, Kp, st);
-}
-const void* wc_lookup_c3b(const float* w, int Ci, int Co, int dgrad, int MT, int nmblk, int nchunks, hipStream_t st) {
-    return wc_lookup_kind(1, w, Ci, Co, dgrad != 0, MT, nmblk, nchunks, st);
-}
-const void* wc_lookup_x3(const float* w, int Ci, int Co, int tr, int Mp, int K, hipStream_t st) {
-    return wc_lookup_kind(2, w, Ci, Co, tr != 0, 0, Mp, K, st);
 }
 
 #ifdef WINO_DIAG
@@ -809,30 +663,6 @@ static unsigned long long* g_wino_diag = nullptr;
 extern "C" void dc_wino_set_diag(void* p) { g_wino_diag = (unsigned long long*)p; }
 unsigned long long* wino_diag_ptr() { return g_wino_diag; }
 #endif
-
-// ---- measurement hook ---------------------------------------------------------------------------------
-namespace {
-struct ConvProf {
-    std::vector<hipEvent_t> e0, e1;
-    int used = 0;
-    double flops = 0.0, exec = 0.0, bytes = 0.0;
-};
-constexpr int NPROF = 8;       // 0 wino_ps, 1 wino_wgrad, 2 c3b_conv (bf16), 3 c3b_wgrad (bf16), 4 1x1 GEMM family, 5 cg_ (3x3 / 2), 6 stem (7x7 / 2), 7 g1x3 (split-operand 1x1 GEMMs)
-ConvProf g_cprof[NPROF];
-int g_cprof_cap = 0, g_cprof_every = 1;
-unsigned g_cprof_seen[NPROF] = {0, 0, 0, 0, 0, 0, 0, 0};
-}  // namespace
-
-hipEvent_t conv_prof_begin(int kind, double algorithmic_flops, double executed_flops, double algorithmic_bytes, hipStream_t st) {
-    ConvProf& d = g_cprof[kind];
-    if (g_cprof_cap == 0 || (g_cprof_seen[kind]++ % (unsigned)g_cprof_every) != 0 || d.used >= g_cprof_cap) return nullptr;
-    d.flops += algorithmic_flops; d.exec += executed_flops; d.bytes += algorithmic_bytes;
-    (void)hipEventRecord(d.e0[d.used], st);
-    return d.e1[d.used++];
-}
-void conv_prof_end(hipEvent_t e, hipStream_t st) {
-    if (e) (void)hipEventRecord(e, st);
-}
 
 // Predicted duration (us) of one wino_ps_kernel launch, used to pick the tile variant v (0: 16 ch x 32 tiles, 4 blocks per
 // CU; 1: 32 x 32, 3 per CU; 2: 32 x 64, 2 per CU) and the reduction split.  Per-block timelines (-DWINO_DIAG=2,
@@ -887,8 +717,17 @@ struct WinoLaunch {
     const dc_bn_fold* bn;                                                // plain launches: BatchNorm folded in (may be null)
 };
 
-// sub-region shape, tile variant and reduction split of a launch: deterministic in the shape (wino_ps_cost below)
-struct WinoPlan { int RH, RW, RS, regs_x, regs_y, nsub, nchunks, MT, G, ksplit; };
+// Everything a launch decides.  wino_plan fills what follows from the shape alone -- the queries (wino_parts, wino_dgrad_split_ok)
+// read it there --, wino_launch_plan the rest from the launch's options.  Deterministic in both (wino_ps_cost above).
+struct WinoPlan {
+    int RH, RW, RS, regs_x, regs_y, nsub, nchunks, MT, G, ksplit;      // sub-region shape, tile variant, reduction split
+    int Mp, Kp, chunks_per_split, mblocks, tblocks;                     // padded GEMM extents, chunks per slab, work items per axis
+    int nparts;                 // partials per channel of the statistics / BatchNorm-backward epilogue: 2 per sub-region slot of the tile blocks
+    size_t b0, b1;              // bytes of the two sources (32-bit buffer offsets)
+    int mode;                   // wino_ps_kernel's MODE
+    bool persist;               // the persistent form: gx < the work items
+    int gx;                     // grid.x (grid.z = ksplit)
+};
 static WinoPlan wino_plan(int B, int K, int M, int Ho, int Wo) {
     WinoPlan p{};
     const int TH = ceil_div(Ho, 2), TW = Wo / 2;
@@ -917,120 +756,120 @@ static WinoPlan wino_plan(int B, int K, int M, int Ho, int Wo) {
             if (fks > 0) p.ksplit = std::max(1, std::min({fks, ks_cap, p.nchunks / 2}));
         }
     }
+    p.Mp = ceil_div(M, p.MT) * p.MT; p.Kp = p.nchunks * PSK;
+    p.chunks_per_split = ceil_div(p.nchunks, p.ksplit);
+    p.mblocks = p.Mp / p.MT; p.tblocks = ceil_div(p.nsub, p.G);
+    p.nparts = 2 * p.tblocks * p.G;
     return p;
 }
 
-static int wino_launch(const WinoLaunch& d, hipStream_t st) {
-    const int K = d.C0 + d.C1, M = d.M, H = d.H, W = d.W;
-    const int Ho = H + 2 * d.P - 2, Wo = W + 2 * d.P - 2;
+// The plan of launch `d`, or every refusal of wino_launch: reads no pointer beyond null tests and calls nothing of HIP, so a
+// refused launch has allocated, enqueued and recorded nothing.
+static int wino_launch_plan(const WinoLaunch& d, WinoPlan& p) {
+    const int K = d.C0 + d.C1, H = d.H, W = d.W;
     const size_t b0 = (size_t)d.B * d.C0 * (H >> d.up0) * (W >> d.up0) * 4, b1 = (size_t)d.B * d.C1 * H * W * 4;
     if (b0 >= 0x7fffffffull || b1 >= 0x7fffffffull) return DC_EINVAL;      // 32-bit buffer offsets
+    p = wino_plan(d.B, K, d.M, H + 2 * d.P - 2, W + 2 * d.P - 2);
+    p.b0 = b0; p.b1 = b1;
+    // BatchNorm fold (plain launches): 1 loader, 2 / 3 data-gradient epilogue; the statistics epilogue rides on mode 0 / 1
+    const dc_bn_fold* bn = d.fused ? nullptr : d.bn;
+    if (bn) {
+        if (bn->groups < 1 || bn->groups > 2 || d.B % bn->groups) return DC_EINVAL;
+        if (bn->bwd_part) {
+            if (p.ksplit > 1 || !bn->bn_x || !bn->bn_mean || (!bn->bn_mask && (!bn->in_scale || !bn->in_shift)) || (bn->bn_mask && ((H * W) & 3)))
+                return DC_EINVAL;
+            p.mode = bn->bn_mask ? 3 : 2;
+        } else if (bn->in_scale) {
+            if (!bn->in_shift || K % PSK) return DC_EINVAL;
+            p.mode = 1;
+        }
+        if (bn->stat_part && (p.ksplit > 1 || p.mode >= 2)) return DC_EINVAL;
+    }
+    if (d.fused && d.split) {
+        if (p.ksplit != 1) return DC_EINVAL;                 // (wino_dgrad_split_ok: the split store exists for the unsplit reduction)
+        p.mode = 4;
+    }
+    // fdiv is exact for dividend * divisor < 2^32: block index by mblocks / tblocks, sub-region index by per_img / regs_x
+    if ((unsigned long long)p.tblocks * p.mblocks * (unsigned)std::max(p.mblocks, p.tblocks) >= 0xffffffffull ||
+        (unsigned long long)(p.nsub + 2 * p.G) * (unsigned)(p.regs_x * p.regs_y) >= 0xffffffffull) return DC_EINVAL;
+    // Persistent form (wino_ps_kernel: one software pipeline over a block's items): only where a launch runs in more than one
+    // round of resident blocks, on an unsplit reduction with an even number (>= 4) of chunks.
+    // (the fold lives in the one-item-per-block form)
+    const int items = p.tblocks * p.mblocks, slots = 256 * (p.MT == 16 ? 4 : (p.G == 1 ? 3 : 2));
+    p.persist = g_wino_persist == 1 && !d.fused && p.ksplit == 1 && p.nchunks >= 4 && (p.nchunks & 1) == 0 && items > slots &&
+                p.mode == 0 && !(bn && bn->stat_part);
+    p.gx = p.persist ? slots : items;
+    return DC_OK;
+}
+
+// The instantiations a launch picks from: rows = {plain MODE 0-3, plain persistent, fused, fused with the split store (MODE 4)},
+// columns = tile variant (MT, G) = (16, 1), (32, 1), (32, 2).
+using WinoPsKernel = void (*)(WinoPsArgs);
+enum { WINO_ROW_PERSIST = 4, WINO_ROW_FUSED = 5, WINO_ROW_FUSED_SPLIT = 6 };
+static const WinoPsKernel g_wino_ps_kernels[7][3] = {
+    {wino_ps_kernel<1, 2, false, false, 0>, wino_ps_kernel<2, 2, false, false, 0>, wino_ps_kernel<2, 4, false, false, 0>},
+    {wino_ps_kernel<1, 2, false, false, 1>, wino_ps_kernel<2, 2, false, false, 1>, wino_ps_kernel<2, 4, false, false, 1>},
+    {wino_ps_kernel<1, 2, false, false, 2>, wino_ps_kernel<2, 2, false, false, 2>, wino_ps_kernel<2, 4, false, false, 2>},
+    {wino_ps_kernel<1, 2, false, false, 3>, wino_ps_kernel<2, 2, false, false, 3>, wino_ps_kernel<2, 4, false, false, 3>},
+    {wino_ps_kernel<1, 2, false, true>, wino_ps_kernel<2, 2, false, true>, wino_ps_kernel<2, 4, false, true>},
+    {wino_ps_kernel<1, 2, true>, wino_ps_kernel<2, 2, true>, wino_ps_kernel<2, 4, true>},
+    {wino_ps_kernel<1, 2, true, false, 4>, wino_ps_kernel<2, 2, true, false, 4>, wino_ps_kernel<2, 4, true, false, 4>},
+};
+
+static int wino_launch(const WinoLaunch& d, hipStream_t st) {
+    WinoPlan p;
+    if (const int rc = wino_launch_plan(d, p)) return rc;
+    const int K = d.C0 + d.C1, M = d.M, H = d.H, W = d.W;
+    const int Ho = H + 2 * d.P - 2, Wo = W + 2 * d.P - 2;
+    const size_t nout = (size_t)d.B * M * Ho * Wo;
+    float* slabs = (float*)((char*)d.ws + wino_uhat_bytes(d.Ci, d.Co));
     WinoPsArgs a{};
     a.x = d.src0; a.x1 = d.src1; a.uhat = (const float*)d.ws; a.bias = d.bias; a.addend = d.fused ? nullptr : d.addend;
     a.B = d.B; a.K = K; a.M = M; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo;
     a.C0 = d.C0; a.up0 = d.up0; a.pad = d.pad; a.P = d.P; a.act = d.act;
-    a.xbytes = (unsigned)b0; a.x1bytes = (unsigned)b1;
-    const WinoPlan pl = wino_plan(d.B, K, M, Ho, Wo);
-    a.RH = pl.RH; a.RW = pl.RW; a.RS = pl.RS;
+    a.xbytes = (unsigned)p.b0; a.x1bytes = (unsigned)p.b1;
+    a.RH = p.RH; a.RW = p.RW; a.RS = p.RS;
     a.SUBS = (2 * a.RH + 2) * a.RS;
-    a.regs_x = pl.regs_x; a.regs_y = pl.regs_y; a.nsub = pl.nsub;
-    a.nchunks = pl.nchunks;
-    const int MT = pl.MT, G = pl.G, ksplit = pl.ksplit;
-    const size_t nout = (size_t)d.B * M * Ho * Wo;
-    // BatchNorm fold (plain launches): 1 loader, 2 / 3 data-gradient epilogue; the statistics epilogue rides on mode 0 / 1
-    int mode = 0;
-    if (d.bn && !d.fused) {
-        const dc_bn_fold* bn = d.bn;
-        if (bn->groups < 1 || bn->groups > 2 || d.B % bn->groups) return DC_EINVAL;
+    a.regs_x = p.regs_x; a.regs_y = p.regs_y; a.nsub = p.nsub;
+    a.nchunks = p.nchunks; a.chunks_per_split = p.chunks_per_split;
+    a.y = p.ksplit > 1 ? slabs : d.out;
+    a.slab_stride = p.ksplit > 1 ? nout : 0;
+    a.tblocks = p.tblocks; a.mblocks = p.mblocks; a.items = p.tblocks * p.mblocks;
+    a.mg_mblocks = fdiv_magic(a.mblocks); a.mg_tblocks = fdiv_magic(a.tblocks); a.mg_per_img = fdiv_magic(a.regs_x * a.regs_y);
+    a.mg_regs_x = fdiv_magic(a.regs_x); a.mg_PR = fdiv_magic(a.RW + 2); a.mg_RW = fdiv_magic(a.RW);
+    a.m_fast = (size_t)d.B * H * W >= (size_t)M * 16 ? 1 : 0;     // x stream (per reduction channel) vs U stream
+    if (const dc_bn_fold* bn = d.fused ? nullptr : d.bn) {
         a.npg = d.B / bn->groups;
         a.in_scale = bn->in_scale; a.in_shift = bn->in_shift;
         if (bn->bwd_part) {
-            if (ksplit > 1 || !bn->bn_x || !bn->bn_mean || (!bn->bn_mask && (!bn->in_scale || !bn->in_shift)) || (bn->bn_mask && ((H * W) & 3)))
-                return DC_EINVAL;
             a.bn_x = bn->bn_x; a.bn_mean = bn->bn_mean; a.bn_mask = (const unsigned long long*)bn->bn_mask; a.bwd_part = bn->bwd_part;
-            a.bwd_nparts = 2 * ceil_div(pl.nsub, G) * G;
-            mode = bn->bn_mask ? 3 : 2;
-        } else if (bn->in_scale) {
-            if (!bn->in_shift || K % PSK) return DC_EINVAL;
-            mode = 1;
+            a.bwd_nparts = p.nparts;
         }
-        if (bn->stat_part) {
-            if (ksplit > 1 || mode >= 2) return DC_EINVAL;
-            a.stat_part = bn->stat_part; a.stat_nparts = 2 * ceil_div(pl.nsub, G) * G;
-        }
+        if (bn->stat_part) { a.stat_part = bn->stat_part; a.stat_nparts = p.nparts; }
     }
-    const int Mp = ceil_div(M, MT) * MT, Kp = a.nchunks * PSK;
-    a.chunks_per_split = ceil_div(a.nchunks, ksplit);
-    float* slabs = (float*)((char*)d.ws + wino_uhat_bytes(d.Ci, d.Co));
-    a.y = ksplit > 1 ? slabs : d.out;
-    a.slab_stride = ksplit > 1 ? nout : 0;
-    if (const float* cached = wc_lookup(d.weight, d.Ci, d.Co, d.dgrad, MT, Mp, Kp, st)) {
-        a.uhat = cached;
-    } else {
-        if (d.dgrad)
-            hipLaunchKernelGGL((wino_weights_kernel<true>), dim3(wino_wblocks(Mp, Kp)), dim3(256), 0, st, d.weight, (float*)d.ws, d.Co, d.Ci, MT, Mp, Kp, PSK);
-        else
-            hipLaunchKernelGGL((wino_weights_kernel<false>), dim3(wino_wblocks(Mp, Kp)), dim3(256), 0, st, d.weight, (float*)d.ws, d.Co, d.Ci, MT, Mp, Kp, PSK);
-        DC_CHECK_LAUNCH();
-    }
+    if (p.mode == 4) { a.out1 = d.out1; a.add0 = d.add0; a.add1 = d.add1; a.split_c0 = d.split_c0; a.split_up = d.split_up; }
 #ifdef WINO_DIAG
     a.diag = g_wino_diag;
 #endif
-    a.tblocks = ceil_div(a.nsub, G); a.mblocks = Mp / MT;
-    a.mg_mblocks = fdiv_magic(a.mblocks); a.mg_tblocks = fdiv_magic(a.tblocks); a.mg_per_img = fdiv_magic(a.regs_x * a.regs_y);
-    a.mg_regs_x = fdiv_magic(a.regs_x); a.mg_PR = fdiv_magic(a.RW + 2); a.mg_RW = fdiv_magic(a.RW);
-    // fdiv is exact for dividend * divisor < 2^32: block index by mblocks / tblocks, sub-region index by per_img / regs_x
-    if ((unsigned long long)a.tblocks * a.mblocks * (unsigned)std::max(a.mblocks, a.tblocks) >= 0xffffffffull ||
-        (unsigned long long)(a.nsub + 2 * G) * (unsigned)(a.regs_x * a.regs_y) >= 0xffffffffull) return DC_EINVAL;
-    a.m_fast = (size_t)d.B * H * W >= (size_t)M * 16 ? 1 : 0;     // x stream (per reduction channel) vs U stream
-    a.items = a.tblocks * a.mblocks;
-    // Persistent form (wino_ps_kernel: one software pipeline over a block's items): only where a launch runs in more than one
-    // round of resident blocks, on an unsplit reduction with an even number (>= 4) of chunks.
-    int gx = a.items;
-    {
-        const int pmode = g_wino_persist;
-        const int bpc = MT == 16 ? 4 : (G == 1 ? 3 : 2), slots = 256 * bpc;
-        if (pmode == 1 && !d.fused && ksplit == 1 && a.nchunks >= 4 && (a.nchunks & 1) == 0 && a.items > slots) gx = slots;
-    }
-    if (mode != 0 || a.stat_part) gx = a.items;           // (the fold lives in the one-item-per-block form)
-    const dim3 grid(gx, 1, ksplit);
-    // SURVEY 8d: algorithmic = 2 MAC of the direct convolution; executed = the 16 Winograd-domain GEMMs incl. tile padding
-    hipEvent_t pe = conv_prof_begin(0, 2.0 * d.B * (double)M * K * 9.0 * H * W,
-                                    2.0 * 16.0 * (double)a.nsub * 32.0 * (double)Mp * Kp,
-                                    (double)b0 + (double)b1 + 4.0 * (double)nout + 36.0 * d.Co * d.Ci, st);
-    if (d.fused && d.split) {
-        if (ksplit != 1) return DC_EINVAL;                 // (wino_dgrad_split_ok: the split store exists for the unsplit reduction)
-        a.out1 = d.out1; a.add0 = d.add0; a.add1 = d.add1; a.split_c0 = d.split_c0; a.split_up = d.split_up;
-        if (MT == 16) hipLaunchKernelGGL((wino_ps_kernel<1, 2, true, false, 4>), grid, dim3(256), 0, st, a);
-        else if (G == 1) hipLaunchKernelGGL((wino_ps_kernel<2, 2, true, false, 4>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((wino_ps_kernel<2, 4, true, false, 4>), grid, dim3(256), 0, st, a);
-    } else if (d.fused) {
-        if (MT == 16) hipLaunchKernelGGL((wino_ps_kernel<1, 2, true>), grid, dim3(256), 0, st, a);
-        else if (G == 1) hipLaunchKernelGGL((wino_ps_kernel<2, 2, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((wino_ps_kernel<2, 4, true>), grid, dim3(256), 0, st, a);
-    } else if (gx < a.items) {
-        if (MT == 16) hipLaunchKernelGGL((wino_ps_kernel<1, 2, false, true>), grid, dim3(256), 0, st, a);
-        else if (G == 1) hipLaunchKernelGGL((wino_ps_kernel<2, 2, false, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((wino_ps_kernel<2, 4, false, true>), grid, dim3(256), 0, st, a);
+    if (const float* cached = wc_lookup(d.weight, d.Ci, d.Co, d.dgrad, p.MT, p.Mp, p.Kp, st)) {
+        a.uhat = cached;
     } else {
-#define WINO_PLAIN(MODE)                                                                                            \
-        do {                                                                                                        \
-            if (MT == 16) hipLaunchKernelGGL((wino_ps_kernel<1, 2, false, false, MODE>), grid, dim3(256), 0, st, a);    \
-            else if (G == 1) hipLaunchKernelGGL((wino_ps_kernel<2, 2, false, false, MODE>), grid, dim3(256), 0, st, a); \
-            else hipLaunchKernelGGL((wino_ps_kernel<2, 4, false, false, MODE>), grid, dim3(256), 0, st, a);             \
-        } while (0)
-        if (mode == 0) WINO_PLAIN(0);
-        else if (mode == 1) WINO_PLAIN(1);
-        else if (mode == 2) WINO_PLAIN(2);
-        else WINO_PLAIN(3);
-#undef WINO_PLAIN
+        hipLaunchKernelGGL((d.dgrad ? wino_weights_kernel<true> : wino_weights_kernel<false>), dim3(wino_wblocks(p.Mp, p.Kp)), dim3(256), 0, st,
+                           d.weight, (float*)d.ws, d.Co, d.Ci, p.MT, p.Mp, p.Kp, PSK);
+        DC_CHECK_LAUNCH();
     }
+    // SURVEY 8d: algorithmic = 2 MAC of the direct convolution; executed = the 16 Winograd-domain GEMMs incl. tile padding
+    hipEvent_t pe = conv_prof_begin(PROF_WINO_PS, 2.0 * d.B * (double)M * K * 9.0 * H * W,
+                                    2.0 * 16.0 * (double)a.nsub * 32.0 * (double)p.Mp * p.Kp,
+                                    (double)p.b0 + (double)p.b1 + 4.0 * (double)nout + 36.0 * d.Co * d.Ci, st);
+    const int row = d.fused ? (p.mode == 4 ? WINO_ROW_FUSED_SPLIT : WINO_ROW_FUSED) : (p.persist ? WINO_ROW_PERSIST : p.mode);
+    hipLaunchKernelGGL(g_wino_ps_kernels[row][p.MT == 16 ? 0 : p.G], dim3(p.gx, 1, p.ksplit), dim3(256), 0, st, a);
     conv_prof_end(pe, st);
     DC_CHECK_LAUNCH();
-    if (ksplit > 1) {
+    if (p.ksplit > 1) {
         const size_t n4 = nout / 4;
         hipLaunchKernelGGL(wino_ysum_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 2048)), dim3(256), 0, st, slabs,
-                           d.out, n4, n4, ksplit, d.fused ? d.bias : (const float*)nullptr, d.fused ? d.act : (int)ACT_NONE,
+                           d.out, n4, n4, p.ksplit, d.fused ? d.bias : (const float*)nullptr, d.fused ? d.act : (int)ACT_NONE,
                            Ho * Wo / 4, M, d.fused ? (const float*)nullptr : d.addend);
         DC_CHECK_LAUNCH();
     }
@@ -1098,196 +937,29 @@ static bool wino_bn_path(int B, int Ci, int Co, int H, int W, bool dgrad) {
 static int wino_run(const float* x, const float* w, float* y, const float* addend, void* ws, int B, int Ci, int Co, int H, int W,
                     bool dgrad, hipStream_t st, const dc_bn_fold* bn = nullptr) {
     if (!x || !w || !y || !ws || B <= 0 || Ci <= 0 || Co <= 0 || H < 1 || W < 2 || (W & 1)) return DC_EINVAL;
-    if (wino_bn_active(bn)) {
-        if (!wino_bn_path(B, Ci, Co, H, W, dgrad)) return DC_EINVAL;
-        WinoLaunch d{};
-        d.src0 = x; d.C0 = dgrad ? Co : Ci; d.weight = w; d.Co = Co; d.Ci = Ci; d.dgrad = dgrad; d.act = ACT_NONE; d.pad = PAD_ZERO;
-        d.P = 1; d.out = y; d.ws = ws; d.B = B; d.H = H; d.W = W; d.M = dgrad ? Ci : Co; d.fused = false; d.addend = addend; d.bn = bn;
-        return wino_launch(d, st);
-    }
+    const bool fold = wino_bn_active(bn);
+    if (fold && !wino_bn_path(B, Ci, Co, H, W, dgrad)) return DC_EINVAL;
     // reduced-precision policy: direct implicit GEMM on the bf16 matrix cores (conv_bf16.hip; the data gradient of a
     // zero-padded convolution is the convolution with the rotated, transposed filter)
-    if (matrix_precision() == DC_PREC_BF16 && c3b_eligible(dgrad ? Co : Ci, 0, 0, H, W, 1)) {
+    if (!fold && matrix_precision() == DC_PREC_BF16 && c3b_eligible(dgrad ? Co : Ci, 0, 0, H, W, 1)) {
         return c3b_conv(x, dgrad ? Co : Ci, 0, nullptr, 0, w, Co, Ci, dgrad ? 1 : 0, 0, nullptr, y, ws, B, H, W, ACT_NONE, PAD_ZERO, 1, st, addend);
     }
     // F(4x4,3x3) (wino4.hip): opt-in (dc_set_wino_f4) for maps its tile groups cover well -- measured against this file's
     // F(2x2,3x3) in tests/test_wino_gpu.py and tools/bench_wino.py; DESIGN 4a has the verdict
-    if (g_wino_f4 && wino4_eligible(B, dgrad ? Co : Ci, dgrad ? Ci : Co, H, W) && wino4_utilisation(H, W) >= 0.85) {
+    if (!fold && g_wino_f4 && wino4_eligible(B, dgrad ? Co : Ci, dgrad ? Ci : Co, H, W) && wino4_utilisation(H, W) >= 0.85) {
         float* slabs = (float*)((char*)ws + std::max(wino_uhat_bytes(Ci, Co), wino4_uhat_bytes(Ci, Co)));
         return wino4_launch(x, w, nullptr, y, addend, ws, slabs, B, Ci, Co, H, W, dgrad, st);
     }
     WinoLaunch d{};
     d.src0 = x; d.C0 = dgrad ? Co : Ci; d.weight = w; d.Co = Co; d.Ci = Ci; d.dgrad = dgrad; d.act = ACT_NONE; d.pad = PAD_ZERO;
     d.P = 1; d.out = y; d.ws = ws; d.B = B; d.H = H; d.W = W; d.M = dgrad ? Ci : Co; d.fused = false; d.addend = addend;
+    d.bn = fold ? bn : nullptr;                  // (the fold rides on this launch alone: wino_bn_path)
     return wino_launch(d, st);
 }
 
 }  // namespace dc
 
 using namespace dc;
-
-extern "C" int dc_conv_profile_enable(int max_launches, int every) {
-    g_cprof_every = every > 0 ? every : 1;
-    for (auto& v : g_cprof_seen) v = 0;
-    for (auto& d : g_cprof) {
-        for (auto e : d.e0) (void)hipEventDestroy(e);
-        for (auto e : d.e1) (void)hipEventDestroy(e);
-        d.e0.clear(); d.e1.clear(); d.used = 0; d.flops = d.exec = d.bytes = 0.0;
-    }
-    g_cprof_cap = 0;
-    if (max_launches <= 0) return DC_OK;
-    for (auto& d : g_cprof) {
-        d.e0.resize(max_launches); d.e1.resize(max_launches);
-        for (int i = 0; i < max_launches; ++i)
-            if (hipEventCreate(&d.e0[i]) != hipSuccess || hipEventCreate(&d.e1[i]) != hipSuccess) return DC_ELAUNCH;
-    }
-    g_cprof_cap = max_launches;
-    return DC_OK;
-}
-
-extern "C" int dc_conv_profile_collect(int kind, double* ms, double* algorithmic_flops, double* executed_flops,
-                                       double* algorithmic_bytes, int* launches) {
-    if (kind < 0 || kind >= NPROF) return DC_EINVAL;
-    ConvProf& d = g_cprof[kind];
-    double tot = 0.0;
-    for (int i = 0; i < d.used; ++i) {
-        float t = 0.f;
-        if (hipEventSynchronize(d.e1[i]) != hipSuccess || hipEventElapsedTime(&t, d.e0[i], d.e1[i]) != hipSuccess) return DC_ELAUNCH;
-        tot += t;
-    }
-    if (ms) *ms = tot;
-    if (algorithmic_flops) *algorithmic_flops = d.flops;
-    if (executed_flops) *executed_flops = d.exec;
-    if (algorithmic_bytes) *algorithmic_bytes = d.bytes;
-    if (launches) *launches = d.used;
-    d.used = 0; d.flops = d.exec = d.bytes = 0.0;
-    return DC_OK;
-}
-
-extern "C" int dc_wino_cache_new_owner(void) {
-    std::lock_guard<std::mutex> lk(g_wc_mu);
-    WcOwner o;
-    o.id = g_wc_next_owner++;
-    g_wc_owners.push_back(o);
-    return o.id;
-}
-
-extern "C" int dc_wino_cache_register(int owner, const float* weight, int Ci, int Co) {
-    if (!weight || Ci <= 0 || Co <= 0) return DC_EINVAL;
-    std::lock_guard<std::mutex> lk(g_wc_mu);
-    WcOwner* o = wc_owner(owner);
-    if (!o) return DC_EINVAL;
-    for (auto& e : g_wc)
-        if (e.w == weight) return (e.Ci == Ci && e.Co == Co && e.owner == owner) ? DC_OK : DC_EINVAL;
-    g_wc.push_back(WcEntry{weight, Ci, Co, owner, {}});
-    o->dirty = true;
-    return DC_OK;
-}
-
-// Forget an owner and every weight it registered.  Its tables and variant buffers are parked, not freed: a captured
-// hipGraph of the owner may still name them.
-extern "C" int dc_wino_cache_release_owner(int owner) {
-    std::lock_guard<std::mutex> lk(g_wc_mu);
-    for (size_t i = 0; i < g_wc.size();) {
-        if (g_wc[i].owner == owner) {
-            for (auto& v : g_wc[i].v)
-                if (v.buf) g_wc_retired.push_back(v.buf);
-            g_wc.erase(g_wc.begin() + i);
-        } else {
-            ++i;
-        }
-    }
-    for (size_t i = 0; i < g_wc_owners.size(); ++i)
-        if (g_wc_owners[i].id == owner) {
-            if (g_wc_owners[i].table) g_wc_retired.push_back(g_wc_owners[i].table);
-            if (g_wc_owners[i].b2d) g_wc_retired.push_back(g_wc_owners[i].b2d);
-            g_wc_owners.erase(g_wc_owners.begin() + i);
-            break;
-        }
-    return DC_OK;
-}
-
-extern "C" int dc_wino_cache_refresh(int owner, void* stream) {
-    std::lock_guard<std::mutex> lk(g_wc_mu);
-    hipStream_t st = (hipStream_t)stream;
-    WcOwner* o = wc_owner(owner);
-    if (!o) return DC_EINVAL;
-    // The descriptor upload allocates, synchronises and copies: none of it is legal on a capturing stream.  A capture that
-    // meets a dirty registry replays the owner's table as it stands (variants outside it keep transforming per launch);
-    // every weight the table names belongs to this owner and lives as long as it does.
-    if (o->dirty && !wc_capturing(st)) {
-        std::vector<WinoWDesc> host;
-        std::vector<int> b2d;
-        int blocks = 0;
-        for (auto& e : g_wc) {
-            if (e.owner != owner) continue;
-            for (auto& v : e.v) {
-                const int nb = wc_variant_blocks(v.kind, v.MT, v.Mp, v.Kp);
-                b2d.insert(b2d.end(), nb, (int)host.size());
-                host.push_back(WinoWDesc{e.w, v.buf, e.Co, e.Ci, v.MT, v.Mp, v.Kp, v.dgrad, blocks, v.kind});
-                blocks += nb;
-            }
-        }
-        // A rebuilt table goes to fresh memory and the old one is retired, not freed or rewritten: a captured graph holds
-        // the old address and block count and must keep seeing the old contents.
-        if (o->b2d) g_wc_retired.push_back(o->b2d);
-        if (o->table) g_wc_retired.push_back(o->table);
-        o->b2d = nullptr; o->table = nullptr; o->table_n = o->blocks = 0;
-        if (blocks > 0 && hipMalloc((void**)&o->b2d, sizeof(int) * blocks) != hipSuccess) { o->b2d = nullptr; return DC_ELAUNCH; }
-        if (!host.empty() && hipMalloc((void**)&o->table, sizeof(WinoWDesc) * host.size()) != hipSuccess) { o->table = nullptr; return DC_ELAUNCH; }
-        // synchronous upload (the descriptor list only changes while the variants of a model are still being met)
-        if (!host.empty() && hipStreamSynchronize(st) != hipSuccess) return DC_ELAUNCH;
-        if (!host.empty() && hipMemcpy(o->table, host.data(), sizeof(WinoWDesc) * host.size(), hipMemcpyHostToDevice) != hipSuccess) return DC_ELAUNCH;
-        if (!b2d.empty() && hipMemcpy(o->b2d, b2d.data(), sizeof(int) * b2d.size(), hipMemcpyHostToDevice) != hipSuccess) return DC_ELAUNCH;
-        o->table_n = (int)host.size(); o->blocks = blocks; o->dirty = false;
-        for (auto& e : g_wc)
-            if (e.owner == owner)
-                for (auto& v : e.v) v.in_table = true;
-    }
-    if (o->table_n > 0 && o->blocks > 0) {
-        hipLaunchKernelGGL(wino_weights_batched_kernel, dim3(o->blocks), dim3(256), 0, st, (const WinoWDesc*)o->table, (const int*)o->b2d, PSK);
-        DC_CHECK_LAUNCH();
-    }
-    for (auto& e : g_wc)
-        if (e.owner == owner)
-            for (auto& v : e.v) v.fresh = v.in_table;
-    o->valid = true;
-    return DC_OK;
-}
-
-extern "C" int dc_wino_cache_invalidate(int owner) {
-    std::lock_guard<std::mutex> lk(g_wc_mu);
-    WcOwner* o = wc_owner(owner);
-    if (!o) return DC_EINVAL;
-    o->valid = false;
-    return DC_OK;
-}
-
-extern "C" int dc_wino_cache_clear(void) {
-    std::lock_guard<std::mutex> lk(g_wc_mu);
-    int rc = DC_OK;
-    if (hipDeviceSynchronize() != hipSuccess) rc = DC_ELAUNCH;
-    for (auto& e : g_wc)
-        for (auto& v : e.v)
-            if (v.buf && hipFree(v.buf) != hipSuccess) rc = DC_ELAUNCH;
-    g_wc.clear();
-    for (void* q : g_wc_retired)
-        if (hipFree(q) != hipSuccess) rc = DC_ELAUNCH;
-    g_wc_retired.clear();
-    for (auto& o : g_wc_owners) {
-        if (o.table && hipFree(o.table) != hipSuccess) rc = DC_ELAUNCH;
-        if (o.b2d && hipFree(o.b2d) != hipSuccess) rc = DC_ELAUNCH;
-    }
-    g_wc_owners.clear();
-    return rc;
-}
-
-extern "C" int dc_wino_cache_variants(void) {
-    std::lock_guard<std::mutex> lk(g_wc_mu);
-    int n = 0;
-    for (auto& e : g_wc) n += (int)e.v.size();
-    return n;
-}
 
 extern "C" size_t dc_wino3x3_workspace(int B, int Ci, int Co, int H, int W) {
     if (B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0) return 0;
@@ -1334,7 +1006,7 @@ static int wino_parts(int B, int K, int M, int H, int W, int groups, bool dgrad,
     const WinoPlan p = wino_plan(B, K, M, H, W);
     if (p.ksplit > 1) return 0;
     if (ppg) *ppg = 2 * p.regs_x * p.regs_y * (B / groups);
-    return 2 * ceil_div(p.nsub, p.G) * p.G;
+    return p.nparts;
 }
 extern "C" int dc_wino3x3_stat_parts(int B, int Ci, int Co, int H, int W, int groups, int* ppg) {
     return wino_parts(B, Ci, Co, H, W, groups, false, Ci, Co, ppg);

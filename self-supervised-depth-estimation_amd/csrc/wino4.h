@@ -1,11 +1,11 @@
-// Internal interface of the Winograd F(4x4,3x3) kernel (wino4.hip), used by wino.hip's dispatch and weight cache.
+// Internal interface of the Winograd F(4x4,3x3) kernel (wino4.hip), used by wino.hip's dispatch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
 namespace dc {
 
-constexpr int W4_MT = 116;     // tile-layout code of the F(4x4,3x3) transformed weights in the weight cache (wino.hip: WcVariant.MT)
+constexpr int W4_MT = 116;     // tile-layout code of the F(4x4,3x3) transformed weights in the weight cache (weight_cache.hip: WcVariant.MT)
 
 bool wino4_eligible(int B, int K, int M, int H, int W);
 double wino4_utilisation(int H, int W);                 // useful / covered output pixels of the tile-group cover of an H x W map

@@ -28,7 +28,7 @@
 //     vector instructions and 21 LDS reads per step behind its own 36 MFMAs (1152 cycles of matrix pipe).
 //   * K-split over gridDim.z with fixed-order slab sums for launches that would not fill the chip (wino_ysum_kernel).
 #include "dc_common.h"
-#include "wino.h"
+#include "conv_prof.h"
 #include "wino4.h"
 
 #include <algorithm>
@@ -339,7 +339,7 @@ int wino4_launch(const float* x, const float* weight, const float* cached_uhat, 
         a.uhat = (const float*)ws;
     }
     // algorithmic = 2 MAC of the direct convolution; executed = the 36 Winograd-domain GEMMs incl. tile padding
-    hipEvent_t pe = conv_prof_begin(0, 2.0 * B * (double)M * K * 9.0 * H * W, 2.0 * 36.0 * (double)a.tblocks * 64.0 * (double)Mp * Kp,
+    hipEvent_t pe = conv_prof_begin(PROF_WINO_PS, 2.0 * B * (double)M * K * 9.0 * H * W, 2.0 * 36.0 * (double)a.tblocks * 64.0 * (double)Mp * Kp,
                                     4.0 * ((double)B * K * H * W + (double)nout) + 36.0 * Co * Ci, st);
     const size_t lds = ((size_t)32 * a.PLANE + 2 * W4_USTEP) * sizeof(float);
     static const bool lds_ok = hipFuncSetAttribute((const void*)wino4_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -24,6 +24,7 @@
 // Requires even W; H arbitrary.
 #include "dc_common.h"
 #include "conv_bf16.h"
+#include "conv_prof.h"
 #include "wino.h"
 
 #include <algorithm>
@@ -454,7 +455,20 @@ __global__ __launch_bounds__(64 * WR_GROUPS) void wino_wreduce_col_kernel(const 
     out[6 + c] = h + q[3];
 }
 
-static inline size_t wg_lds(int mr, int ng) { return (size_t)ng * (2 * 16 * mr * WG_GPS + 2 * WG_KT * WG_XPS) * sizeof(float); }
+static constexpr size_t wg_lds(int mr, int ng) { return (size_t)ng * (2 * 16 * mr * WG_GPS + 2 * WG_KT * WG_XPS) * sizeof(float); }
+
+// The instantiations a launch picks from, each with its block size and dynamic LDS: rows = {plain, plain with the input's BatchNorm
+// re-formed for one group (BNIN 1), for two (BNIN 2), fused}, columns = (mr, ng) = (4, 1), (4, 2), (2, 1); entry 3 row + column.
+struct WgKernel { void (*fn)(WinoWgArgs); int threads; size_t lds; };
+template <bool FUSED, int MR, int NG, int BNIN = 0>
+static constexpr WgKernel wg_kernel() { return {wino_wgrad_kernel<FUSED, MR, NG, BNIN>, 256 * NG, wg_lds(MR, NG)}; }
+enum { WG_ROW_FUSED = 3 };
+static const WgKernel g_wg_kernels[4 * 3] = {
+    wg_kernel<false, 4, 1>(), wg_kernel<false, 4, 2>(), wg_kernel<false, 2, 1>(),
+    wg_kernel<false, 4, 1, 1>(), wg_kernel<false, 4, 2, 1>(), wg_kernel<false, 2, 1, 1>(),
+    wg_kernel<false, 4, 1, 2>(), wg_kernel<false, 4, 2, 2>(), wg_kernel<false, 2, 1, 2>(),
+    wg_kernel<true, 4, 1>(), wg_kernel<true, 4, 2>(), wg_kernel<true, 2, 1>(),
+};
 
 struct WgPlan { int RH, RW, GRS, XRS, regs_x, regs_y, nsub, mblocks, kblocks, splits, mr, ng; };
 
@@ -504,14 +518,12 @@ static int wg_launch(const float* x0, int C0, int up0, const float* x1, int C1, 
     a.RH = p.RH; a.RW = p.RW; a.GRS = p.GRS; a.XRS = p.XRS;
     a.regs_x = p.regs_x; a.regs_y = p.regs_y; a.nsub = p.nsub; a.splits = p.splits; a.kblocks = p.kblocks; a.mblocks = p.mblocks;
     a.xbytes = (unsigned)b0; a.x1bytes = (unsigned)b1; a.gbytes = (unsigned)gb;
-    {
-        const int nmk_ = p.mblocks * p.kblocks, per_img = p.regs_x * p.regs_y;
-        a.mg_nmk = fdiv_magic(nmk_); a.mg_kblocks = fdiv_magic(p.kblocks); a.mg_RW = fdiv_magic(p.RW); a.mg_XPR = fdiv_magic(p.RW + 2);
-        a.mg_per_img = fdiv_magic(per_img); a.mg_regs_x = fdiv_magic(p.regs_x);
-        // exact while dividend * divisor < 2^32: block index by nmk, sub-region index by per_img
-        if ((unsigned long long)p.splits * nmk_ * (unsigned)nmk_ >= 0xffffffffull || (unsigned long long)p.nsub * (unsigned)per_img >= 0xffffffffull)
-            return DC_EINVAL;
-    }
+    const int nmk = p.mblocks * p.kblocks, per_img = p.regs_x * p.regs_y;
+    a.mg_nmk = fdiv_magic(nmk); a.mg_kblocks = fdiv_magic(p.kblocks); a.mg_RW = fdiv_magic(p.RW); a.mg_XPR = fdiv_magic(p.RW + 2);
+    a.mg_per_img = fdiv_magic(per_img); a.mg_regs_x = fdiv_magic(p.regs_x);
+    // exact while dividend * divisor < 2^32: block index by nmk, sub-region index by per_img
+    if ((unsigned long long)p.splits * nmk * (unsigned)nmk >= 0xffffffffull || (unsigned long long)p.nsub * (unsigned)per_img >= 0xffffffffull)
+        return DC_EINVAL;
 #ifdef WINO_DIAG
     a.diag = wino_diag_ptr();
 #endif
@@ -520,38 +532,15 @@ static int wg_launch(const float* x0, int C0, int up0, const float* x1, int C1, 
         if (fused || !bn->in_shift || bn->groups < 1 || bn->groups > 2 || B % bn->groups) return DC_EINVAL;
         a.in_scale = bn->in_scale; a.in_shift = bn->in_shift; a.npg = B / bn->groups;
     }
-    const int nmk = p.mblocks * p.kblocks;
-    hipEvent_t pe = conv_prof_begin(1, 2.0 * B * (double)Co * Ci * 9.0 * H * W,
+    // the dynamic-LDS limit of all twelve on the first launch of any (a later capture then meets no attribute call)
+    static const bool attr = std::all_of(std::begin(g_wg_kernels), std::end(g_wg_kernels),
+                                         [](const WgKernel& k) { return set_max_dynamic_lds(k.fn, k.lds); });
+    if (!attr) return DC_ELAUNCH;
+    const WgKernel& k = g_wg_kernels[3 * (fused ? WG_ROW_FUSED : (bnin ? bn->groups : 0)) + (p.mr == 4 ? p.ng - 1 : 2)];
+    hipEvent_t pe = conv_prof_begin(PROF_WINO_WGRAD, 2.0 * B * (double)Co * Ci * 9.0 * H * W,
                                     2.0 * 16.0 * (double)p.nsub * 16.0 * (double)(p.mblocks * 16 * p.mr) * (p.kblocks * WG_KT),
                                     (double)b0 + (double)b1 + (double)gb + 36.0 * Co * Ci, st);
-    static const bool attr = set_max_dynamic_lds(wino_wgrad_kernel<true, 4, 1>, wg_lds(4, 1)) && set_max_dynamic_lds(wino_wgrad_kernel<false, 4, 1>, wg_lds(4, 1)) &&
-                             set_max_dynamic_lds(wino_wgrad_kernel<true, 4, 2>, wg_lds(4, 2)) && set_max_dynamic_lds(wino_wgrad_kernel<false, 4, 2>, wg_lds(4, 2)) &&
-                             set_max_dynamic_lds(wino_wgrad_kernel<true, 2, 1>, wg_lds(2, 1)) && set_max_dynamic_lds(wino_wgrad_kernel<false, 2, 1>, wg_lds(2, 1)) &&
-                             set_max_dynamic_lds(wino_wgrad_kernel<false, 4, 1, 1>, wg_lds(4, 1)) && set_max_dynamic_lds(wino_wgrad_kernel<false, 4, 2, 1>, wg_lds(4, 2)) &&
-                             set_max_dynamic_lds(wino_wgrad_kernel<false, 2, 1, 1>, wg_lds(2, 1)) &&
-                             set_max_dynamic_lds(wino_wgrad_kernel<false, 4, 1, 2>, wg_lds(4, 1)) && set_max_dynamic_lds(wino_wgrad_kernel<false, 4, 2, 2>, wg_lds(4, 2)) &&
-                             set_max_dynamic_lds(wino_wgrad_kernel<false, 2, 1, 2>, wg_lds(2, 1));
-    if (!attr) return DC_ELAUNCH;
-    const dim3 grid(p.splits * nmk);
-    const size_t lds = wg_lds(p.mr, p.ng);
-    if (bnin && bn->groups == 1) {
-        if (p.mr == 4 && p.ng == 2) hipLaunchKernelGGL((wino_wgrad_kernel<false, 4, 2, 1>), grid, dim3(512), lds, st, a);
-        else if (p.mr == 4) hipLaunchKernelGGL((wino_wgrad_kernel<false, 4, 1, 1>), grid, dim3(256), lds, st, a);
-        else hipLaunchKernelGGL((wino_wgrad_kernel<false, 2, 1, 1>), grid, dim3(256), lds, st, a);
-    } else if (bnin) {
-        if (p.mr == 4 && p.ng == 2) hipLaunchKernelGGL((wino_wgrad_kernel<false, 4, 2, 2>), grid, dim3(512), lds, st, a);
-        else if (p.mr == 4) hipLaunchKernelGGL((wino_wgrad_kernel<false, 4, 1, 2>), grid, dim3(256), lds, st, a);
-        else hipLaunchKernelGGL((wino_wgrad_kernel<false, 2, 1, 2>), grid, dim3(256), lds, st, a);
-    } else if (p.mr == 4 && p.ng == 2) {
-        if (fused) hipLaunchKernelGGL((wino_wgrad_kernel<true, 4, 2>), grid, dim3(512), lds, st, a);
-        else hipLaunchKernelGGL((wino_wgrad_kernel<false, 4, 2>), grid, dim3(512), lds, st, a);
-    } else if (p.mr == 4) {
-        if (fused) hipLaunchKernelGGL((wino_wgrad_kernel<true, 4, 1>), grid, dim3(256), lds, st, a);
-        else hipLaunchKernelGGL((wino_wgrad_kernel<false, 4, 1>), grid, dim3(256), lds, st, a);
-    } else {
-        if (fused) hipLaunchKernelGGL((wino_wgrad_kernel<true, 2, 1>), grid, dim3(256), lds, st, a);
-        else hipLaunchKernelGGL((wino_wgrad_kernel<false, 2, 1>), grid, dim3(256), lds, st, a);
-    }
+    hipLaunchKernelGGL(k.fn, dim3(p.splits * nmk), dim3(k.threads), k.lds, st, a);
     conv_prof_end(pe, st);
     DC_CHECK_LAUNCH();
     const int rblocks = nmk * p.mr * WG_KR * 4;

@@ -199,6 +199,8 @@ REFUSALS = [
     ("odd W", "fwd", (2, 8, 8, 4, 5), 1, ("in_scale", "in_shift")),
     ("a split reduction with stat_part", "fwd", WC.SPLIT_REDUCTION, 1, ("stat_part",)),
     ("a split reduction with bwd_part", "dgrad", WC.SPLIT_REDUCTION, 1, ("in_scale", "in_shift", "bn_x", "bn_mean", "bwd_part")),
+    # (300000 sub-regions of one tile each: the block index leaves the range in which the kernel's multiply-high division is exact)
+    ("sub-region index beyond the exact-division range", "fwd", (300000, 1, 1, 2, 2), 1, ("stat_part",)),
 ]
 
 

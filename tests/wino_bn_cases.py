@@ -37,7 +37,7 @@ TENSOR_TOL = 2e-5             # max|hip - fp64| <= 2e-5 max|fp64|: the bound tes
 E32_MAX = 1e-4
 EINVAL = -1
 
-# csrc/wino.hip, csrc/wino_wgrad.hip, csrc/conv_bf16.h
+# csrc/wino.hip, csrc/weight_cache.h, csrc/wino_wgrad.hip, csrc/conv_bf16.h
 PSK = 8                                              # reduction channels per staged chunk (wino_ps_kernel)
 PS_REGIONS = [(4, 8), (2, 16), (3, 10), (8, 4)]      # wino_ps_pick_region: 32-tile sub-regions (RH, RW)
 WG_REGIONS = [(2, 8), (4, 4), (3, 5)]                # wg_plan: 16-tile sub-regions
