@@ -630,6 +630,37 @@ int dc_attnconv_bwd(const dc_attn_map* x, const dc_attn_params* p, const dc_attn
                     const float* dx_add, const dc_attn_map* dres, float* dparams, void* ws, int B, int C, int H, int W, int relu_in,
                     int relu_res, void* stream);
 
+/* ------------------------------------------------------------------ f3 7x7 local self-attention of the attention encoder */
+/* The attention arithmetic of AttentionConv as ResnetEncoderAttention instantiates it (networks/attention.py:29-52, identical to
+ * networks/resnet_encoder_attention.py:43-66; built with kernel_size 7, padding 3, stride 1, bias=False at :150-153), AFTER the
+ * three 1x1 convolutions (those are dc_pointwise_* GEMMs):
+ *   logit_t[c] = q[c] * (k_t[c] + rel_t[c]),  t = (dy, dx) in 7 x 7;  rel_t[c] = rel_h[c][dy] for c < C/2, rel_w[c - C/2][dx] otherwise
+ *   y[c]       = sum_t softmax_t(logit)[c] * v_t[c],      lse[c] = logsumexp_t(logit)[c]
+ * k_t, v_t are k, v at pixel + (dy - 3, dx - 3); a tap outside the image carries k = v = 0 and STILL takes part in the softmax
+ * with logit q * rel (the reference pads x, and the convolutions have no bias).  The reference's `groups` has no effect on the
+ * arithmetic (the product is per channel, the sum runs over taps only): the op is 49-tap attention per channel plane.
+ * q, k, v: fp32, element (b, c, y, x) at ptr[b * batch_stride + (c * H + y) * W + x] -- each with its own batch stride in elements
+ * (>= C*H*W), so slices of a wider tensor are read in place.  rel_h, rel_w: (C/2, 7) row-major.  y, lse, gy, dq, dk, dv: plain
+ * contiguous (B,C,H,W).  fp32 throughout, softmax around the explicit maximum (forward) / the saved lse (backward).
+ * dc_sasa_fwd writes y and, unless lse is NULL (inference), lse.  dc_sasa_bwd writes dq, dk, dv (every element once) and
+ * drel_h, drel_w (C/2, 7), overwritten:
+ *   a_t[p] = exp(logit_t[p] - lse[p]),  dl_t[p] = a_t[p] gy[p] (v_t[p] - y[p]),   p' = p + o_t
+ *   dq[p] = sum_t dl_t[p] (k_t[p] + rel_t)   dk[p'] = sum_t dl_t[p' - o_t] q[p' - o_t]   dv[p'] = sum_t a_t[p' - o_t] gy[p' - o_t]
+ *   drel_h[c][dy] = sum_{b,p,dx} dl_t q (c < C/2),   drel_w[c][dx] = sum_{b,p,dy} dl_t q (c >= C/2)      (padded taps included)
+ * No atomics: per-block partial rows in ws (dc_sasa_bwd_workspace bytes, 0 for a refused shape), summed in fixed order by a second
+ * kernel; two runs are bitwise equal.  All launches go on `stream`; no host synchronisation, no allocation.
+ * DC_EINVAL before any launch (nothing written): C odd or < 2, B / H / W <= 0, a required pointer NULL, B*C*H*W >= 2^31, a batch
+ * stride < C*H*W.
+ * dc_sasa_plan: the launch geometry of a shape (the same for both directions) -- plan[0..4] = tile height, tile width, tiles
+ * along x, tiles along y, channel planes per block (small maps: a block takes several planes); DC_EINVAL for a refused shape. */
+int dc_sasa_plan(int B, int C, int H, int W, int* plan);
+int dc_sasa_fwd(const float* q, const float* k, const float* v, long long q_bstride, long long k_bstride, long long v_bstride,
+                const float* rel_h, const float* rel_w, float* y, float* lse, int B, int C, int H, int W, void* stream);
+size_t dc_sasa_bwd_workspace(int B, int C, int H, int W);
+int dc_sasa_bwd(const float* q, const float* k, const float* v, long long q_bstride, long long k_bstride, long long v_bstride,
+                const float* rel_h, const float* rel_w, const float* y, const float* lse, const float* gy, float* dq, float* dk,
+                float* dv, float* drel_h, float* drel_w, void* ws, int B, int C, int H, int W, void* stream);
+
 /* ------------------------------------------------------------------ f2 ConvGRU temporal fusion (gru_version v5) */
 /* networks/rnn.py:101-143 `ConvGRUCell`: the two 3x3 convolutions are dc_conv3x3_fwd calls with (x, h) / (x, r*h) as the two
  * concatenated sources, zero padding, bias, sigmoid / tanh epilogue; these entry points are the gate arithmetic between

@@ -102,7 +102,7 @@ _lib = None
 
 
 def _sig(lib):
-    i, f, p, z = c_int, c_float, c_void_p, c_size_t
+    i, f, p, z, ll = c_int, c_float, c_void_p, c_size_t, ctypes.c_longlong
     S = {
         "dc_version": (c_char_p, []),
         "dc_arch": (c_char_p, []),
@@ -263,6 +263,10 @@ def _sig(lib):
         "dc_attnconv_bwd_workspace": (z, [i, i, i, i]),
         "dc_attnconv_bwd": (i, [POINTER(AttnMap), POINTER(AttnParams), POINTER(AttnMap), p, POINTER(AttnMap), p, POINTER(AttnMap), p,
                                 p, i, i, i, i, i, i, p]),
+        "dc_sasa_plan": (i, [i, i, i, i, POINTER(c_int)]),
+        "dc_sasa_fwd": (i, [p, p, p, ll, ll, ll, p, p, p, p, i, i, i, i, p]),
+        "dc_sasa_bwd_workspace": (z, [i, i, i, i]),
+        "dc_sasa_bwd": (i, [p, p, p, ll, ll, ll, p, p, p, p, p, p, p, p, p, p, p, i, i, i, i, p]),
         "dc_profile_enable": (i, [i]),
         "dc_profile_collect": (i, [POINTER(c_double), POINTER(c_int), POINTER(c_double), POINTER(c_int), POINTER(c_double),
                                    POINTER(c_double)]),

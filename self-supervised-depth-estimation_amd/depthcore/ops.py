@@ -1805,6 +1805,66 @@ def residual_attention_unit(srcs, kinds, params1, params2):
 
 
 # ----------------------------------------------------------------------------------------------
+# f3 7x7 local self-attention of the attention encoder    (reference networks/attention.py:29-52, behind the 1x1 convolutions)
+# ----------------------------------------------------------------------------------------------
+def _plane_strided(t):
+    """(tensor, batch stride in elements) for dc_sasa_*: `t` itself when it is a fp32 device tensor whose images are dense
+    (C,H,W) blocks -- a channel slice of a wider tensor included -- and a contiguous copy otherwise."""
+    if not t.is_cuda:
+        raise _lib.DepthcoreError("depthcore ops need device tensors (got %s); there is no CPU path" % t.device)
+    if t.dtype != torch.float32:
+        raise _lib.DepthcoreError("expected %s, got %s" % (torch.float32, t.dtype))
+    B, C, H, W = t.shape
+    if t.stride()[1:] != (H * W, W, 1) or (B > 1 and t.stride(0) < C * H * W):
+        t = t.contiguous()
+    return t, (t.stride(0) if B > 1 else C * H * W)
+
+
+class _LocalAttention7(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, rel_h, rel_w):
+        L = _lib.lib()
+        (qq, qs), (kk, ks), (vv, vs) = (_plane_strided(t.detach()) for t in (q, k, v))
+        B, C, H, W = qq.shape
+        rh, rw = _c(rel_h.detach()), _c(rel_w.detach())
+        if kk.shape != qq.shape or vv.shape != qq.shape or C % 2 or rh.numel() != (C // 2) * 7 or rw.numel() != (C // 2) * 7:
+            raise _lib.DepthcoreError("local_attention7: q %s, k %s, v %s must agree, C even, rel_h / rel_w (C/2, 7) (got %s, %s)"
+                                      % (tuple(qq.shape), tuple(kk.shape), tuple(vv.shape), tuple(rh.shape), tuple(rw.shape)))
+        need = any(ctx.needs_input_grad)
+        y = torch.empty(B, C, H, W, dtype=torch.float32, device=qq.device)
+        lse = torch.empty_like(y) if need else None           # (no_grad: the inference path saves nothing)
+        check(L.dc_sasa_fwd(qq.data_ptr(), kk.data_ptr(), vv.data_ptr(), qs, ks, vs, ptr(rh), ptr(rw), ptr(y), ptr(lse), B, C, H, W,
+                            stream(qq)), "dc_sasa_fwd")
+        if need:
+            ctx.save_for_backward(qq, kk, vv, rh, rw, y, lse)
+            ctx.strides = (qs, ks, vs)
+            ctx.slots = (_slot(rel_h), _slot(rel_w))
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        L = _lib.lib()
+        qq, kk, vv, rh, rw, y, lse = ctx.saved_tensors
+        qs, ks, vs = ctx.strides
+        B, C, H, W = y.shape
+        g_c = _c(gy)
+        dq, dk, dv = torch.empty_like(y), torch.empty_like(y), torch.empty_like(y)
+        drh, drw = _grad_dst(ctx.slots[0], rh), _grad_dst(ctx.slots[1], rw)      # (C/2 * 7 contiguous values in the parameters' shapes)
+        ws = torch.empty(L.dc_sasa_bwd_workspace(B, C, H, W), dtype=torch.uint8, device=y.device)
+        check(L.dc_sasa_bwd(qq.data_ptr(), kk.data_ptr(), vv.data_ptr(), qs, ks, vs, ptr(rh), ptr(rw), ptr(y), ptr(lse), ptr(g_c),
+                            ptr(dq), ptr(dk), ptr(dv), ptr(drh), ptr(drw), ws.data_ptr(), B, C, H, W, stream(y)), "dc_sasa_bwd")
+        return dq, dk, dv, drh, drw
+
+
+def local_attention7(q, k, v, rel_h, rel_w):
+    """y[c] = sum_t softmax_t(q[c] (k_t[c] + rel_t[c])) v_t[c] over the 7x7 window (zero padding 3, stride 1) of (B,C,H,W) fp32
+    maps; rel_t = rel_h[c, dy] for c < C/2 and rel_w[c - C/2, dx] otherwise (rel_h, rel_w: C/2 * 7 values in any shape).  One fused
+    kernel forward (it saves y and the log-sum-exp; under no_grad nothing), one plus a small reduction backward.  q, k, v may be
+    channel slices of one wider tensor: they are read in place."""
+    return _LocalAttention7.apply(q, k, v, rel_h, rel_w)
+
+
+# ----------------------------------------------------------------------------------------------
 # f2 ConvGRU cell gate arithmetic + sequence residual        (reference networks/rnn.py:101-143, trainer_gru.py:637-639)
 # ----------------------------------------------------------------------------------------------
 class _GruRH(torch.autograd.Function):

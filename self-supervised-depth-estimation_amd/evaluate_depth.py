@@ -10,7 +10,10 @@ and writes the outputs.  Where it differs from the reference:
     the half-pixel sampling of cv2.resize(INTER_LINEAR) when upsampling, not its bits (cv2 is not a dependency);
   - saved disparities (--save_pred_disps) are fp32 also with --post_process (the reference saves fp64 there);
   - gt_depths.npz is read only when something is scored, so --no_eval and the benchmark split need none;
-  - the encoder is ResnetEncoder(--num_layers) (the reference builds a resnet18 whatever the option says);
+  - the encoder is ResnetEncoder(--num_layers) (the reference builds a resnet18 whatever the option says), or
+    ResnetEncoderAttention(--num_layers) with --model rn_encoder_with_attention / rn_fusion (trainer_dpt.py:78-92); weights
+    saved from the other class are refused.  load_networks() without a `model` option (test_simple.py) takes the class the
+    checkpoint was saved from;
   - the Fusion_v3 and ConvGRU front-ends are not evaluated (NotImplementedError).
 """
 import json
@@ -76,7 +79,15 @@ def load_networks(opt, device):
         raise FileNotFoundError("Cannot find a folder at {}".format(folder))
     print("-> Loading weights from {}".format(folder))
     encoder_dict = torch.load(os.path.join(folder, "encoder.pth"), map_location="cpu")
-    encoder = networks.ResnetEncoder(opt.num_layers, False)
+    # the encoder class: what --model names (as trainer.py builds it); a caller without that option (test_simple.py) gets the
+    # class the checkpoint was saved from.  A checkpoint of the other class is an error, never a silently dropped layer.
+    saved_cls = networks.ResnetEncoderAttention if any(k.startswith("atten") for k in encoder_dict) else networks.ResnetEncoder
+    cls = networks.depth_encoder_class(opt.model) if hasattr(opt, "model") else saved_cls
+    if cls is not saved_cls:
+        raise ValueError("--model {!r} builds {} but {} holds a {} (its keys {} atten1..4.*): pass the --model the weights were "
+                         "trained with".format(opt.model, cls.__name__, os.path.join(folder, "encoder.pth"), saved_cls.__name__,
+                                               "include" if saved_cls is networks.ResnetEncoderAttention else "lack"))
+    encoder = cls(opt.num_layers, False)
     decoder = networks.DepthDecoder(encoder.num_ch_enc)
     model_dict = encoder.state_dict()
     encoder.load_state_dict({k: v for k, v in encoder_dict.items() if k in model_dict})

@@ -378,6 +378,11 @@ class ResnetEncoder(nn.Module):
         x = (input_image - 0.45) / 0.225
         return self._trunk(_conv(e.conv1, x), bn_groups)
 
+    def _after_stage(self, n, t):
+        """What becomes feature map n (and the next stage's input) from the output of layer n: the output itself here;
+        ResnetEncoderAttention applies its attention layer."""
+        return t
+
     def _trunk(self, x, bn_groups):
         """everything behind conv1; x = conv1((input - 0.45) / 0.225)"""
         e = self.encoder
@@ -394,10 +399,10 @@ class ResnetEncoder(nn.Module):
             self.features.append(t)
             return t
         feature(x)
-        feature(e.layer1(_ops.maxpool3x3s2(x, _ops.skip_of(x)) if x.is_cuda else e.maxpool(x)))
-        feature(e.layer2(self.features[-1]))
-        feature(e.layer3(self.features[-1]))
-        self.features.append(e.layer4(self.features[-1]))
+        feature(self._after_stage(1, e.layer1(_ops.maxpool3x3s2(x, _ops.skip_of(x)) if x.is_cuda else e.maxpool(x))))
+        feature(self._after_stage(2, e.layer2(self.features[-1])))
+        feature(self._after_stage(3, e.layer3(self.features[-1])))
+        self.features.append(self._after_stage(4, e.layer4(self.features[-1])))
         if self.training:   # nn.BatchNorm2d bookkeeping, one multi-tensor launch instead of one per layer
             if self._nbt is None:
                 self._nbt = [m.num_batches_tracked for m in e.modules() if isinstance(m, nn.BatchNorm2d)]

@@ -18,6 +18,8 @@ through the depth encoder + decoder and fused by `networks.Fusion_v3` (BASELINE 
 `opt.gru = "v5"` switches it to trainer_gru.py:595-644 (`run_gru_v5`, BASELINE configs[3]): a batch is ONE sequence of
 `opt.len_sequence` frames (dict keys carry the sequence index: ("color", f, s, j), ("K", s, j)), the encoder features of the
 sequence pass through `networks.ConvGRUBlocks_v5`, and the loss runs on the sequence stacked along the batch.
+`opt.model = "rn_encoder_with_attention"` (or `"rn_fusion"` together with `opt.fusion = "v3"`) builds the depth encoder as
+`networks.ResnetEncoderAttention` (trainer_dpt.py:78-92); every other value, the default included, builds `ResnetEncoder`.
 """
 import contextlib
 import json
@@ -117,7 +119,13 @@ class Trainer:
                     os.path.isfile(os.path.join(os.path.expanduser(folder), "{}.pth".format(name))):
                 return False                                     # overwritten by load_model() below
             return True                                          # -> ResnetEncoder raises: no download, no silent scratch
-        self.models["encoder"] = networks.ResnetEncoder(self.opt.num_layers, _init_for("encoder"))
+        # trainer_dpt.py:78-92: --model rn_encoder_with_attention / rn_fusion put the self-attention encoder under the depth
+        # decoder (the pose networks stay as they are); every other value builds the plain encoder
+        model = getattr(self.opt, "model", None)
+        if model == "rn_fusion" and self.opt.fusion != "v3":
+            raise ValueError("model 'rn_fusion' is the self-attention encoder under the Fusion_v3 front-end: it needs fusion='v3' "
+                             "(use model 'rn_encoder_with_attention' for the encoder alone)")
+        self.models["encoder"] = networks.depth_encoder_class(model)(self.opt.num_layers, _init_for("encoder"))
         self.models["depth"] = networks.DepthDecoder(self.models["encoder"].num_ch_enc, self.opt.scales)
         if self.opt.fusion:                                      # trainer_fusion_v3.py:74
             self.models["fusion"] = networks.Fusion_v3(attention=not self.opt.disable_attention)
