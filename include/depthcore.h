@@ -791,6 +791,30 @@ int dc_data_jitter_to_tensor(const uint8_t* img, float* color, float* color_aug,
  *     callers whose data loader produced the planar tensors (the reference's).  `out` 16-byte aligned. */
 int dc_data_to_rgbx(const uint8_t* img, float* out, int n_img, int npix, void* stream);
 int dc_pack_rgbx(const float* x, float* out, int n_img, int npix, void* stream);
+/* Ragged batch: n_img images of DIFFERENT sizes in one packed uint8 buffer (a shuffled KITTI batch mixes five native sizes),
+ * one launch per pass, the arithmetic of dc_data_resize_axis per image (byte-equal results).
+ *   dc_ragged_img: one image of one pass -- (Hi, Wi, 3) at byte src_off of `src`, written at byte dst_off of `dst` as
+ *     (Hi, out_size, 3) (axis 1, width; `flip` != 0 mirrors the source row first) or (out_size, Wi, 3) (axis 0, height; flip
+ *     must be 0).  `table` indexes `tab`, or is < 0 for an image that already has out_size along the axis: it is copied (axis 1:
+ *     or mirrored) in the same launch, where Pillow skips the pass.
+ *   dc_ragged_table: one dc_resample_table result (in_size -> out_size, the same out_size for the whole launch) inside the
+ *     concatenated arrays: bounds at bounds[bounds_off ..] (2 * out_size ints), kk at kk[kk_off ..] (out_size * ksize ints).
+ * desc / tab / bounds are passed twice, as HOST and as DEVICE copies of the same bytes: the host copies are checked before any
+ * launch -- DC_EINVAL (nothing launched, nothing written) for an image that reaches outside `src` (src_bytes) or `dst`
+ * (dst_bytes), a table whose in_size is not the image's or whose ksize is not dc_resample_ksize's, a tap outside [0, in_size),
+ * a table outside bounds_len / kk_len (in ints), flip on axis 0.  The kernels read only the device copies.  Distinct images
+ * must not overlap in `dst` (not checked).  One launch on `stream`; no allocation, no synchronisation. */
+typedef struct dc_ragged_img {
+    long long src_off, dst_off;
+    int Hi, Wi, table, flip;
+} dc_ragged_img;
+typedef struct dc_ragged_table {
+    int bounds_off, kk_off, ksize, in_size;
+} dc_ragged_table;
+int dc_data_ragged_resize_axis(const uint8_t* src, size_t src_bytes, uint8_t* dst, size_t dst_bytes, const dc_ragged_img* desc_host,
+                               const dc_ragged_img* desc_dev, int n_img, int out_size, int axis, const dc_ragged_table* tab_host,
+                               const dc_ragged_table* tab_dev, int n_tab, const int* bounds_host, const int* bounds_dev,
+                               size_t bounds_len, const int* kk_dev, size_t kk_len, void* stream);
 
 /* ------------------------------------------------------------------ depth metrics (validation)
  * Trainer.compute_depth_losses (trainer.py:624-652, called at :248 and from val at :460) and the KITTI Eigen protocol of

@@ -77,6 +77,73 @@ __global__ __launch_bounds__(256) void data_flip_kernel(const uint8_t* __restric
     o[2] = p[2];
 }
 
+// ---- ragged batch: images of DIFFERENT sizes in one packed buffer, one launch per pass -----------------------------------
+// A shuffled KITTI batch mixes five native sizes; each image carries its own descriptor (offsets, size, coefficient table)
+// and the arithmetic of the two kernels above is repeated per image.  Every descriptor load and every early return is
+// block-uniform (blockIdx only).  table < 0: that image already has the target size along the axis -> plain (x: or
+// mirrored) copy in the same launch, where Pillow skips the pass.
+// width pass: (Hi, Wi) at src_off -> (Hi, Wo) at dst_off; grid (ceil(Wo / 256), max Hi, n)
+__global__ __launch_bounds__(256) void data_ragged_x_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                           const dc_ragged_img* __restrict__ desc, int Wo,
+                                                           const dc_ragged_table* __restrict__ tab, const int* __restrict__ bounds_all,
+                                                           const int* __restrict__ kk_all) {
+    const dc_ragged_img d = desc[blockIdx.z];
+    const int y = blockIdx.y, xo = blockIdx.x * 256 + threadIdx.x;
+    if (y >= d.Hi) return;   // rows above this image's own height
+    if (xo >= Wo) return;
+    const uint8_t* row = src + (size_t)d.src_off + (size_t)y * d.Wi * 3;
+    uint8_t* o = dst + (size_t)d.dst_off + ((size_t)y * Wo + xo) * 3;
+    const bool mirror = d.flip != 0;
+    if (d.table < 0) {       // Wi == Wo (checked on the host)
+        const uint8_t* p = row + (size_t)(mirror ? Wo - 1 - xo : xo) * 3;
+        o[0] = p[0];
+        o[1] = p[1];
+        o[2] = p[2];
+        return;
+    }
+    const dc_ragged_table t = tab[d.table];
+    const int* bounds = bounds_all + t.bounds_off;
+    const int x0 = bounds[2 * xo], n = bounds[2 * xo + 1];
+    const int* k = kk_all + t.kk_off + (size_t)xo * t.ksize;
+    int a0 = 1 << (kPrecisionBits - 1), a1 = a0, a2 = a0;
+    for (int j = 0; j < n; ++j) {
+        const int sx = mirror ? d.Wi - 1 - (x0 + j) : x0 + j;
+        const uint8_t* p = row + (size_t)sx * 3;
+        const int c = k[j];
+        a0 += c * p[0];
+        a1 += c * p[1];
+        a2 += c * p[2];
+    }
+    o[0] = clip8(a0);
+    o[1] = clip8(a1);
+    o[2] = clip8(a2);
+}
+
+// height pass: (Hi, Wi) at src_off -> (Ho, Wi) at dst_off, one thread per output byte; grid (ceil(max Wi * 3 / 256), Ho, n)
+__global__ __launch_bounds__(256) void data_ragged_y_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                           const dc_ragged_img* __restrict__ desc, int Ho,
+                                                           const dc_ragged_table* __restrict__ tab, const int* __restrict__ bounds_all,
+                                                           const int* __restrict__ kk_all) {
+    const dc_ragged_img d = desc[blockIdx.z];
+    const int yo = blockIdx.y, xb = blockIdx.x * 256 + threadIdx.x;
+    const int row = d.Wi * 3;
+    if (xb >= row) return;
+    const uint8_t* base = src + (size_t)d.src_off + xb;
+    uint8_t* o = dst + (size_t)d.dst_off + (size_t)yo * row + xb;
+    if (d.table < 0) {       // Hi == Ho (checked on the host)
+        *o = base[(size_t)yo * row];
+        return;
+    }
+    const dc_ragged_table t = tab[d.table];
+    const int* bounds = bounds_all + t.bounds_off;
+    const int y0 = bounds[2 * yo], n = bounds[2 * yo + 1];
+    const int* k = kk_all + t.kk_off + (size_t)yo * t.ksize;
+    const uint8_t* p = base + (size_t)y0 * row;
+    int a = 1 << (kPrecisionBits - 1);
+    for (int j = 0; j < n; ++j) a += k[j] * p[(size_t)j * row];
+    *o = clip8(a);
+}
+
 // ------------------------------------------------------------------------------------------------------------- ColorJitter
 __device__ __forceinline__ int luma(int r, int g, int b) { return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16; }   // Convert.c L24
 
@@ -349,6 +416,49 @@ extern "C" int dc_data_resize_axis(const uint8_t* src, uint8_t* dst, int n_img, 
         hipLaunchKernelGGL(data_resize_y_kernel, dim3((row + 255) / 256, out_size, n_img), dim3(256), 0, (hipStream_t)stream, src, dst, Hi,
                            out_size, row, bounds, kk, ksize);
     }
+    DC_CHECK_LAUNCH();
+    return DC_OK;
+}
+
+extern "C" int dc_data_ragged_resize_axis(const uint8_t* src, size_t src_bytes, uint8_t* dst, size_t dst_bytes, const dc_ragged_img* desc_host,
+                                          const dc_ragged_img* desc_dev, int n_img, int out_size, int axis, const dc_ragged_table* tab_host,
+                                          const dc_ragged_table* tab_dev, int n_tab, const int* bounds_host, const int* bounds_dev,
+                                          size_t bounds_len, const int* kk_dev, size_t kk_len, void* stream) {
+    if (!src || !dst || src == dst || !desc_host || !desc_dev || n_img <= 0 || n_img > 65535 || out_size <= 0 || out_size > 65535 ||
+        (axis != 0 && axis != 1) || n_tab < 0)
+        return DC_EINVAL;
+    if (n_tab > 0 && (!tab_host || !tab_dev || !bounds_host || !bounds_dev || !kk_dev)) return DC_EINVAL;
+    // every table: the size of its axis, and every tap inside [0, in_size) and inside the concatenated arrays
+    for (int t = 0; t < n_tab; ++t) {
+        const dc_ragged_table& T = tab_host[t];
+        if (T.in_size <= 0 || T.in_size > 65535 || T.ksize != dc_resample_ksize(T.in_size, out_size) || T.bounds_off < 0 || T.kk_off < 0 ||
+            (size_t)T.bounds_off + 2 * (size_t)out_size > bounds_len || (size_t)T.kk_off + (size_t)out_size * T.ksize > kk_len)
+            return DC_EINVAL;
+        const int* b = bounds_host + T.bounds_off;
+        for (int o = 0; o < out_size; ++o)
+            if (b[2 * o] < 0 || b[2 * o + 1] < 0 || b[2 * o + 1] > T.ksize || b[2 * o] + b[2 * o + 1] > T.in_size) return DC_EINVAL;
+    }
+    // every image: inside both buffers, and its table is the one of its own size
+    int max_h = 0, max_w = 0;
+    for (int i = 0; i < n_img; ++i) {
+        const dc_ragged_img& d = desc_host[i];
+        if (d.Hi <= 0 || d.Hi > 65535 || d.Wi <= 0 || d.Wi > 65535 || d.src_off < 0 || d.dst_off < 0) return DC_EINVAL;
+        if (axis == 0 && d.flip) return DC_EINVAL;   // the mirror belongs to the width pass
+        const size_t in_bytes = (size_t)d.Hi * d.Wi * 3;
+        const size_t out_bytes = axis ? (size_t)d.Hi * out_size * 3 : (size_t)out_size * d.Wi * 3;
+        if ((size_t)d.src_off > src_bytes || in_bytes > src_bytes - (size_t)d.src_off) return DC_EINVAL;
+        if ((size_t)d.dst_off > dst_bytes || out_bytes > dst_bytes - (size_t)d.dst_off) return DC_EINVAL;
+        const int in_size = axis ? d.Wi : d.Hi;
+        if (d.table < 0 ? in_size != out_size : (d.table >= n_tab || tab_host[d.table].in_size != in_size)) return DC_EINVAL;
+        max_h = std::max(max_h, d.Hi);
+        max_w = std::max(max_w, d.Wi);
+    }
+    if (axis == 1)
+        hipLaunchKernelGGL(data_ragged_x_kernel, dim3((out_size + 255) / 256, max_h, n_img), dim3(256), 0, (hipStream_t)stream, src, dst,
+                           desc_dev, out_size, tab_dev, bounds_dev, kk_dev);
+    else
+        hipLaunchKernelGGL(data_ragged_y_kernel, dim3((max_w * 3 + 255) / 256, out_size, n_img), dim3(256), 0, (hipStream_t)stream, src, dst,
+                           desc_dev, out_size, tab_dev, bounds_dev, kk_dev);
     DC_CHECK_LAUNCH();
     return DC_OK;
 }

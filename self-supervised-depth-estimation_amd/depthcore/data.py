@@ -5,6 +5,9 @@ The reference runs this in `num_workers` CPU processes per item with Pillow / to
 uploaded once as uint8 HWC and everything downstream (flip, Lanczos pyramid, ColorJitter, ToTensor) happens in HBM through
 libdepthcore's `dc_data_*` entry points, byte-exact with the CPU pipeline (tests/test_data_gpu.py, oracle/data_ref.py).
 Random draws stay on the host (`sample_item`), in the reference's order.  There is no CPU path.
+`GpuPreprocessor.__call__` takes a batch of one native size; `GpuPreprocessor.ragged` takes items of different native sizes
+packed back to back (what a shuffled KITTI loader delivers, depthcore/loader.py) and makes scale 0 with two launches over
+the whole batch (`dc_data_ragged_resize_axis`, tests/test_data_ragged_gpu.py).
 """
 import random
 
@@ -16,6 +19,9 @@ from ._lib import check, stream
 
 BRIGHTNESS, CONTRAST, SATURATION, HUE = 0, 1, 2, 3
 NO_OP = -1
+# mirror of `dc_ragged_img` (include/depthcore.h)
+RAGGED_IMG = np.dtype([("src_off", np.int64), ("dst_off", np.int64), ("Hi", np.int32), ("Wi", np.int32), ("table", np.int32),
+                       ("flip", np.int32)])
 
 
 def resample_table(in_size, out_size):
@@ -60,6 +66,7 @@ class GpuPreprocessor:
         if self.device.type != "cuda":
             raise _lib.DepthcoreError("GpuPreprocessor needs a GPU device; there is no CPU path")
         self._tables = {}
+        self._ragged = {}
 
     def _table(self, in_size, out_size):
         key = (in_size, out_size)
@@ -148,6 +155,110 @@ class GpuPreprocessor:
             if s == 0:
                 # the photometric kernels gather from pixel-interleaved RGBx: written here, once per item, from the same uint8
                 # level (same division by 255 -> the same values as ("color", f, 0)) instead of repacked in every training step
+                packed = torch.empty((n, h, w, 4), dtype=torch.float32, device=img.device)
+                check(L.dc_data_to_rgbx(img.data_ptr(), packed.data_ptr(), n, h * w, stream(img)), "dc_data_to_rgbx")
+                packed = packed.view(Fn, B, h, w, 4)
+                for i, f in enumerate(self.frame_idxs):
+                    out[("color_packed", f, 0)] = packed[i]
+        return out
+
+    # ---- ragged batches: items of different native sizes (a shuffled KITTI batch mixes five) --------------------------------
+    def _ragged_tables(self, axis, in_sizes, out_size):
+        """The concatenated Lanczos tables of one axis (mirror of dc_ragged_table), grown when a new native size shows up:
+        -> (index of each size or -1 for out_size itself, host tab, device tab, host bounds, device bounds, device kk)."""
+        store = self._ragged.setdefault((axis, out_size), {"index": {}, "tab": [], "bounds": [], "kk": [], "dev": None})
+        for size in in_sizes:
+            if size != out_size and size not in store["index"]:
+                bounds, kk = resample_table(size, out_size)
+                store["index"][size] = len(store["tab"])
+                store["tab"].append((sum(b.size for b in store["bounds"]), sum(k.size for k in store["kk"]), kk.shape[1], size))
+                store["bounds"].append(bounds.reshape(-1))
+                store["kk"].append(kk.reshape(-1))
+                store["dev"] = None
+        if store["dev"] is None and store["tab"]:
+            tab = np.array(store["tab"], np.int32)
+            bounds, kk = np.concatenate(store["bounds"]), np.concatenate(store["kk"])
+            store["dev"] = (tab, torch.from_numpy(tab).to(self.device), bounds, torch.from_numpy(bounds).to(self.device),
+                            torch.from_numpy(kk).to(self.device))
+        return [store["index"].get(size, -1) for size in in_sizes], store["dev"]
+
+    def _ragged_pass(self, src, dst, desc, out_size, axis, tables):
+        L = _lib.lib()
+        desc_dev = torch.from_numpy(desc.view(np.uint8)).to(self.device)
+        tab = tab_dev = bounds = bounds_dev = kk_dev = None
+        if tables is not None:
+            tab, tab_dev, bounds, bounds_dev, kk_dev = tables
+        check(L.dc_data_ragged_resize_axis(
+            src.data_ptr(), src.numel(), dst.data_ptr(), dst.numel(), desc.ctypes.data, desc_dev.data_ptr(), len(desc), out_size, axis,
+            tab.ctypes.data if tab is not None else None, tab_dev.data_ptr() if tab is not None else None,
+            len(tab) if tab is not None else 0, bounds.ctypes.data if tab is not None else None,
+            bounds_dev.data_ptr() if tab is not None else None, bounds.size if tab is not None else 0,
+            kk_dev.data_ptr() if tab is not None else None, kk_dev.numel() if tab is not None else 0, stream(src)),
+            "dc_data_ragged_resize_axis")
+
+    def ragged(self, packed_u8, sizes, flips=None, jitters=None):
+        """`__call__` for a batch whose items have DIFFERENT native sizes.  packed_u8: 1-D uint8 device tensor holding the
+        decoded frames back to back, frame-major like `__call__` (image f * B + b is frame f of item b, (Hn_b, Wn_b, 3));
+        sizes: B pairs (Hn, Wn) -- the frames of an item share its size (they come from one drive); flips / jitters as in
+        `__call__`.  Scale 0 comes from two launches over the whole batch (dc_data_ragged_resize_axis, width then height);
+        the further scales and everything behind the resize run on the uniform path.  -> the dict of `__call__`."""
+        Fn, B = len(self.frame_idxs), len(sizes)
+        if packed_u8.dtype != torch.uint8 or packed_u8.dim() != 1 or not packed_u8.is_cuda or not packed_u8.is_contiguous():
+            raise _lib.DepthcoreError("packed frames must be a contiguous 1-D uint8 device tensor")
+        if B == 0 or (flips is not None and len(flips) != B) or (jitters is not None and len(jitters) != B):
+            raise _lib.DepthcoreError("sizes, flips and jitters have one entry per item")
+        n, h, w = Fn * B, self.height, self.width
+        xtab, xdev = self._ragged_tables(1, [int(s[1]) for s in sizes], w)
+        ytab, ydev = self._ragged_tables(0, [int(s[0]) for s in sizes], h)
+        dx, dy = np.zeros(n, RAGGED_IMG), np.zeros(n, RAGGED_IMG)
+        src_off = mid_off = 0
+        for f in range(Fn):
+            for b, (hn, wn) in enumerate(sizes):
+                i = f * B + b
+                dx[i] = (src_off, mid_off, hn, wn, xtab[b], 1 if flips is not None and flips[b] else 0)
+                dy[i] = (mid_off, i * h * w * 3, hn, w, ytab[b], 0)
+                src_off += int(hn) * int(wn) * 3
+                mid_off += int(hn) * w * 3
+        mid = torch.empty(mid_off, dtype=torch.uint8, device=packed_u8.device)
+        img = torch.empty((n, h, w, 3), dtype=torch.uint8, device=packed_u8.device)
+        self._ragged_pass(packed_u8, mid, dx, w, 1, xdev)
+        self._ragged_pass(mid, img, dy, h, 0, ydev)
+        return self._levels(img, Fn, B, jitters)
+
+    def _levels(self, img, Fn, B, jitters):
+        """Scale 0 (n, height, width, 3) uint8, already flipped -> every key of `__call__` (scales 1.. resized from it)."""
+        L = _lib.lib()
+        n = Fn * B
+        steps = params = sums = None
+        if jitters is not None and any(j is not None for j in jitters):
+            st_h = np.full((n, 4), NO_OP, np.int32)
+            pr_h = np.zeros((n, 4), np.float32)
+            for b, j in enumerate(jitters):
+                if j is None:
+                    continue
+                order, factors = j
+                for k, op in enumerate(order):
+                    st_h[b::B, k] = op
+                    pr_h[b::B, k] = float(hue_shift(factors[op])) if op == HUE else factors[op]
+            steps = torch.from_numpy(st_h).to(img.device)
+            params = torch.from_numpy(pr_h).to(img.device)
+            sums = torch.empty(n, dtype=torch.int64, device=img.device)
+        out = {}
+        for s in range(self.num_scales):
+            h, w = self.height // (2 ** s), self.width // (2 ** s)
+            if s:
+                img = self._resize(img, h, w, None)
+            color = torch.empty((n, 3, h, w), dtype=torch.float32, device=img.device)
+            aug = torch.empty_like(color) if steps is not None else None
+            check(L.dc_data_jitter_to_tensor(img.data_ptr(), color.data_ptr(), aug.data_ptr() if aug is not None else None, n, h * w,
+                                             steps.data_ptr() if aug is not None else None, params.data_ptr() if aug is not None else None,
+                                             sums.data_ptr() if aug is not None else None, stream(img)), "dc_data_jitter_to_tensor")
+            color = color.view(Fn, B, 3, h, w)
+            color_aug = aug.view(Fn, B, 3, h, w) if aug is not None else color
+            for i, f in enumerate(self.frame_idxs):
+                out[("color", f, s)] = color[i]
+                out[("color_aug", f, s)] = color_aug[i]
+            if s == 0:
                 packed = torch.empty((n, h, w, 4), dtype=torch.float32, device=img.device)
                 check(L.dc_data_to_rgbx(img.data_ptr(), packed.data_ptr(), n, h * w, stream(img)), "dc_data_to_rgbx")
                 packed = packed.view(Fn, B, h, w, 4)

@@ -1,0 +1,225 @@
+"""Batches for the training loop (reference trainer.py:152-164: two shuffled `DataLoader`s with drop_last).
+
+The reference's loader forks `num_workers` processes that each decode, resize, jitter and convert one item with Pillow.
+Here the only host work is DECODING: the frames of a batch are decoded on a thread pool (PIL releases the GIL while it
+decodes) straight into a pinned staging buffer, one host-to-device copy moves them, and the data step runs on the device
+over the ragged batch (GpuPreprocessor.ragged: a shuffled KITTI batch mixes five native sizes).  No worker processes:
+nothing forks after the GPU has been initialised.
+
+Two halves:
+  * host -- `plan` (which items, which random draws) and `decode_batch` (files -> one packed uint8 buffer): no GPU needed;
+  * device -- upload + data step on a side stream of the loader's own, handed to the consumer's stream with an event.
+Every GPU call is made by the consuming thread (the pool threads only decode), so a training step that is being captured
+into a hipGraph never meets a launch or an allocation of another thread.
+
+Sampling is a function of (seed, epoch) alone: one `random.Random` gives the permutation and then, in item order, the
+draws of `sample_item` -- batches do not depend on thread timing.  `rank` / `world_size` take a strided shard of the same
+permutation, the same number of steps on every rank.
+"""
+import collections
+import random
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+from PIL import Image
+
+from .data import GpuPreprocessor, sample_item
+
+MAX_THREADS = 16      # decode threads: bounded by the option and by this, never by the machine's core count
+
+
+def epoch_rng(seed, epoch):
+    """The generator of one epoch's permutation and draws."""
+    return random.Random("depthcore.loader/%d/%d" % (seed, epoch))
+
+
+try:
+    import pyarrow
+except ImportError:         # optional: only the way the decoded pixels leave Pillow depends on it
+    pyarrow = None
+
+
+def _pixels(rgb):
+    """(H, W, 3) uint8 view or copy of a loaded RGB image.  Pillow keeps RGB as four bytes per pixel; `np.asarray` repacks
+    them through `tobytes`, chunk by chunk under the interpreter lock -- with a dozen decode threads that starves the thread
+    launching the training step (and the step starves the decoders).  Pillow's Arrow export hands out its own memory
+    instead, and the 4 -> 3 byte copy into the staging buffer is then one numpy loop that runs without the lock."""
+    if pyarrow is not None and hasattr(rgb, "__arrow_c_array__"):
+        try:
+            flat = pyarrow.array(rgb).flatten().to_numpy(zero_copy_only=True)
+            return flat.reshape(rgb.height, rgb.width, 4)[:, :, :3]
+        except (ValueError, pyarrow.ArrowException):      # an image spread over several memory blocks has no zero-copy export
+            pass
+    return np.asarray(rgb)
+
+
+def _decode_into(path, dst):
+    with open(path, "rb") as f:
+        with Image.open(f) as img:
+            rgb = img if img.mode == "RGB" else img.convert("RGB")
+            if (rgb.height, rgb.width) != dst.shape[:2]:
+                raise ValueError("%s is %dx%d, its item's first frame %dx%d: the frames of an item share one size"
+                                 % (path, rgb.height, rgb.width, dst.shape[0], dst.shape[1]))
+            rgb.load()
+            dst[...] = _pixels(rgb)
+
+
+def _image_size(path):
+    with open(path, "rb") as f:
+        with Image.open(f) as img:          # reads the header only
+            return img.height, img.width
+
+
+class BatchLoader:
+    def __init__(self, dataset, batch_size, num_workers=12, device="cuda", seed=0, shuffle=True, rank=0, world_size=1, prefetch=2):
+        self.dataset, self.batch_size = dataset, int(batch_size)
+        self.is_train = bool(dataset.is_train)
+        self.seed, self.shuffle, self.rank, self.world_size = int(seed), bool(shuffle), int(rank), int(world_size)
+        self.prefetch = max(0, min(int(prefetch), 2))        # two staging buffers: at most two batches ahead
+        self.device = torch.device(device)
+        self.epoch = 0
+        self.threads = max(1, min(int(num_workers), MAX_THREADS))
+        self._pool = None
+        self._pre = self._intrinsics = self._side = None
+        self._staging, self._copied = [None, None], [None, None]
+        self._jobs = collections.deque()
+
+    # ------------------------------------------------------------------------------------------------------------ host half
+    def __len__(self):
+        """Steps per epoch: the same on every rank (drop_last over the rank's shard)."""
+        return len(self.dataset) // self.world_size // self.batch_size
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def plan(self, epoch=None):
+        """The epoch's batches: [(indices, draws)], draws = one `sample_item` result per item, in item order."""
+        rng = epoch_rng(self.seed, self.epoch if epoch is None else epoch)
+        order = list(range(len(self.dataset)))
+        if self.shuffle:
+            rng.shuffle(order)
+        order = order[self.rank::self.world_size][:len(self) * self.batch_size]
+        batches = []
+        for i in range(len(self)):
+            indices = order[i * self.batch_size:(i + 1) * self.batch_size]
+            batches.append((indices, [sample_item(self.is_train, rng) for _ in indices]))
+        return batches
+
+    def _pool_(self):
+        if self._pool is None:
+            self._pool = ThreadPoolExecutor(self.threads, thread_name_prefix="depthcore-decode")
+        return self._pool
+
+    def _submit(self, indices, draws, alloc):
+        """Start decoding a batch: sizes from the headers of each item's first frame, then one task per frame writing at
+        its offset of `alloc(total bytes)` (frame-major: image f * B + b).  -> job dict with the futures."""
+        ds = self.dataset
+        paths = [ds.frame_paths(i) for i in indices]
+        sizes = [_image_size(p[0]) for p in paths]
+        per_frame = sum(h * w * 3 for h, w in sizes)
+        buf = alloc(per_frame * len(ds.frame_idxs))
+        futures, off = [], 0
+        for f in range(len(ds.frame_idxs)):
+            for b, (h, w) in enumerate(sizes):
+                dst = buf[off:off + h * w * 3].reshape(h, w, 3)
+                futures.append(self._pool_().submit(_decode_into, paths[b][f], dst))
+                off += h * w * 3
+        flips = [bool(d[0]) for d in draws]
+        meta = self._pool_().submit(lambda: [ds.metadata(i, fl) for i, fl in zip(indices, flips)])
+        return {"buf": buf[:off], "sizes": sizes, "flips": flips, "jitters": [d[1] for d in draws], "futures": futures, "meta": meta}
+
+    @staticmethod
+    def _finish(job):
+        for fut in job["futures"]:
+            fut.result()
+        metas = job["meta"].result()
+        extras = {k: np.stack([m[k] for m in metas]) for k in (metas[0] if metas else {})}
+        return job["buf"], job["sizes"], job["flips"], job["jitters"], extras
+
+    def decode_batch(self, indices, draws=None, out=None):
+        """Host half of one batch: -> (packed uint8 buffer, sizes [(Hn, Wn)] per item, flips, jitters, extras).  The buffer
+        holds the decoded frames back to back, frame-major (what GpuPreprocessor.ragged takes); extras: the stacked
+        "depth_gt" (B, 1, H, W) / "stereo_T" (B, 4, 4) of datasets that have them.  draws: one (do_flip, jitter) per item
+        (default: none).  out: a uint8 array to decode into (default: a new one)."""
+        draws = draws if draws is not None else [(False, None)] * len(indices)
+
+        def alloc(nbytes):
+            if out is None:
+                return np.empty(nbytes, np.uint8)
+            if out.size < nbytes:
+                raise ValueError("decode_batch: %d bytes do not fit the given buffer of %d" % (nbytes, out.size))
+            return out
+        return self._finish(self._submit(indices, draws, alloc))
+
+    # ---------------------------------------------------------------------------------------------------------- device half
+    def _stage(self, slot, nbytes):
+        """Pinned staging buffer `slot`, free again: the copy that last read it has completed."""
+        if self._copied[slot] is not None:
+            self._copied[slot].synchronize()
+            self._copied[slot] = None
+        if self._staging[slot] is None or self._staging[slot].numel() < nbytes:
+            self._staging[slot] = torch.empty(nbytes + nbytes // 8, dtype=torch.uint8).pin_memory()
+        return self._staging[slot].numpy()
+
+    def _upload(self, job, slot):
+        """One host-to-device copy + the data step, on the loader's stream -> (batch dict, event that completes it)."""
+        buf, sizes, flips, jitters, extras = self._finish(job)
+        ds = self.dataset
+        if self._pre is None:
+            self._pre = GpuPreprocessor(ds.height, ds.width, ds.num_scales, [f for f in ds.frame_idxs], self.device)
+            self._intrinsics = self._pre.intrinsics(ds.K, self.batch_size)
+            self._side = torch.cuda.Stream(self.device)
+        with torch.cuda.stream(self._side):
+            dev = torch.empty(buf.size, dtype=torch.uint8, device=self.device)
+            dev.copy_(self._staging[slot][:buf.size], non_blocking=True)
+            self._copied[slot] = torch.cuda.Event()
+            self._copied[slot].record(self._side)
+            batch = self._pre.ragged(dev, sizes, flips, jitters)
+            batch.update(self._intrinsics)
+            for k, v in extras.items():
+                batch[k] = torch.from_numpy(np.ascontiguousarray(v)).to(self.device)
+            ready = torch.cuda.Event()
+            ready.record(self._side)
+        return batch, ready
+
+    def __iter__(self):
+        """One epoch (`set_epoch`) of batches: dicts of device tensors only, the same keys and shapes every step."""
+        for job in self._jobs:                      # an abandoned iteration: let its decodes finish before the buffers go on
+            if "futures" in job:
+                self._finish(job)
+        self._jobs.clear()
+        batches = self.plan()
+        nxt = 0
+
+        def submit_until(last):
+            # batch j decodes into staging buffer j % 2: `_stage` waits for the copy of batch j - 2, which has been issued by
+            # then (batch j - 2 is the one being handed out, or an earlier one)
+            nonlocal nxt
+            while nxt < len(batches) and nxt <= last:
+                slot = nxt % 2
+                job = self._submit(*batches[nxt], alloc=lambda nbytes, slot=slot: self._stage(slot, nbytes))
+                job["slot"] = slot
+                self._jobs.append(job)
+                nxt += 1
+
+        for step in range(len(batches)):
+            submit_until(step)
+            cur = self._jobs.popleft()
+            if "futures" in cur:
+                cur = dict(zip(("batch", "ready"), self._upload(cur, cur["slot"])))
+            submit_until(step + self.prefetch)
+            # the next batch's copy and data step go out now if its frames are already decoded: they run under this step
+            if self._jobs and "futures" in self._jobs[0] and all(f.done() for f in self._jobs[0]["futures"] + [self._jobs[0]["meta"]]):
+                job = self._jobs[0]
+                self._jobs[0] = dict(zip(("batch", "ready"), self._upload(job, job["slot"])))
+            consumer = torch.cuda.current_stream(self.device)
+            consumer.wait_event(cur["ready"])
+            for t in cur["batch"].values():
+                t.record_stream(consumer)
+            yield cur["batch"]
+
+    def close(self):
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
+            self._pool = None

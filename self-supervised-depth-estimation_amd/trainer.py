@@ -2,8 +2,11 @@
 
 Same method names and dict schemas as the reference so that code written against
 `Trainer.process_batch / predict_poses / generate_images_pred / compute_reprojection_loss /
-compute_losses` keeps working; the control plane around it (data loading, tensorboard, checkpoints,
-validation) is out of scope (SURVEY 8, rows a14-a18 only).
+compute_losses` keeps working.  The loop around it -- `train()` / `run_epoch()` / `log_time()` / `log()` / `val()`
+(reference trainer.py:210-254, 444-463, 654-671) with checkpoints every `save_frequency` epochs -- is fed by
+`depthcore.loader.BatchLoader` over the `datasets/` package: frames are decoded on host threads and the per-item
+data step (flip, Lanczos pyramid, ColorJitter, ToTensor) runs on the device.  Scalars are appended to
+`<log_path>/<mode>/scalars.jsonl`; there is no tensorboard writer and no image logging.
 
 Two equivalent loss paths, both on hand-written gfx950 kernels:
   * fused (default): generate_images_pred + compute_losses are ONE forward op and ONE backward op
@@ -24,6 +27,7 @@ sequence pass through `networks.ConvGRUBlocks_v5`, and the loss runs on the sequ
 import contextlib
 import json
 import os
+import time
 import types
 
 import numpy as np
@@ -213,6 +217,7 @@ class Trainer:
             "de/abs_rel", "de/sq_rel", "de/rms", "de/log_rms", "da/a1", "da/a2", "da/a3"]
         self.step = 0
         self.epoch = 0
+        self.train_loader = self.val_loader = self._val_iter = None        # build_loaders(): train() needs them, a step does not
         self._side_stream = None
         self._main_stream = None          # the high-priority stream of the eager step (_step_stream)
         use_cache = self.device.type == "cuda" and getattr(self.opt, "wino_weight_cache", True)
@@ -249,8 +254,9 @@ class Trainer:
     # ------------------------------------------------------------------ trainer.py:444-463, 624-652
     def val(self, inputs):
         """Validate the model on a single minibatch (trainer.py:444-463): eval mode, process_batch under no_grad, the depth
-        metrics when the batch carries "depth_gt", back to train mode; returns (outputs, losses).  The project has no loaders:
-        the batch is the argument (the reference pulls it from val_loader); tensorboard logging stays with the caller.
+        metrics when the batch carries "depth_gt", back to train mode; returns (outputs, losses).  The batch is the argument:
+        `run_epoch` passes the next one of its cycling validation iterator (the reference's val pulls it from val_loader
+        itself) and logs the returned losses.
         Training is left where it was -- parameters, BatchNorm statistics and num_batches_tracked (eval mode reads the running
         statistics), optimiser state, self.step, the device noise seed, captured graphs -- and the Winograd weight cache is
         invalidated again.  With opt.cpu_tiebreak_noise the loss draws its tie-break noise from the CPU generator, as the
@@ -642,6 +648,121 @@ class Trainer:
             losses["loss/{}".format(scale)] = loss
         losses["loss"] = total_loss / self.num_scales
         return losses
+
+    # ------------------------------------------------------------------ trainer.py:139-164, 210-254, 654-671
+    DATASETS = {"kitti": "KITTIRAWDataset", "kitti_odom": "KITTIOdomDataset", "kitti_depth": "KITTIDepthDataset"}
+
+    def build_loaders(self, prefetch=2):
+        """The two shuffled loaders of trainer.py:139-164 over `<splits_dir>/<split>/{train,val}_files.txt`: `opt.dataset`
+        picks the class, `opt.png` the extension; the validation loader is shuffled too and draws no augmentation.  Each rank
+        reads a strided shard of the same permutation (depthcore.loader.BatchLoader)."""
+        import datasets
+        from depthcore.loader import BatchLoader
+        if self.opt.gru:
+            raise NotImplementedError("training loops for the ConvGRU front-end need the reference's sequence dataset "
+                                      "(datasets/kitti_dataset_seq.py), which this project does not have")
+        if self.opt.dataset not in self.DATASETS:
+            raise ValueError("dataset %r: one of %s" % (self.opt.dataset, sorted(self.DATASETS)))
+        cls = getattr(datasets, self.DATASETS[self.opt.dataset])
+        ext = ".png" if self.opt.png else ".jpg"
+        loaders = []
+        for mode in ("train", "val"):
+            path = os.path.join(self.opt.splits_dir, self.opt.split, "%s_files.txt" % mode)
+            if not os.path.isfile(path):
+                raise FileNotFoundError("%s not found: no split files ship with the project, point --splits_dir at yours" % path)
+            with open(path) as f:
+                names = f.read().splitlines()
+            ds = cls(self.opt.data_path, names, self.opt.height, self.opt.width, self.opt.frame_ids, 4, is_train=mode == "train",
+                     img_ext=ext)
+            loaders.append(BatchLoader(ds, self.opt.batch_size, self.opt.num_workers, self.device, seed=int(mode == "val"), shuffle=True,
+                                       rank=self.rank, world_size=self.world_size, prefetch=prefetch))
+        self.train_loader, self.val_loader = loaders
+        self._val_iter = None
+        return self.train_loader, self.val_loader
+
+    @staticmethod
+    def is_log_step(batch_idx, step, log_frequency):
+        """trainer.py:241-245, verbatim: often during the first 2000 steps, then every 2000th.  `step` counts the steps
+        taken BEFORE this one, as the reference's self.step does where it evaluates this."""
+        early_phase = batch_idx % log_frequency == 0 and step < 2000
+        late_phase = step % 2000 == 0
+        return early_phase or late_phase
+
+    def train(self):
+        """Run the entire training pipeline (trainer.py:210-219)."""
+        if self.opt.gru:
+            raise NotImplementedError("train() covers the vanilla and Fusion_v3 front-ends; the ConvGRU loop needs the "
+                                      "reference's sequence dataset")
+        if self.train_loader is None:
+            self.build_loaders()
+        self.epoch = 0
+        self.step = 0
+        self.start_time = time.time()
+        self.num_total_steps = len(self.train_loader) * self.opt.num_epochs
+        self.save_opts()
+        for epoch in range(self.opt.num_epochs):
+            self.start_epoch(epoch)
+            self.run_epoch()
+            if (self.epoch + 1) % self.opt.save_frequency == 0:
+                self.save_model()
+
+    def run_epoch(self):
+        """One epoch of training with validation at the log steps (trainer.py:221-254).  The learning-rate scheduler steps
+        at the END of the epoch: the reference calls it first, which under any torch >= 1.1 drops the rate one epoch early;
+        `scheduler_step_size` full epochs run at the initial rate here."""
+        self.set_train()
+        self.train_loader.set_epoch(self.epoch)
+        with self.on_step_stream():
+            for batch_idx, inputs in enumerate(self.train_loader):
+                before_op_time = time.time()
+                outputs, losses = self.train_step(inputs)
+                duration = time.time() - before_op_time
+                step = self.step - 1                   # train_step has counted this step already
+                if self.is_log_step(batch_idx, step, self.opt.log_frequency):
+                    self.log_time(batch_idx, duration, float(losses["loss"].detach()), step)
+                    losses = dict(losses)              # (under hip_graph the step's dict is the static one of every replay)
+                    if "depth_gt" in inputs:
+                        self.compute_depth_losses(inputs, outputs, losses)
+                    self.log("train", losses, step)
+                    if not self.opt.fusion:            # Trainer.val refuses the sequence front-ends
+                        _, val_losses = self.val(self._next_val_batch())
+                        self.log("val", val_losses, step)
+        self.model_lr_scheduler.step()
+
+    def _next_val_batch(self):
+        """trainer.py:448-452: the validation loader is cycled, one batch per log step."""
+        for _ in range(2):
+            if self._val_iter is None:
+                self._val_iter = iter(self.val_loader)
+            try:
+                return next(self._val_iter)
+            except StopIteration:
+                self.val_loader.set_epoch(self.val_loader.epoch + 1)
+                self._val_iter = None
+        raise ValueError("the validation split has fewer items than one batch")
+
+    def log_time(self, batch_idx, duration, loss, step=None):
+        """trainer.py:654-664: the reference's terminal line."""
+        def hm(t):
+            t = int(t)
+            return "{:02d}h{:02d}m{:02d}s".format(t // 3600, t // 60 % 60, t % 60)
+        step = self.step if step is None else step
+        samples_per_sec = self.opt.batch_size / duration
+        time_sofar = time.time() - self.start_time
+        training_time_left = (self.num_total_steps / step - 1.0) * time_sofar if step > 0 else 0
+        print("epoch {:>3} | batch {:>6} | examples/s: {:5.1f} | loss: {:.5f} | time elapsed: {} | time left: {}".format(
+            self.epoch, batch_idx, samples_per_sec, loss, hm(time_sofar), hm(training_time_left)))
+
+    def log(self, mode, losses, step=None):
+        """The scalars of trainer.py:666-671 (`writer.add_scalar(l, v, self.step)`), one JSON object per call appended to
+        `<log_path>/<mode>/scalars.jsonl`: {"step": ..., name: value, ...}.  No images."""
+        folder = os.path.join(self.log_path, mode)
+        os.makedirs(folder, exist_ok=True)
+        row = {"step": int(self.step if step is None else step)}
+        for name, v in losses.items():
+            row[name] = float(v.detach()) if torch.is_tensor(v) else float(v)
+        with open(os.path.join(folder, "scalars.jsonl"), "a") as f:
+            f.write(json.dumps(row) + "\n")
 
     # ------------------------------------------------------------------ trainer.py:700-763
     @property
