@@ -735,6 +735,21 @@ int dc_set_wino_f4(int mode);
  * arithmetic in the same order per output: results are bitwise those of the classic launch.  Process-global; the initial
  * mode comes from DC_WINO_PERSIST (default 0); returns the previous mode, or DC_EINVAL.  Measurements: DESIGN.md 4a. */
 int dc_set_wino_persist(int mode);
+/* Where the two-group weight-gradient launches of the fp32 Winograd kernels (dc_wino3x3_wgrad / _wgrad_bn and the fused
+ * dc_conv3x3_bwd* blocks on them: 64-channel tiles with at least four sub-regions per 4-wave group) stage the next chunk inside
+ * a barrier interval.  A wave's chunk is matrix work on the current LDS slab plus one contiguous staging phase (commit the
+ * prefetched registers to the other slab, request the chunk after), which may sit anywhere between the interval's two
+ * barriers.  Phase 1 is the classic order, staging behind the matrix work; phase 0 puts it in front.  -1 = auto: the two
+ * groups of a block, whose waves share the SIMDs pairwise behind one barrier, take phases 1 and 0, so that one group stages
+ * while the other multiplies.  0 and 1 force that phase on every wave.  DC_WINO_PHASE_DEFAULT -- the initial mode unless
+ * DC_WINO_PHASE names another -- is what the launches ship with: auto.  No barrier moves and no accumulation order changes:
+ * results are bitwise the same in every mode.  The other Winograd launches (one-group weight gradients, forward and data
+ * gradient) keep the classic order in every mode: their SIMD partners are other blocks with barriers of their own, and
+ * staggering them measured nothing.  The mode is read at launch and travels as a kernel argument.
+ * Process-global; returns the previous mode; DC_EINVAL (which reads the same as a previous mode of -1) for any other value,
+ * and the mode stays as it was. */
+#define DC_WINO_PHASE_DEFAULT (-3)
+int dc_set_wino_phase(int mode);
 /* Data gradient of the fused blocks on the Winograd kernels (dc_conv3x3_bwd / _bwd_add): 1 (default) writes the interior of the
  * correlation straight to dx0 / dx1 -- concat split, the 2 x 2 sums of an upsampled x0 and the addends in the store epilogue -- and
  * adds what ReflectionPad folds back from the padded ring in one small launch; 0 = the full correlation over the padded domain into a

@@ -21,6 +21,8 @@
 //   * split reduction without atomics: block (split, m-block, k-block) writes q[a][.] = (dU G)[a][.] (3 values per
 //     row a) to its slab with lane-contiguous stores; wino_wreduce_kernel sums the slabs in fixed order and applies
 //     G^T.  Deterministic.
+//   * the two 4-wave groups of a two-group block (NG = 2) share the SIMDs pairwise behind one barrier; they run the chunk in
+//     different orders -- one stages the next chunk while the other multiplies (dc_set_wino_phase; the reduction loop).
 // Requires even W; H arbitrary.
 #include "dc_common.h"
 #include "conv_bf16.h"
@@ -39,6 +41,7 @@ constexpr int WG_MR = 4, WG_KR = 2;                    // 16-channel tiles per w
 constexpr int WG_KT = 16 * WG_KR;                      // x-side channels per block (gy side: 16 MR)
 constexpr int WG_GPS = 66;                             // gy slab channel stride (floats), = 2 mod 32, >= 64
 constexpr int WG_XPS = 130;                            // x slab channel stride, = 2 mod 32, >= 120
+constexpr int WINO_PHASES = 2;                         // staging positions inside a barrier interval (dc_set_wino_phase); the last is the classic order
 constexpr int WG_SLAB = 4 * WG_MR * WG_KR * 4 * 3 * 64;   // floats one block writes (MR = 4; half of it for MR = 2)
 
 struct WinoWgArgs {
@@ -58,6 +61,7 @@ struct WinoWgArgs {
     // relu(scale[g, k] x + shift[g, k]) is re-formed between the global load and the LDS store (dc_bn_fold)
     const float* in_scale; const float* in_shift;
     int npg;
+    int phase;                        // NG = 2 launches: dc_set_wino_phase, -1 auto, 0 .. WINO_PHASES - 1 for every wave
 };
 unsigned long long* wino_diag_ptr();
 
@@ -78,6 +82,15 @@ __global__ __launch_bounds__(256 * NG, 2) void wino_wgrad_kernel(WinoWgArgs a) {
 #endif
     const int lane = threadIdx.x & 63, wave_all = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int grp = NG == 1 ? 0 : wave_all >> 2, wave = wave_all & 3, tid = threadIdx.x & 255;     // group, Winograd row, thread of the group
+    // where this wave stages inside a barrier interval (the reduction loop below).  The two groups of an NG = 2 block are SIMD
+    // partners behind one barrier; auto: group 0 keeps the classic order, group 1 stages first.  NG = 1 launches keep the classic
+    // order at compile time: their SIMD partners are waves of other blocks with barriers of their own, for which the two orders
+    // are the same cycle, and a phase taken from the hardware wave slot measured no gain
+    int early = 0;
+    if constexpr (NG == 2) {
+        const int phase = a.phase < 0 ? (grp == 1 ? 0 : WINO_PHASES - 1) : a.phase;
+        early = __builtin_amdgcn_readfirstlane(phase == 0 ? 1 : 0);
+    }
     float* const gl0 = wg_smem + grp * GROUP_LDS;
     float* const xl0 = gl0 + 2 * GL;
     auto gl = [&](int buf) { return gl0 + buf * GL; };
@@ -270,7 +283,17 @@ __global__ __launch_bounds__(256 * NG, 2) void wino_wgrad_kernel(WinoWgArgs a) {
     };
 
     // ---- reduction over this block's sub-regions: split, split + splits, ... (NG = 2: alternately to the two groups; the
-    // barriers are the block's, so a group that runs out of work keeps pace without computing)
+    // barriers are the block's, so a group that runs out of work keeps pace without computing).
+    // Staging = commit of the next chunk + request of the one after, one contiguous phase.  The commit writes the slab that was
+    // last read before the previous barrier and the request refills exactly the registers the commit emptied, so the phase may
+    // sit anywhere between the interval's two barriers.  This kernel has two positions: behind the chunk's matrix work (the
+    // classic order, phase 1) or in front of it (phase 0).  Waves of one SIMD in different phases stage under each
+    // other's MFMAs instead of all multiplying, then all staging.  Same barriers, same accumulation order: bitwise the same q.
+    //   classic:  B | C(0) S(1) B | C(1) S(2) B | ...             S(j): commit chunk j, request chunk j + 1
+    //   phase 0:  B | S(1) C(0) B | S(2) C(1) B | ...   written as   B S(1) | C(0) B S(2) | C(1) B S(3) | ...
+    // so the loop holds ONE copy of the staging code with the barrier on either side of it.  (Copies of the staging per position
+    // inside one loop, and one copy of the loop per phase, both cost ~40 VGPRs -- 217 -> 254-256 with scratch, the 32-channel
+    // tiles from three blocks per CU to two.)
     const int stride = NG * a.splits;
     int sub = split0 + grp * a.splits;
     if (sub < a.nsub) {
@@ -279,18 +302,22 @@ __global__ __launch_bounds__(256 * NG, 2) void wino_wgrad_kernel(WinoWgArgs a) {
         if (sub + stride < a.nsub) prefetch(sub + stride);
     }
     __syncthreads();
+    if (early && sub + stride < a.nsub) {             // S(1) of the rotated order
+        commit(1);
+        if (sub + 2 * stride < a.nsub) prefetch(sub + 2 * stride);
+    }
 #ifdef WINO_DIAG
     const unsigned long long dg0 = __builtin_amdgcn_s_memtime();
 #endif
     for (int it = 0, lead = split0; lead < a.nsub; lead += stride, sub += stride, ++it) {     // `lead`: group 0's sub-region (block-uniform trip count)
-        if (sub < a.nsub) {
-            compute(it & 1);
-            if (sub + stride < a.nsub) {
-                commit((it + 1) & 1);
-                if (sub + 2 * stride < a.nsub) prefetch(sub + 2 * stride);
-            }
+        if (sub < a.nsub) compute(it & 1);
+        if (early) __syncthreads();
+        const int nxt = sub + (1 + early) * stride;          // the chunk committed now; its slab was last read before the previous barrier
+        if (nxt < a.nsub) {
+            commit((it + 1 + early) & 1);
+            if (nxt + stride < a.nsub) prefetch(nxt + stride);
         }
-        __syncthreads();
+        if (!early) __syncthreads();
     }
 
 #ifdef WINO_DIAG
@@ -470,6 +497,16 @@ static const WgKernel g_wg_kernels[4 * 3] = {
     wg_kernel<true, 4, 1>(), wg_kernel<true, 4, 2>(), wg_kernel<true, 2, 1>(),
 };
 
+// dc_set_wino_phase.  DC_WINO_PHASE_DEFAULT is the mode the launches ship with: auto (-4.2 % over the step's weight-gradient
+// shapes against the classic order, every two-group shape faster: DESIGN 4a)
+constexpr int WG_PHASE_SHIPPED = -1;
+static bool wino_phase_valid(int m) { return m == DC_WINO_PHASE_DEFAULT || (m >= -1 && m < WINO_PHASES); }
+static int g_wino_phase = [] {
+    const char* f = getenv("DC_WINO_PHASE");
+    const int v = f ? atoi(f) : DC_WINO_PHASE_DEFAULT;
+    return wino_phase_valid(v) ? v : DC_WINO_PHASE_DEFAULT;
+}();
+
 struct WgPlan { int RH, RW, GRS, XRS, regs_x, regs_y, nsub, mblocks, kblocks, splits, mr, ng; };
 
 static WgPlan wg_plan(int B, int Ci, int Co, int H, int W) {
@@ -527,6 +564,7 @@ static int wg_launch(const float* x0, int C0, int up0, const float* x1, int C1, 
 #ifdef WINO_DIAG
     a.diag = wino_diag_ptr();
 #endif
+    a.phase = g_wino_phase == DC_WINO_PHASE_DEFAULT ? WG_PHASE_SHIPPED : g_wino_phase;
     const bool bnin = bn && bn->in_scale;
     if (bnin) {
         if (fused || !bn->in_shift || bn->groups < 1 || bn->groups > 2 || B % bn->groups) return DC_EINVAL;
@@ -567,6 +605,13 @@ int wino_wgrad_fused(const float* x0, int C0, int up0, const float* x1, int C1, 
 }  // namespace dc
 
 using namespace dc;
+
+extern "C" int dc_set_wino_phase(int mode) {
+    if (!wino_phase_valid(mode)) return DC_EINVAL;
+    const int prev = g_wino_phase;
+    g_wino_phase = mode;
+    return prev;
+}
 
 extern "C" size_t dc_wino3x3_wgrad_workspace(int B, int Ci, int Co, int H, int W) {
     if (B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W < 2 || (W & 1)) return 0;
