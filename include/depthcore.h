@@ -830,6 +830,26 @@ int dc_data_ragged_resize_axis(const uint8_t* src, size_t src_bytes, uint8_t* ds
                                const dc_ragged_img* desc_dev, int n_img, int out_size, int axis, const dc_ragged_table* tab_host,
                                const dc_ragged_table* tab_dev, int n_tab, const int* bounds_host, const int* bounds_dev,
                                size_t bounds_len, const int* kk_dev, size_t kk_len, void* stream);
+/* Warm batch: every key of the data step gathered from CACHE SLOTS (depthcore/frame_cache.py), no resize.  A slot holds the
+ * UNFLIPPED, already resized pyramid of one frame: level s is a tightly packed (height>>s, width>>s, 3) uint8 HWC image at byte
+ * sum_{t<s} (height>>t)*(width>>t)*3 of the slot.  Image i of the batch is the slot at byte slot_off of `arena`, read with its
+ * rows mirrored when flip != 0 (the Lanczos tables are mirror-symmetric, so this equals resizing the mirrored native frame).
+ *   color[s]     (n_img, 3, height>>s, width>>s) float32 from the untouched pixel (HOST arrays of num_scales device pointers);
+ *   color_aug[s] the same through the image's ColorJitter chain -- the arithmetic of dc_data_jitter_to_tensor, the contrast mean
+ *                taken per image AND per level -- or color_aug NULL (then steps / params / sums may be NULL);
+ *   packed       (n_img, height, width, 4) RGBx of scale 0 as dc_data_to_rgbx writes it, 16-byte aligned, or NULL.
+ * steps / params (n_img, 4) and sums (n_img, num_scales) uint64 scratch are DEVICE pointers.  desc is passed as HOST and DEVICE
+ * copies of the same bytes; the host copy is checked before anything is launched: DC_EINVAL (nothing launched, nothing written)
+ * for a slot that reaches outside arena_bytes, n_img <= 0, a height or width not divisible by 2^(num_scales-1), num_scales
+ * outside 1..DC_MAX_SCALES.  At most two launches on `stream` for the whole batch and all levels (the sum pass only with
+ * color_aug) behind one memset of `sums`; no allocation, no synchronisation. */
+typedef struct dc_cached_img {
+    long long slot_off;
+    int flip, reserved;
+} dc_cached_img;
+int dc_data_cached_levels(const uint8_t* arena, size_t arena_bytes, const dc_cached_img* desc_host, const dc_cached_img* desc_dev,
+                          int n_img, int height, int width, int num_scales, float* const* color, float* const* color_aug,
+                          float* packed, const int* steps, const float* params, unsigned long long* sums, void* stream);
 
 /* ------------------------------------------------------------------ depth metrics (validation)
  * Trainer.compute_depth_losses (trainer.py:624-652, called at :248 and from val at :460) and the KITTI Eigen protocol of

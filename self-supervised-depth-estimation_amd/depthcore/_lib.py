@@ -260,6 +260,7 @@ def _sig(lib):
         "dc_pack_rgbx": (i, [p, p, i, i, p]),
         "dc_data_jitter_to_tensor": (i, [p, p, p, i, i, p, p, p, p]),
         "dc_data_ragged_resize_axis": (i, [p, z, p, z, p, p, i, i, i, p, p, i, p, p, z, p, z, p]),
+        "dc_data_cached_levels": (i, [p, z, p, p, i, i, i, i, p, p, p, p, p, p, p]),
         "dc_attnconv_fwd": (i, [POINTER(AttnMap), POINTER(AttnParams), POINTER(AttnMap), p, i, i, i, i, i, i, p]),
         "dc_attnconv_param_count": (i, [i]),
         "dc_attnconv_bwd_workspace": (z, [i, i, i, i]),

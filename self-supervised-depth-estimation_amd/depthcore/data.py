@@ -7,7 +7,9 @@ libdepthcore's `dc_data_*` entry points, byte-exact with the CPU pipeline (tests
 Random draws stay on the host (`sample_item`), in the reference's order.  There is no CPU path.
 `GpuPreprocessor.__call__` takes a batch of one native size; `GpuPreprocessor.ragged` takes items of different native sizes
 packed back to back (what a shuffled KITTI loader delivers, depthcore/loader.py) and makes scale 0 with two launches over
-the whole batch (`dc_data_ragged_resize_axis`, tests/test_data_ragged_gpu.py).
+the whole batch (`dc_data_ragged_resize_axis`, tests/test_data_ragged_gpu.py); `GpuPreprocessor.cached` takes frames whose
+resized pyramids already sit in cache slots (depthcore/frame_cache.py) and makes the same dict without any resize, in two
+launches (`dc_data_cached_levels`, tests/test_data_cached_gpu.py).
 """
 import random
 
@@ -22,6 +24,8 @@ NO_OP = -1
 # mirror of `dc_ragged_img` (include/depthcore.h)
 RAGGED_IMG = np.dtype([("src_off", np.int64), ("dst_off", np.int64), ("Hi", np.int32), ("Wi", np.int32), ("table", np.int32),
                        ("flip", np.int32)])
+# mirror of `dc_cached_img`
+CACHED_IMG = np.dtype([("slot_off", np.int64), ("flip", np.int32), ("reserved", np.int32)])
 
 
 def resample_table(in_size, out_size):
@@ -34,6 +38,20 @@ def resample_table(in_size, out_size):
     kk = np.zeros((out_size, ksize), np.int32)
     check(L.dc_resample_table(int(in_size), int(out_size), bounds.ctypes.data, kk.ctypes.data), "dc_resample_table")
     return bounds, kk
+
+
+def slot_layout(height, width, num_scales):
+    """A cache slot (dc_data_cached_levels): the byte offset of every level of the pyramid -- level s is a tightly packed
+    (height >> s, width >> s, 3) uint8 image behind the levels before it -- and the size of the slot."""
+    height, width, num_scales = int(height), int(width), int(num_scales)
+    if not 1 <= num_scales <= _lib.MAX_SCALES or height <= 0 or width <= 0 or height % (1 << (num_scales - 1)) or width % (1 << (num_scales - 1)):
+        raise _lib.DepthcoreError("%d x %d is not divisible by 2^(%d - 1), or num_scales is outside 1..%d"
+                                  % (height, width, num_scales, _lib.MAX_SCALES))
+    offsets, total = [], 0
+    for s in range(num_scales):
+        offsets.append(total)
+        total += (height >> s) * (width >> s) * 3
+    return offsets, total
 
 
 def sample_item(is_train=True, rng=random, brightness=(0.8, 1.2), contrast=(0.8, 1.2), saturation=(0.8, 1.2), hue=(-0.1, 0.1)):
@@ -264,6 +282,63 @@ class GpuPreprocessor:
                 packed = packed.view(Fn, B, h, w, 4)
                 for i, f in enumerate(self.frame_idxs):
                     out[("color_packed", f, 0)] = packed[i]
+        return out
+
+    def cached(self, arena, slots, flips=None, jitters=None):
+        """`ragged` for a batch whose frames already sit in cache slots (depthcore/frame_cache.py): arena is a 1-D uint8 device
+        tensor of slots of `slot_layout(height, width, num_scales)` bytes, each the UNFLIPPED resized pyramid of one frame;
+        slots: the slot index of every image, frame-major like `ragged` (image f * B + b is frame f of item b); flips /
+        jitters: one entry per item.  One dc_data_cached_levels call (two launches) -> the dict of `__call__`."""
+        Fn = len(self.frame_idxs)
+        if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_cuda or not arena.is_contiguous():
+            raise _lib.DepthcoreError("the arena must be a contiguous 1-D uint8 device tensor")
+        n = len(slots)
+        B = n // Fn
+        if n == 0 or n != B * Fn or (flips is not None and len(flips) != B) or (jitters is not None and len(jitters) != B):
+            raise _lib.DepthcoreError("one slot per frame of every item, flips and jitters one entry per item")
+        L = _lib.lib()
+        S, dev = self.num_scales, arena.device
+        _, slot_bytes = slot_layout(self.height, self.width, S)
+        aug = jitters is not None and any(j is not None for j in jitters)
+        # descriptors, steps and params travel in ONE host-to-device copy: [desc n x 16 | steps n x 16 | params n x 16] bytes
+        host = np.zeros(n * (48 if aug else 16), np.uint8)
+        desc = host[:n * 16].view(CACHED_IMG)
+        desc["slot_off"] = np.asarray(slots, np.int64) * slot_bytes
+        if flips is not None:
+            desc["flip"] = np.tile(np.asarray(flips, bool), Fn)
+        if aug:
+            st_h, pr_h = host[n * 16:n * 32].view(np.int32).reshape(n, 4), host[n * 32:].view(np.float32).reshape(n, 4)
+            st_h[...] = NO_OP
+            for b, j in enumerate(jitters):
+                if j is None:
+                    continue
+                order, factors = j
+                for k, op in enumerate(order):
+                    st_h[b::B, k] = op
+                    pr_h[b::B, k] = float(hue_shift(factors[op])) if op == HUE else factors[op]
+        host_dev = torch.from_numpy(host).to(dev)
+        base = host_dev.data_ptr()
+        sums = torch.empty(n * S, dtype=torch.int64, device=dev) if aug else None
+        color = [torch.empty((n, 3, self.height >> s, self.width >> s), dtype=torch.float32, device=dev) for s in range(S)]
+        color_aug = [torch.empty_like(c) for c in color] if aug else None
+        packed = torch.empty((n, self.height, self.width, 4), dtype=torch.float32, device=dev)
+        ptrs = _lib.c_void_p * S
+        check(L.dc_data_cached_levels(
+            arena.data_ptr(), arena.numel(), desc.ctypes.data, base, n, self.height, self.width, S,
+            ptrs(*[c.data_ptr() for c in color]), ptrs(*[c.data_ptr() for c in color_aug]) if aug else None, packed.data_ptr(),
+            base + n * 16 if aug else None, base + n * 32 if aug else None, sums.data_ptr() if aug else None, stream(arena)),
+            "dc_data_cached_levels")
+        out = {}
+        for s in range(S):
+            c = color[s].view(Fn, B, 3, self.height >> s, self.width >> s)
+            a = color_aug[s].view(Fn, B, 3, self.height >> s, self.width >> s) if aug else c
+            for i, f in enumerate(self.frame_idxs):
+                out[("color", f, s)] = c[i]
+                out[("color_aug", f, s)] = a[i]
+            if s == 0:
+                pk = packed.view(Fn, B, self.height, self.width, 4)
+                for i, f in enumerate(self.frame_idxs):
+                    out[("color_packed", f, 0)] = pk[i]
         return out
 
     def intrinsics(self, K, batch):

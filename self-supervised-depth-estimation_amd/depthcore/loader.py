@@ -15,6 +15,9 @@ into a hipGraph never meets a launch or an allocation of another thread.
 Sampling is a function of (seed, epoch) alone: one `random.Random` gives the permutation and then, in item order, the
 draws of `sample_item` -- batches do not depend on thread timing.  `rank` / `world_size` take a strided shard of the same
 permutation, the same number of steps on every rank.
+
+`cache_bytes` > 0 adds a cache of resized frames in HBM (depthcore/frame_cache.py): the host then decodes only the frames
+the cache lacks, and a warm batch is gathered from cache slots in two launches.  The batches are the same, bit for bit.
 """
 import collections
 import random
@@ -25,6 +28,7 @@ import torch
 from PIL import Image
 
 from .data import GpuPreprocessor, sample_item
+from .frame_cache import FrameCache
 
 MAX_THREADS = 16      # decode threads: bounded by the option and by this, never by the machine's core count
 
@@ -72,8 +76,15 @@ def _image_size(path):
 
 
 class BatchLoader:
-    def __init__(self, dataset, batch_size, num_workers=12, device="cuda", seed=0, shuffle=True, rank=0, world_size=1, prefetch=2):
+    def __init__(self, dataset, batch_size, num_workers=12, device="cuda", seed=0, shuffle=True, rank=0, world_size=1, prefetch=2,
+                 cache_bytes=0):
+        """cache_bytes > 0: keep resized frames on the device (depthcore/frame_cache.py) in an arena of that many bytes --
+        a frame is decoded the first time a batch needs it and served from its slot afterwards.  0: no cache."""
         self.dataset, self.batch_size = dataset, int(batch_size)
+        self.cache = None
+        if cache_bytes:
+            self.cache = FrameCache(dataset.height, dataset.width, dataset.num_scales, cache_bytes,
+                                    len(dataset.frame_idxs) * self.batch_size, device)
         self.is_train = bool(dataset.is_train)
         self.seed, self.shuffle, self.rank, self.world_size = int(seed), bool(shuffle), int(rank), int(world_size)
         self.prefetch = max(0, min(int(prefetch), 2))        # two staging buffers: at most two batches ahead
@@ -129,6 +140,41 @@ class BatchLoader:
         meta = self._pool_().submit(lambda: [ds.metadata(i, fl) for i, fl in zip(indices, flips)])
         return {"buf": buf[:off], "sizes": sizes, "flips": flips, "jitters": [d[1] for d in draws], "futures": futures, "meta": meta}
 
+    def _submit_cached(self, indices, draws, alloc):
+        """`_submit` with the frame cache on: only the frames the cache lacks are decoded, each file once however often the
+        batch names it (frame 0 stands in for a missing neighbour), back to back into `alloc(total bytes)`; a batch whose
+        frames are all cached touches no file and no staging buffer.  The size of a missing frame comes from the header of
+        its item's first missing frame.  A native width whose Lanczos table is not mirror-symmetric cannot be cached
+        (FrameCache.symmetric): a batch that holds such an item goes down the uncached path whole and counts as bypassed."""
+        ds, cache = self.dataset, self.cache
+        paths = [ds.frame_paths(i) for i in indices]
+        need, hits = {}, 0
+        for item in paths:
+            size = None
+            for path in item:
+                if cache.lookup(path) is not None:
+                    hits += 1
+                elif path not in need:
+                    size = size or _image_size(path)
+                    need[path] = size
+        if not all(cache.symmetric(w) for _, w in need.values()):
+            cache.stats["bypassed"] += sum(len(item) for item in paths)
+            return self._submit(indices, draws, alloc)
+        cache.stats["hits"] += hits
+        cache.stats["misses"] += sum(len(item) for item in paths) - hits
+        cache.stats["decoded"] += len(need)
+        total = sum(h * w * 3 for h, w in need.values())
+        buf = alloc(total)[:total] if need else None
+        futures, frames, off = [], [], 0
+        for path, (h, w) in need.items():
+            futures.append(self._pool_().submit(_decode_into, path, buf[off:off + h * w * 3].reshape(h, w, 3)))
+            frames.append((path, off, h, w))
+            off += h * w * 3
+        flips = [bool(d[0]) for d in draws]
+        meta = self._pool_().submit(lambda: [ds.metadata(i, fl) for i, fl in zip(indices, flips)])
+        return {"paths": paths, "frames": frames, "buf": buf, "flips": flips, "jitters": [d[1] for d in draws], "futures": futures,
+                "meta": meta}
+
     @staticmethod
     def _finish(job):
         for fut in job["futures"]:
@@ -164,12 +210,14 @@ class BatchLoader:
 
     def _upload(self, job, slot):
         """One host-to-device copy + the data step, on the loader's stream -> (batch dict, event that completes it)."""
-        buf, sizes, flips, jitters, extras = self._finish(job)
         ds = self.dataset
         if self._pre is None:
             self._pre = GpuPreprocessor(ds.height, ds.width, ds.num_scales, [f for f in ds.frame_idxs], self.device)
             self._intrinsics = self._pre.intrinsics(ds.K, self.batch_size)
             self._side = torch.cuda.Stream(self.device)
+        if "paths" in job:
+            return self._upload_cached(job, slot)
+        buf, sizes, flips, jitters, extras = self._finish(job)
         with torch.cuda.stream(self._side):
             dev = torch.empty(buf.size, dtype=torch.uint8, device=self.device)
             dev.copy_(self._staging[slot][:buf.size], non_blocking=True)
@@ -183,14 +231,60 @@ class BatchLoader:
             ready.record(self._side)
         return batch, ready
 
+    def _upload_cached(self, job, slot):
+        """`_upload` of a `_submit_cached` job: the decoded frames go up in one copy and into slots -- cache slots while
+        there are free ones, else the arena's overflow slots, which only this batch reads; a frame that an earlier batch has
+        inserted since this one was submitted just uses its slot -- and the batch is gathered from the slots
+        (GpuPreprocessor.cached).  Slots are given out here, on the consuming thread, in batch order; everything runs in
+        order on the loader's stream, so a slot is written before any batch reads it and the overflow slots are free again
+        when the next batch builds."""
+        for fut in job["futures"]:
+            fut.result()
+        metas = job["meta"].result()
+        extras = {k: np.stack([m[k] for m in metas]) for k in (metas[0] if metas else {})}
+        cache, buf = self.cache, job["buf"]
+        where, build, spilled = {}, [], 0
+        for path, off, h, w in job["frames"]:
+            where[path] = cache.lookup(path)
+            if where[path] is None:
+                where[path] = cache.insert(path)
+                if where[path] is None:
+                    where[path] = cache.overflow_slot(spilled)
+                    spilled += 1
+                build.append((off, h, w, where[path]))
+        paths = job["paths"]
+        slots = []
+        for f in range(len(self.dataset.frame_idxs)):
+            for item in paths:
+                s = where.get(item[f])
+                slots.append(s if s is not None else cache.lookup(item[f]))
+        if any(s is None for s in slots):
+            raise RuntimeError("a frame of this batch has left the cache since the batch was planned (FrameCache.clear during an epoch)")
+        with torch.cuda.stream(self._side):
+            if build:
+                dev = torch.empty(buf.size, dtype=torch.uint8, device=self.device)
+                dev.copy_(self._staging[slot][:buf.size], non_blocking=True)
+                self._copied[slot] = torch.cuda.Event()
+                self._copied[slot].record(self._side)
+                cache.build(self._pre, dev, build)
+            batch = self._pre.cached(cache.arena, slots, job["flips"], job["jitters"])
+            batch.update(self._intrinsics)
+            for k, v in extras.items():
+                batch[k] = torch.from_numpy(np.ascontiguousarray(v)).to(self.device)
+            ready = torch.cuda.Event()
+            ready.record(self._side)
+        return batch, ready
+
     def __iter__(self):
         """One epoch (`set_epoch`) of batches: dicts of device tensors only, the same keys and shapes every step."""
         for job in self._jobs:                      # an abandoned iteration: let its decodes finish before the buffers go on
             if "futures" in job:
-                self._finish(job)
+                for fut in job["futures"] + [job["meta"]]:
+                    fut.result()
         self._jobs.clear()
         batches = self.plan()
         nxt = 0
+        submit = self._submit if self.cache is None else self._submit_cached
 
         def submit_until(last):
             # batch j decodes into staging buffer j % 2: `_stage` waits for the copy of batch j - 2, which has been issued by
@@ -198,7 +292,7 @@ class BatchLoader:
             nonlocal nxt
             while nxt < len(batches) and nxt <= last:
                 slot = nxt % 2
-                job = self._submit(*batches[nxt], alloc=lambda nbytes, slot=slot: self._stage(slot, nbytes))
+                job = submit(*batches[nxt], alloc=lambda nbytes, slot=slot: self._stage(slot, nbytes))
                 job["slot"] = slot
                 self._jobs.append(job)
                 nxt += 1

@@ -674,8 +674,10 @@ class Trainer:
                 names = f.read().splitlines()
             ds = cls(self.opt.data_path, names, self.opt.height, self.opt.width, self.opt.frame_ids, 4, is_train=mode == "train",
                      img_ext=ext)
+            # the frame cache serves the training loader only: the validation loader hands out one batch per log step
+            cache_bytes = int(float(getattr(self.opt, "frame_cache_gb", 0) or 0) * 2 ** 30) if mode == "train" else 0
             loaders.append(BatchLoader(ds, self.opt.batch_size, self.opt.num_workers, self.device, seed=int(mode == "val"), shuffle=True,
-                                       rank=self.rank, world_size=self.world_size, prefetch=prefetch))
+                                       rank=self.rank, world_size=self.world_size, prefetch=prefetch, cache_bytes=cache_bytes))
         self.train_loader, self.val_loader = loaders
         self._val_iter = None
         return self.train_loader, self.val_loader
@@ -727,6 +729,10 @@ class Trainer:
                     if not self.opt.fusion:            # Trainer.val refuses the sequence front-ends
                         _, val_losses = self.val(self._next_val_batch())
                         self.log("val", val_losses, step)
+        cache = getattr(self.train_loader, "cache", None)
+        if cache is not None:
+            print("epoch {:>3} | frame cache: {} of {} slots | {}".format(
+                self.epoch, len(cache), cache.capacity, " | ".join("%s: %d" % kv for kv in cache.stats.items())))
         self.model_lr_scheduler.step()
 
     def _next_val_batch(self):

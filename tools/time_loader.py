@@ -5,9 +5,12 @@ Prints one JSON line:
   decode_images_per_s   PIL decode of 1242 x 375 JPEGs on min(num_workers, 16) threads (host only)
   data_step_*_ms        B x 3 frames, the five sizes mixed: GpuPreprocessor.ragged against the same batch grouped by size,
                         `__call__` per group, index_copy back into batch order (the existing kernels); runs alternate
-  loader_batches_per_s  BatchLoader with prefetch 2 and prefetch 0 (nothing consumes the batches but an event wait)
-  train_*_ms_per_step   Trainer.train_step fed by the loader against the same loop fed by one device-resident synthetic
-                        batch; same process, alternating blocks (`synthetic_alone`: before the process has a loader)
+  data_step_ragged_vs_cached_ms  the same batch served from a warm frame cache (GpuPreprocessor.cached) against ragged,
+                        alternating blocks, every block's median listed
+  loader_batches_per_s  BatchLoader with prefetch 2 and prefetch 0 (nothing consumes the batches but an event wait); `cache_cold` /
+                        `cache_warm`: with a frame cache, the epoch that decodes every file and the epochs after it
+  train_*_ms_per_step   Trainer.train_step fed by the loader, by the loader on a warm frame cache, and by one device-resident
+                        synthetic batch; same process, alternating blocks (`synthetic_alone`: before the process has a loader)
 
     python tools/time_loader.py [--batch 12] [--height 192] [--width 640] [--num_workers 12] [--steps 40]
 """
@@ -26,7 +29,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "self-supervised-depth-estimation_amd"))
 import datasets  # noqa: E402
 import trainer as T  # noqa: E402
-from depthcore.data import GpuPreprocessor  # noqa: E402
+from depthcore.data import GpuPreprocessor, slot_layout  # noqa: E402
+from depthcore.frame_cache import FrameCache  # noqa: E402
 from depthcore.loader import BatchLoader, _decode_into  # noqa: E402
 from depthcore.synthetic import synthetic_batch  # noqa: E402
 
@@ -150,7 +154,38 @@ def main():
         res["data_step_ragged_ms"] = [round(v, 3) for v in rag]
         res["data_step_grouped_ms"] = [round(v, 3) for v in grp]
 
+        # 2b. the same batch from a warm frame cache (GpuPreprocessor.cached: two launches) against ragged, alternating blocks
+        cache = FrameCache(a.height, a.width, 4, (3 * B + 1) * slot_layout(a.height, a.width, 4)[1], 0, dev)
+        assert all(cache.symmetric(w) for _, w in sizes), "a native width fails the symmetry gate"
+        frames, off = [], 0
+        for f in range(3):
+            for h, w in sizes:
+                frames.append((off, h, w, cache.insert("image %d" % len(frames))))
+                off += h * w * 3
+        cache.build(pre, packed, frames)
+        slots = [fr[3] for fr in frames]
+        warm = pre.cached(cache.arena, slots, flips, jitters)
+        assert all(torch.equal(warm[k], got[k]) for k in got), "cached and ragged results differ"
+        rag2, cac = [], []
+        for _ in range(5):
+            rag2.append(median_ms(lambda: pre.ragged(packed, sizes, flips, jitters), 15))
+            cac.append(median_ms(lambda: pre.cached(cache.arena, slots, flips, jitters), 15))
+        res["data_step_ragged_vs_cached_ms"] = {"ragged": [round(v, 3) for v in rag2], "cached": [round(v, 3) for v in cac]}
+        del cache, warm
+
         # 3. the loader alone
+        cache_bytes = (len(KITTI_SIZES) * a.frames + 3 * B + 1) * slot_layout(a.height, a.width, 4)[1]
+        ldc = BatchLoader(ds, B, a.num_workers, dev, seed=1, prefetch=2, cache_bytes=cache_bytes)
+        for epoch, name in enumerate(("cold", "warm", "warm")):      # the first epoch decodes every file, the later ones none
+            ldc.set_epoch(epoch)
+            it = iter(ldc)
+            next(it)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            count = sum(1 for _ in it)
+            torch.cuda.synchronize()
+            res.setdefault("loader_batches_per_s_cache_%s" % name, []).append(round(count / (time.perf_counter() - t0), 1))
+        res["loader_cache_stats"] = dict(ldc.cache.stats)
         for prefetch in (2, 0, 2, 0):
             ld2 = BatchLoader(ds, B, a.num_workers, dev, seed=1, prefetch=prefetch)
             it, count = iter(ld2), 0
@@ -164,23 +199,27 @@ def main():
             ld2.close()
 
         # 4. the training step fed by the loader against the same loop on device-resident synthetic inputs
-        def cycle():
-            epoch = 0
+        def cycle(loader, epoch=0):
             while True:
-                ld.set_epoch(epoch)
-                for batch in ld:
+                loader.set_epoch(epoch)
+                for batch in loader:
                     yield batch
                 epoch += 1
-        feed = cycle()
+        feed, feed_warm = cycle(ld), cycle(ldc, 3)       # ldc: the cached loader of 3, every file in its slot by now
         with tr.on_step_stream():
             for _ in range(5):
                 tr.train_step(dict(synth))
                 tr.train_step(next(feed))
+                tr.train_step(next(feed_warm))
             for _ in range(3):
-                for name, src in (("synthetic", lambda: dict(synth)), ("loader", lambda: next(feed))):
+                for name, src in (("synthetic", lambda: dict(synth)), ("loader", lambda: next(feed)),
+                                  ("loader_warm_cache", lambda: next(feed_warm))):
                     res.setdefault("train_%s_ms_per_step" % name, []).append(steps_ms(src))
         feed.close()
+        feed_warm.close()
+        assert ldc.cache.stats["decoded"] == res["loader_cache_stats"]["decoded"], "the warm loader decoded a file"
         ld.close()
+        ldc.close()
         tr.close()
     print(json.dumps(res))
 
