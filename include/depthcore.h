@@ -578,6 +578,32 @@ int dc_convs2_dgrad(const float* gy, const float* weight, float* dx, void* ws, i
 size_t dc_convs2_wgrad_workspace(int B, int Ci, int Co, int Hi, int Wi, int ksize);
 int dc_convs2_wgrad(const float* x, const float* gy, float* dweight, void* ws, int B, int Ci, int Co, int Hi, int Wi, int ksize,
                     void* stream);
+/* What the launches above (raw_frames = 0) or dc_stem_fwd / dc_stem_wgrad (raw_frames = 1: B the output batch, Ci 3 or 6, ksize 7) run
+ * for one shape, decided by the function they and the three workspace queries call themselves (csrc/convgemm.hip: cg_plan), under the
+ * calling thread's matrix precision, dc_get_gemm_split() and the process's DC_STEM_PATCH, DC_CONV_TRIP and DC_STEM_X3.  DC_EINVAL for
+ * what the launches refuse (dc_convs2_supported; raw_frames = 1 off the patch-staged stem) or a NULL plan; touches no device memory
+ * and makes no HIP call.  Tests and diagnostics; the launches need no query. */
+/* stem_fwd_x3_kernel / stem_fwd_kernel / cg_fwd3_kernel / cg_fwd_kernel / g1x3_conv3s2_fwd (gemm1x1_x3.hip) / c3b_conv (conv_bf16.hip) */
+enum { DC_S2_FWD_STEM_X3 = 0, DC_S2_FWD_STEM_F32, DC_S2_FWD_TRIP, DC_S2_FWD_GATHER, DC_S2_FWD_G1X3, DC_S2_FWD_BF16 };
+/* stem_wgrad_kernel / cg_wgrad3_kernel / cg_wgrad_kernel / g1x3_conv3s2_wgrad / c3b_wgrad */
+enum { DC_S2_DW_STEM = 0, DC_S2_DW_TRIP, DC_S2_DW_GATHER, DC_S2_DW_G1X3, DC_S2_DW_BF16 };
+/* nothing follows the weight-gradient kernel / slab_reduce16_kernel<float> / its 16-byte form (stem: stem_wreduce_kernel) */
+enum { DC_S2_RED_NONE = 0, DC_S2_RED_SCALAR, DC_S2_RED_16B };
+/* refused (ksize 7, Ci % 4, Co % 32) / cg_dgrad3_kernel / c3b_conv on the dilated gradient */
+enum { DC_S2_DX_NONE = 0, DC_S2_DX_PARITY, DC_S2_DX_BF16 };
+typedef struct dc_convs2_plan {
+    int32_t fwd;                  /* DC_S2_FWD_* */
+    int32_t fwd_mt, fwd_nt;       /* DC_S2_FWD_TRIP / _GATHER: the kernel's <MT, NT> (32 MT rows x 32 NT pixels); 0 otherwise */
+    int32_t fwd_slabs;            /* DC_S2_FWD_TRIP: reduction slabs (1: straight into y, else cg_slabsum_kernel follows); 0 otherwise */
+    int32_t fwd_wpad;             /* cg_wpad_kernel runs first (DC_S2_FWD_STEM_* / _GATHER with Ci k k % 32 != 0) */
+    int32_t dw;                   /* DC_S2_DW_* */
+    int32_t dw_slabs;             /* DC_S2_DW_TRIP / _GATHER: slabs of the pixel reduction (1: straight into dweight); 0 otherwise */
+    int32_t dw_blocks, dw_tiles_per_block;    /* DC_S2_DW_STEM: blocks (= slabs) and the 2 x 64 pixel tiles each walks at most; 0 otherwise */
+    int32_t dw_reduce;            /* DC_S2_RED_* by Co Ci k k % 4 (16-byte aligned buffers); the G1X3 / BF16 kernels bring their own: NONE */
+    int32_t dx;                   /* DC_S2_DX_* */
+    int32_t dx_slabs;             /* DC_S2_DX_PARITY: output-channel slabs (1: straight into dx, else cg_slabsum_kernel follows); 0 otherwise */
+} dc_convs2_plan;
+int dc_convs2_plan_query(int B, int Ci, int Co, int Hi, int Wi, int ksize, int raw_frames, dc_convs2_plan* plan);
 
 /* Any other nn.Conv2d shape of the trunks (networks/resnet_encoder.py:74-98 via torchvision: square kernel, symmetric stride
  * and zero padding, no groups / dilation): odd or tiny maps, a 1x1 / 2 on an odd map, a stem whose input needs a gradient.

@@ -1068,46 +1068,111 @@ static int cg_fwd3_plan(int B, int Ci, int Co, int Hi, int Wi, CgTile& t) {
     return s;
 }
 
-extern "C" size_t dc_convs2_fwd_workspace(int B, int Ci, int Co, int Hi, int Wi, int ksize) {
-    if (!cg_ok(B, Ci, Co, Hi, Wi, ksize)) return 0;
-    const int K = Ci * ksize * ksize, Kp = cg_kp(Ci, ksize);
-    const size_t b16 = ksize == 3 ? c3b_weights_bytes(Ci, Co) : 0;
-    size_t slabs = 0;
-    if (trip_ok(Ci, ksize)) {
-        CgTile t;
-        const int sp = cg_fwd3_plan(B, Ci, Co, Hi, Wi, t);
-        if (sp > 1) slabs = (size_t)sp * B * Co * (Hi / 2) * (Wi / 2) * sizeof(float);
+static int cg_dgrad3_splits(int B, int Ci, int Co, int Hi, int Wi);
+
+// ---- the plan: every branch the three launches, dc_stem_* and the three workspace queries take, decided ONCE here (and exported as
+// dc_convs2_plan_query, which tests/convs2_cases.py compares field by field with its transcription of this function).  The fp32
+// family (stem / trip / gather, with its tiles and slabs) is filled in whatever the mode: the workspaces cover it AND the bf16 /
+// split-operand routes, because the precision and dc_set_gemm_split may change between a query and its launch.
+struct CgPlan {
+    int K, Kp;
+    bool wpad;                                     // the forward pads the weight rows to Kp first
+    bool stem, trip;                               // patch-staged stem / triple gathers; neither: the general gather kernels
+    bool stem_x3;                                  // stem forward on split operands
+    bool fwd_bf16, fwd_x3, dw_bf16, dw_x3;         // 3x3 on conv_bf16.hip / gemm1x1_x3.hip
+    CgTile ft; int fsp;                            // forward: tile (trip / gather), reduction slabs (trip)
+    int wmt, wnt, wchunks, wsplits;                // weight gradient (trip / gather): tiles of 64 x (96 | 64), pixel chunks, slabs
+    StemArgs sa;                                   // stem: tiles, blocks
+    bool dx, dx_bf16; int dxsp;                    // data gradient: exists, on conv_bf16.hip, output-channel slabs
+};
+static bool cg_plan(int B, int Ci, int Co, int Hi, int Wi, int ks, CgPlan& p) {
+    if (!cg_ok(B, Ci, Co, Hi, Wi, ks)) return false;
+    p = CgPlan{};
+    p.K = Ci * ks * ks; p.Kp = cg_kp(Ci, ks);
+    p.wpad = p.Kp != p.K;                // stem: rows of 147 / 294 floats are neither 16-byte aligned nor a multiple of the chunk
+    p.stem = stem_ok(Ci, Co, ks);
+    p.trip = !p.stem && trip_ok(Ci, ks);
+    p.stem_x3 = p.stem && stem_x3_enabled() && p.wpad;
+    const bool b16 = ks == 3 && matrix_precision() == DC_PREC_BF16;
+    p.fwd_bf16 = p.dw_bf16 = b16 && c3b_eligible(Ci, 0, 0, Hi, Wi, 2);
+    p.fwd_x3 = !p.fwd_bf16 && ks == 3 && cg_x3_enabled() && g1x3_conv3s2_ok(B, Ci, Co, Hi, Wi);
+    p.dw_x3 = !p.dw_bf16 && ks == 3 && cg_x3_enabled() && g1x3_conv3s2_wgrad_ok(B, Ci, Co, Hi, Wi);
+    const int N = B * (Hi / 2) * (Wi / 2);
+    p.fsp = 1;
+    if (p.stem) {
+        p.sa = stem_args(B, Ci, Co, Hi, Wi);
+    } else {
+        if (p.trip) p.fsp = cg_fwd3_plan(B, Ci, Co, Hi, Wi, p.ft);
+        else p.ft = cg_pick(Co, N);
+        p.wchunks = ceil_div(N, GKC);
+        p.wmt = ceil_div(Co, 64); p.wnt = ceil_div(p.K, p.trip ? 96 : 64);
+        p.wsplits = cg_wsplits(p.wmt * p.wnt, p.wchunks);
     }
+    p.dx = ks == 3 && !(Ci & 3) && !(Co % GKC);
+    p.dx_bf16 = p.dx && b16 && c3b_eligible(Co, 0, 1, Hi, Wi, 1);
+    p.dxsp = p.dx ? cg_dgrad3_splits(B, Ci, Co, Hi, Wi) : 0;
+    return true;
+}
+
+extern "C" int dc_convs2_plan_query(int B, int Ci, int Co, int Hi, int Wi, int ksize, int raw_frames, dc_convs2_plan* plan) {
+    CgPlan p;
+    if (!plan || !cg_plan(B, Ci, Co, Hi, Wi, ksize, p) || (raw_frames && !p.stem)) return DC_EINVAL;
+    *plan = dc_convs2_plan{};
+    const bool f32_fwd = !p.fwd_bf16 && !p.fwd_x3, f32_dw = !p.dw_bf16 && !p.dw_x3;
+    plan->fwd = p.fwd_bf16 ? DC_S2_FWD_BF16 : p.fwd_x3 ? DC_S2_FWD_G1X3 : p.stem ? (p.stem_x3 ? DC_S2_FWD_STEM_X3 : DC_S2_FWD_STEM_F32)
+              : p.trip ? DC_S2_FWD_TRIP : DC_S2_FWD_GATHER;
+    if (f32_fwd && !p.stem) { plan->fwd_mt = p.ft.mt; plan->fwd_nt = p.ft.nt; }
+    if (f32_fwd && p.trip) plan->fwd_slabs = p.fsp;
+    plan->fwd_wpad = f32_fwd && p.wpad;
+    plan->dw = p.dw_bf16 ? DC_S2_DW_BF16 : p.dw_x3 ? DC_S2_DW_G1X3 : p.stem ? DC_S2_DW_STEM : p.trip ? DC_S2_DW_TRIP : DC_S2_DW_GATHER;
+    if (f32_dw && p.stem) {
+        plan->dw_blocks = p.sa.nblocks; plan->dw_tiles_per_block = ceil_div(p.sa.ntiles, p.sa.nblocks);
+        plan->dw_reduce = DC_S2_RED_16B;
+    } else if (f32_dw) {
+        plan->dw_slabs = p.wsplits;
+        plan->dw_reduce = p.wsplits > 1 ? ((Co * p.K) % 4 == 0 ? DC_S2_RED_16B : DC_S2_RED_SCALAR) : DC_S2_RED_NONE;
+    }
+    plan->dx = !p.dx ? DC_S2_DX_NONE : p.dx_bf16 ? DC_S2_DX_BF16 : DC_S2_DX_PARITY;
+    if (plan->dx == DC_S2_DX_PARITY) plan->dx_slabs = p.dxsp;
+    return DC_OK;
+}
+
+extern "C" size_t dc_convs2_fwd_workspace(int B, int Ci, int Co, int Hi, int Wi, int ksize) {
+    CgPlan p;
+    if (!cg_plan(B, Ci, Co, Hi, Wi, ksize, p)) return 0;
+    const size_t b16 = ksize == 3 ? c3b_weights_bytes(Ci, Co) : 0;
+    const size_t slabs = p.fsp > 1 ? (size_t)p.fsp * B * Co * (Hi / 2) * (Wi / 2) * sizeof(float) : 0;
     // (7x7 stem: the zero-padded fp32 weights + their three bf16 pieces for the split-operand forward)
-    const size_t wpad = Kp == K ? (size_t)16 : (size_t)Co * Kp * sizeof(float) + (ksize == 7 ? (size_t)Co * Kp * 6 + 512 : 0);
+    const size_t wpad = !p.wpad ? (size_t)16 : (size_t)Co * p.Kp * sizeof(float) + (ksize == 7 ? (size_t)Co * p.Kp * 6 + 512 : 0);
     const size_t x3 = ksize == 3 && g1x3_conv3s2_ok(B, Ci, Co, Hi, Wi) ? g1x3_conv3s2_fwd_ws(Ci, Co) : 0;
     return std::max(std::max(std::max(wpad, b16), slabs), x3);
 }
 
 extern "C" int dc_convs2_fwd(const float* x, const float* weight, float* y, void* ws, int B, int Ci, int Co, int Hi, int Wi, int ksize,
                              void* stream) {
-    if (!x || !weight || !y || !ws || !cg_ok(B, Ci, Co, Hi, Wi, ksize)) return DC_EINVAL;
+    CgPlan pl;
+    if (!x || !weight || !y || !ws || !cg_plan(B, Ci, Co, Hi, Wi, ksize, pl)) return DC_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (ksize == 3 && matrix_precision() == DC_PREC_BF16 && c3b_eligible(Ci, 0, 0, Hi, Wi, 2))      // bf16 matrix cores (conv_bf16.hip)
+    if (pl.fwd_bf16)                                                                                // bf16 matrix cores (conv_bf16.hip)
         return c3b_conv(x, Ci, 0, nullptr, 0, weight, Co, Ci, 0, 0, nullptr, y, ws, B, Hi, Wi, ACT_NONE, PAD_ZERO, 2, st);
-    if (ksize == 3 && cg_x3_enabled() && g1x3_conv3s2_ok(B, Ci, Co, Hi, Wi)) return g1x3_conv3s2_fwd(x, weight, y, ws, B, Ci, Co, Hi, Wi, st);
+    if (pl.fwd_x3) return g1x3_conv3s2_fwd(x, weight, y, ws, B, Ci, Co, Hi, Wi, st);
     CgArgs a{};
     a.x = x; a.out = y; a.B = B; a.Ci = Ci; a.Co = Co; a.Hi = Hi; a.Wi = Wi; a.Ho = Hi / 2; a.Wo = Wi / 2;
-    a.K = Ci * ksize * ksize; a.Kp = cg_kp(Ci, ksize);
+    a.K = pl.K; a.Kp = pl.Kp;
     a.xbytes = (unsigned)((size_t)B * Ci * Hi * Wi * sizeof(float));
-    if (a.Kp != a.K) {       // stem: rows of 147 / 294 floats are neither 16-byte aligned nor a multiple of the chunk
+    if (pl.wpad) {
         hipLaunchKernelGGL(cg_wpad_kernel, dim3(ceil_div(Co * a.Kp, 256)), dim3(256), 0, st, weight, (float*)ws, Co, a.K, a.Kp);
         DC_CHECK_LAUNCH();
         a.w = (const float*)ws;
     } else {
         a.w = weight;
     }
-    if (stem_ok(Ci, Co, ksize)) {
-        StemArgs sa = stem_args(B, Ci, Co, Hi, Wi);
+    if (pl.stem) {
+        StemArgs sa = pl.sa;
         sa.x = x; sa.w = a.w; sa.out = y;
         hipEvent_t pe = conv_prof_begin(PROF_STEM, 2.0 * B * (double)Co * a.K * a.Ho * a.Wo, 2.0 * B * (double)Co * sa.Kp * a.Ho * a.Wo,
                                         4.0 * ((double)B * Ci * Hi * Wi + (double)B * Co * a.Ho * a.Wo + (double)Co * a.K), st);
-        if (stem_x3_enabled() && a.Kp != a.K) {
+        if (pl.stem_x3) {
             const int rc = stem_fwd_x3_launch<false>(sa, ws, st);
             if (rc != DC_OK) return rc;
         } else {
@@ -1118,9 +1183,9 @@ extern "C" int dc_convs2_fwd(const float* x, const float* weight, float* y, void
         return DC_OK;
     }
     const int N = B * a.Ho * a.Wo;
-    if (trip_ok(Ci, ksize)) {
-        CgTile t;
-        const int sp = cg_fwd3_plan(B, Ci, Co, Hi, Wi, t);
+    if (pl.trip) {
+        const CgTile t = pl.ft;
+        const int sp = pl.fsp;
         if (sp > 1) a.out = (float*)ws;            // (Kp == K for the 3x3: the workspace holds nothing else on this path)
         a.mtiles = ceil_div(Co, 64); a.ntiles = ceil_div(N, 32 * t.nt);
         const size_t lds3 = ((size_t)64 * (96 + RP) + (size_t)96 * (t.nt == 4 ? 128 : 80)) * sizeof(float);
@@ -1141,7 +1206,7 @@ extern "C" int dc_convs2_fwd(const float* x, const float* weight, float* y, void
         }
         return DC_OK;
     }
-    const CgTile t = cg_pick(Co, N);
+    const CgTile t = pl.ft;
     a.mtiles = ceil_div(Co, 32 * t.mt); a.ntiles = ceil_div(N, 32 * t.nt);
     const dim3 grid(a.mtiles * a.ntiles);
     const size_t lds = cg_lds_fwd(t);
@@ -1160,14 +1225,11 @@ extern "C" int dc_convs2_fwd(const float* x, const float* weight, float* y, void
 }
 
 extern "C" size_t dc_convs2_wgrad_workspace(int B, int Ci, int Co, int Hi, int Wi, int ksize) {
-    if (!cg_ok(B, Ci, Co, Hi, Wi, ksize)) return 0;
-    const int K = Ci * ksize * ksize;
-    if (stem_ok(Ci, Co, ksize)) {
-        const StemArgs sa = stem_args(B, Ci, Co, Hi, Wi);
-        return (size_t)sa.nblocks * 64 * sa.Kp * sizeof(float);
-    }
-    const int tiles = ceil_div(Co, 64) * ceil_div(K, trip_ok(Ci, ksize) ? 96 : 64);
-    const int splits = cg_wsplits(tiles, ceil_div(B * (Hi / 2) * (Wi / 2), GKC));
+    CgPlan p;
+    if (!cg_plan(B, Ci, Co, Hi, Wi, ksize, p)) return 0;
+    const int K = p.K;
+    if (p.stem) return (size_t)p.sa.nblocks * 64 * p.sa.Kp * sizeof(float);
+    const int splits = p.wsplits;
     const size_t b16 = ksize == 3 ? (size_t)c3b_wgrad_split(B, Hi / 2, Wi / 2, Co, Ci, 2) * Co * K * sizeof(float) : 0;
     const size_t x3 = ksize == 3 && g1x3_conv3s2_wgrad_ok(B, Ci, Co, Hi, Wi) ? g1x3_conv3s2_wgrad_ws(B, Ci, Co, Hi, Wi) : 0;
     return std::max(std::max(splits > 1 ? (size_t)splits * Co * K * sizeof(float) : (size_t)16, b16), x3);
@@ -1175,17 +1237,17 @@ extern "C" size_t dc_convs2_wgrad_workspace(int B, int Ci, int Co, int Hi, int W
 
 extern "C" int dc_convs2_wgrad(const float* x, const float* gy, float* dweight, void* ws, int B, int Ci, int Co, int Hi, int Wi,
                                int ksize, void* stream) {
-    if (!x || !gy || !dweight || !ws || !cg_ok(B, Ci, Co, Hi, Wi, ksize)) return DC_EINVAL;
+    CgPlan pl;
+    if (!x || !gy || !dweight || !ws || !cg_plan(B, Ci, Co, Hi, Wi, ksize, pl)) return DC_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (ksize == 3 && matrix_precision() == DC_PREC_BF16 && c3b_eligible(Ci, 0, 0, Hi, Wi, 2)) {    // bf16 matrix cores
+    if (pl.dw_bf16) {                                                                               // bf16 matrix cores
         const int sp = c3b_wgrad_split(B, Hi / 2, Wi / 2, Co, Ci, 2);
         const int rc = c3b_wgrad(x, Ci, 0, nullptr, 0, gy, (float*)ws, sp, B, Co, Hi, Wi, PAD_ZERO, 2, st);
         return rc != DC_OK ? rc : conv_wreduce((const float*)ws, nullptr, dweight, nullptr, sp, Co * Ci * 9, 0, st);
     }
-    if (ksize == 3 && cg_x3_enabled() && g1x3_conv3s2_wgrad_ok(B, Ci, Co, Hi, Wi))
-        return g1x3_conv3s2_wgrad(x, gy, dweight, ws, B, Ci, Co, Hi, Wi, st);
-    if (stem_ok(Ci, Co, ksize)) {
-        StemArgs sa = stem_args(B, Ci, Co, Hi, Wi);
+    if (pl.dw_x3) return g1x3_conv3s2_wgrad(x, gy, dweight, ws, B, Ci, Co, Hi, Wi, st);
+    if (pl.stem) {
+        StemArgs sa = pl.sa;
         sa.x = x; sa.gy = gy; sa.out = (float*)ws;
         const size_t lds = stem_lds_wgrad(Ci);
         hipEvent_t pe = conv_prof_begin(PROF_STEM, 2.0 * B * (double)Co * sa.K * (Hi / 2) * (Wi / 2), 2.0 * B * (double)Co * sa.Kp * (Hi / 2) * (Wi / 2),
@@ -1200,12 +1262,12 @@ extern "C" int dc_convs2_wgrad(const float* x, const float* gy, float* dweight, 
     }
     CgArgs a{};
     a.x = x; a.gy = gy; a.B = B; a.Ci = Ci; a.Co = Co; a.Hi = Hi; a.Wi = Wi; a.Ho = Hi / 2; a.Wo = Wi / 2;
-    a.K = Ci * ksize * ksize; a.Kp = a.K;
+    a.K = pl.K; a.Kp = a.K;
     a.xbytes = (unsigned)((size_t)B * Ci * Hi * Wi * sizeof(float));
-    a.chunks = ceil_div(B * a.Ho * a.Wo, GKC);
-    const bool trip = trip_ok(Ci, ksize);
-    a.mtiles = ceil_div(Co, 64); a.ntiles = ceil_div(a.K, trip ? 96 : 64);
-    a.splits = cg_wsplits(a.mtiles * a.ntiles, a.chunks);
+    a.chunks = pl.wchunks;
+    const bool trip = pl.trip;
+    a.mtiles = pl.wmt; a.ntiles = pl.wnt;
+    a.splits = pl.wsplits;
     a.out = a.splits > 1 ? (float*)ws : dweight;
     const dim3 grid(a.mtiles * a.ntiles, a.splits);
     const size_t lds = trip ? (size_t)2 * (64 + 96) * (GKC + RP) * sizeof(float) : cg_lds_wgrad({2, 2});
@@ -1229,13 +1291,15 @@ extern "C" int dc_convs2_wgrad(const float* x, const float* gy, float* dweight, 
 }
 
 // ---- the stem on the RAW frames: normalisation and temporal pair concat folded into the patch loader -------------------------
-static int stem_frames(StemArgs& sa, const float* const* frames, int nf, float mean, float stdv, int Bf, int Hi, int Wi, int Co) {
+static int stem_frames(StemArgs& sa, bool& x3, const float* const* frames, int nf, float mean, float stdv, int Bf, int Hi, int Wi, int Co) {
     if (!frames || nf < 1 || nf > 3 || !(stdv > 0.f) || Bf <= 0) return DC_EINVAL;
     const int B = nf == 3 ? 2 * Bf : Bf, Ci = nf == 1 ? 3 : 6;
-    if (!cg_ok(B, Ci, Co, Hi, Wi, 7) || !stem_ok(Ci, Co, 7)) return DC_EINVAL;
+    CgPlan pl;
+    if (!cg_plan(B, Ci, Co, Hi, Wi, 7, pl) || !pl.stem) return DC_EINVAL;
     for (int i = 0; i < nf; ++i)
         if (!frames[i]) return DC_EINVAL;
-    sa = stem_args(B, Ci, Co, Hi, Wi);
+    sa = pl.sa;
+    x3 = pl.stem_x3;
     sa.nf = nf; sa.Bf = Bf; sa.mean = mean; sa.stdv = stdv;
     for (int i = 0; i < 3; ++i) sa.f[i] = frames[i < nf ? i : 0];
     return DC_OK;
@@ -1250,7 +1314,8 @@ extern "C" int dc_stem_supported(int nf, int Bf, int Co, int Hi, int Wi) {
 extern "C" int dc_stem_fwd(const float* const* frames, int nf, float mean, float stdv, const float* weight, float* y, void* ws, int Bf,
                            int Hi, int Wi, int Co, void* stream) {
     StemArgs sa{};
-    if (!weight || !y || !ws || stem_frames(sa, frames, nf, mean, stdv, Bf, Hi, Wi, Co) != DC_OK) return DC_EINVAL;
+    bool x3 = false;
+    if (!weight || !y || !ws || stem_frames(sa, x3, frames, nf, mean, stdv, Bf, Hi, Wi, Co) != DC_OK) return DC_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(cg_wpad_kernel, dim3(ceil_div(Co * sa.Kp, 256)), dim3(256), 0, st, weight, (float*)ws, Co, sa.K, sa.Kp);
     DC_CHECK_LAUNCH();
@@ -1258,7 +1323,7 @@ extern "C" int dc_stem_fwd(const float* const* frames, int nf, float mean, float
     const double npix = (double)sa.B * (Hi / 2) * (Wi / 2);
     hipEvent_t pe = conv_prof_begin(PROF_STEM, 2.0 * npix * Co * sa.K, 2.0 * npix * Co * sa.Kp,
                                     4.0 * ((double)sa.B * sa.Ci * Hi * Wi + npix * Co + (double)Co * sa.K), st);
-    if (stem_x3_enabled()) {
+    if (x3) {
         const int rc = stem_fwd_x3_launch<true>(sa, ws, st);
         if (rc != DC_OK) return rc;
     } else {
@@ -1272,7 +1337,8 @@ extern "C" int dc_stem_fwd(const float* const* frames, int nf, float mean, float
 extern "C" int dc_stem_wgrad(const float* const* frames, int nf, float mean, float stdv, const float* gy, float* dweight, void* ws,
                              int Bf, int Hi, int Wi, int Co, void* stream) {
     StemArgs sa{};
-    if (!gy || !dweight || !ws || stem_frames(sa, frames, nf, mean, stdv, Bf, Hi, Wi, Co) != DC_OK) return DC_EINVAL;
+    bool x3 = false;
+    if (!gy || !dweight || !ws || stem_frames(sa, x3, frames, nf, mean, stdv, Bf, Hi, Wi, Co) != DC_OK) return DC_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     sa.gy = gy; sa.out = (float*)ws;
     const size_t lds = stem_lds_wgrad(sa.Ci);
@@ -1302,26 +1368,28 @@ static int cg_dgrad3_splits(int B, int Ci, int Co, int Hi, int Wi) {
 }
 
 extern "C" size_t dc_convs2_dgrad_workspace(int B, int Ci, int Co, int Hi, int Wi, int ksize) {
-    if (!cg_ok(B, Ci, Co, Hi, Wi, ksize) || ksize != 3 || (Ci & 3) || Co % GKC) return 0;
-    const int sp = cg_dgrad3_splits(B, Ci, Co, Hi, Wi);
+    CgPlan p;
+    if (!cg_plan(B, Ci, Co, Hi, Wi, ksize, p) || !p.dx) return 0;
+    const int sp = p.dxsp;
     const size_t wt = ((size_t)9 * Co * Ci * sizeof(float) + 255) & ~(size_t)255;
     return std::max(wt + (sp > 1 ? (size_t)sp * B * Ci * Hi * Wi * sizeof(float) : 0), c3b_weights_bytes(Ci, Co));
 }
 
 extern "C" int dc_convs2_dgrad(const float* gy, const float* weight, float* dx, void* ws, int B, int Ci, int Co, int Hi, int Wi,
                                int ksize, void* stream) {
-    if (!gy || !weight || !dx || !ws || !dc_convs2_dgrad_workspace(B, Ci, Co, Hi, Wi, ksize)) return DC_EINVAL;
+    CgPlan pl;
+    if (!gy || !weight || !dx || !ws || !cg_plan(B, Ci, Co, Hi, Wi, ksize, pl) || !pl.dx) return DC_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     // bf16 matrix cores: stride-1 convolution of the DILATED g' with the rotated, transposed filter (conv_bf16.hip).  Three
     // quarters of its multiplies meet a structural zero -- at 16x the fp32 matrix rate the kernel is bound by its HBM reads
-    if (matrix_precision() == DC_PREC_BF16 && c3b_eligible(Co, 0, 1, Hi, Wi, 1))
+    if (pl.dx_bf16)
         return c3b_conv(gy, Co, 3, nullptr, 0, weight, Co, Ci, 1, 0, nullptr, dx, ws, B, Hi, Wi, ACT_NONE, PAD_ZERO, 1, st);
     hipLaunchKernelGGL(cg_wt3_kernel, dim3(ceil_div(9 * Co * Ci, 256)), dim3(256), 0, st, weight, (float*)ws, Co, Ci);
     DC_CHECK_LAUNCH();
     CgArgs a{};
     a.w = (const float*)ws; a.gy = gy; a.out = dx; a.B = B; a.Ci = Ci; a.Co = Co; a.Hi = Hi; a.Wi = Wi; a.Ho = Hi / 2; a.Wo = Wi / 2;
     const int N = B * a.Ho * a.Wo;
-    const int sp = cg_dgrad3_splits(B, Ci, Co, Hi, Wi);
+    const int sp = pl.dxsp;
     float* slabs = (float*)((char*)ws + (((size_t)9 * Co * Ci * sizeof(float) + 255) & ~(size_t)255));
     if (sp > 1) a.out = slabs;
     const CgTile t{2, 2};

@@ -98,6 +98,12 @@ class Conv3x3Plan(Structure):
     _fields_ = [(n, c_int32) for n in ("fwd", "fwd_v2", "fwd_mr", "gprime", "dx", "ring", "dw", "db", "bwd_v2", "dx_mr", "dw_mr", "split")]
 
 
+class ConvS2Plan(Structure):
+    """Mirror of `dc_convs2_plan` (include/depthcore.h: dc_convs2_plan_query); the values are the DC_S2_* enums there."""
+    _fields_ = [(n, c_int32) for n in ("fwd", "fwd_mt", "fwd_nt", "fwd_slabs", "fwd_wpad", "dw", "dw_slabs", "dw_blocks",
+                                       "dw_tiles_per_block", "dw_reduce", "dx", "dx_slabs")]
+
+
 _lib = None
 
 
@@ -203,6 +209,7 @@ def _sig(lib):
         "dc_convs2_dgrad": (i, [p, p, p, p, i, i, i, i, i, i, p]),
         "dc_convs2_wgrad_workspace": (z, [i, i, i, i, i, i]),
         "dc_convs2_wgrad": (i, [p, p, p, p, i, i, i, i, i, i, p]),
+        "dc_convs2_plan_query": (i, [i, i, i, i, i, i, i, POINTER(ConvS2Plan)]),
         "dc_conv2d_direct_fwd": (i, [p, p, p, p, i, i, i, i, i, i, i, i, p]),
         "dc_conv2d_direct_dgrad": (i, [p, p, p, i, i, i, i, i, i, i, i, p]),
         "dc_conv2d_direct_wgrad": (i, [p, p, p, p, i, i, i, i, i, i, i, i, p]),
