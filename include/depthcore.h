@@ -214,6 +214,25 @@ int dc_set_photo_full(int mode);
 /* The current process-wide setting.  Callers that may see the setter between a forward and its backward read it once, at the forward,
  * and pin it in the desc with DC_OPT_PHOTO_FULL / DC_OPT_PHOTO_SPLIT (depthcore/ops.py does). */
 int dc_get_photo_full(void);
+/* How dc_photo_fwd / dc_photo_bwd cut one descriptor's images into blocks, filled from the function the launches size their grids
+ * with (csrc/photo.hip: carve) under the desc's flags and the current dc_set_photo_full mode.  Reads sizes and flags only (no
+ * pointer of the desc), launches nothing and makes no HIP call.  DC_EINVAL for a NULL desc / plan and for the sizes and flag
+ * combinations the launches refuse.  Tests and diagnostics; the launches need no query.
+ *   a "strip" is the run of image columns one wave owns (strip k starts at column k * strip width; the waves also read halo
+ *   columns on each side), a "row block" the run of rows it marches; the last strip / block of an image may be ragged. */
+typedef struct dc_photo_plan {
+    int32_t strip_f, strip_g, strip_p;             /* columns owned per strip: evaluation forward and identity_kernel (62), training
+                                                      forward photo_fwdg_kernel (60), pointwise backward photo_bwdg_kernel (64) */
+    int32_t strips_f, strips_g, strips_p;          /* strips per image row of the three */
+    int32_t rows_f, rows_g, rows_p, rows_id;       /* rows per block: the three kernels above, and identity_kernel's own */
+    int32_t rowblocks_f, rowblocks_g, rowblocks_p, rowblocks_id;
+    int32_t sm_chunk, nchunk;                      /* smooth_fwd_kernel: pixels of one scale image per block (row-major, so a chunk
+                                                      ends mid-row), blocks per image at scale 0 (the launch's grid.x) */
+    int32_t full;                                  /* 1: the training forward goes all the way and photo_bwdg_kernel does not run */
+    int32_t dg_tw[DC_MAX_SCALES], dg_th[DC_MAX_SCALES];            /* disp_grad_kernel: tile of scale-s pixels per block ... */
+    int32_t dg_tiles_x[DC_MAX_SCALES], dg_tiles_y[DC_MAX_SCALES];  /* ... and tiles per scale-s image */
+} dc_photo_plan;
+int dc_photo_plan_query(const dc_photo_desc* d, dc_photo_plan* plan);
 
 /* Measurement hook (bench.py `roofline`): when enabled, dc_photo_fwd / dc_photo_bwd bracket their
  * dominant kernel (photo_fwd_kernel / photo_bwd_kernel) AND their whole launch chain (forward: identity + smoothness +

@@ -1543,9 +1543,22 @@ static Carve carve(const dc_photo_desc* d) {
     return c;
 }
 
+// The checks of fill_args that read only the sizes and flags (dc_photo_plan_query refuses exactly these).
+static bool geometry_ok(const dc_photo_desc* d) {
+    return d && d->B > 0 && d->H >= 4 && d->W >= 4 && d->num_scales >= 1 && d->num_scales <= DC_MAX_SCALES;
+}
+static bool flags_ok(const dc_photo_desc* d) {
+    if ((d->flags & DC_OPT_PRED_MASK) && !(d->flags & DC_OPT_NO_AUTOMASK)) return false;       // trainer.py:116-117
+    return !((d->flags & DC_OPT_PHOTO_SPLIT) && (d->flags & DC_OPT_PHOTO_FULL));
+}
+// exact 2^s pyramid of at least 2 x 2 (the reference asserts H, W multiples of 32, trainer.py:37-38)
+static bool scale_ok(const dc_photo_desc* d, int s) {
+    const int hs = d->H >> s, ws = d->W >> s;
+    return hs >= 2 && ws >= 2 && (hs << s) == d->H && (ws << s) == d->W;
+}
+
 static int fill_args(const dc_photo_desc* d, PhotoArgs& a, Carve& c, bool backward) {
-    if (!d || d->B <= 0 || d->H < 4 || d->W < 4 || d->num_scales < 1 || d->num_scales > DC_MAX_SCALES)
-        return DC_EINVAL;
+    if (!geometry_ok(d)) return DC_EINVAL;
     int nTs = 0;                                                     // per-scale poses: all 2 * num_scales or none
     for (int s = 0; s < d->num_scales; ++s) nTs += (d->T_scale[s][0] ? 1 : 0) + (d->T_scale[s][1] ? 1 : 0);
     if (nTs != 0 && nTs != 2 * d->num_scales) return DC_EINVAL;
@@ -1553,8 +1566,7 @@ static int fill_args(const dc_photo_desc* d, PhotoArgs& a, Carve& c, bool backwa
         !d->workspace)
         return DC_EINVAL;
     if (!(d->min_depth > 0.f) || !(d->max_depth > d->min_depth)) return DC_EINVAL;
-    if ((d->flags & DC_OPT_PRED_MASK) && !(d->flags & DC_OPT_NO_AUTOMASK)) return DC_EINVAL;    // trainer.py:116-117
-    if ((d->flags & DC_OPT_PHOTO_SPLIT) && (d->flags & DC_OPT_PHOTO_FULL)) return DC_EINVAL;
+    if (!flags_ok(d)) return DC_EINVAL;
     const int npk = (d->packed[0] ? 1 : 0) + (d->packed[1] ? 1 : 0) + (d->packed[2] ? 1 : 0);
     if (npk != 0 && npk != 3) return DC_EINVAL;                      // all three or none
     for (int k = 0; k < npk; ++k)
@@ -1580,9 +1592,7 @@ static int fill_args(const dc_photo_desc* d, PhotoArgs& a, Carve& c, bool backwa
         if (!d->disp[s] || !d->color_s[s] || !d->argmin[s]) return DC_EINVAL;
         a.disp[s] = d->disp[s]; a.color_s[s] = d->color_s[s];
         a.hs[s] = d->H >> s; a.ws[s] = d->W >> s;
-        if (a.hs[s] < 2 || a.ws[s] < 2) return DC_EINVAL;
-        // exact 2^s pyramid (the reference asserts H, W multiples of 32, trainer.py:37-38)
-        if ((a.hs[s] << s) != d->H || (a.ws[s] << s) != d->W) return DC_EINVAL;
+        if (!scale_ok(d, s)) return DC_EINVAL;
         a.ry[s] = (float)a.hs[s] / (float)d->H;
         a.rx[s] = (float)a.ws[s] / (float)d->W;
         a.noise[s] = d->noise[s]; a.argmin[s] = d->argmin[s];
@@ -1701,6 +1711,28 @@ extern "C" int dc_profile_collect(double* fwd_ms, int* fwd_launches, double* bwd
 extern "C" size_t dc_photo_workspace(const dc_photo_desc* d) {
     if (!d || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->num_scales < 1 || d->num_scales > DC_MAX_SCALES) return 0;
     return carve(d).total;
+}
+
+extern "C" int dc_photo_plan_query(const dc_photo_desc* d, dc_photo_plan* plan) {
+    if (!plan || !geometry_ok(d) || !flags_ok(d)) return DC_EINVAL;
+    for (int s = 0; s < d->num_scales; ++s)
+        if (!scale_ok(d, s)) return DC_EINVAL;
+    const Carve c = carve(d);
+    *plan = dc_photo_plan{};
+    plan->strip_f = 62; plan->strip_g = 60; plan->strip_p = 64;
+    plan->strips_f = c.strips_f; plan->strips_g = c.strips_b; plan->strips_p = c.strips_p;
+    plan->rows_f = c.rows_f; plan->rows_g = c.rows_g; plan->rows_p = c.rows_p; plan->rows_id = ID_ROWS;
+    plan->rowblocks_f = c.rowblocks_f; plan->rowblocks_g = c.rowblocks_g; plan->rowblocks_p = c.rowblocks_p;
+    plan->rowblocks_id = ceil_div(d->H, ID_ROWS);
+    plan->sm_chunk = SM_CHUNK; plan->nchunk = c.nchunk;
+    plan->full = c.full ? 1 : 0;
+    for (int s = 0; s < d->num_scales; ++s) {        // the grid dc_photo_bwd builds for disp_grad_kernel
+        plan->dg_tw[s] = DG_W >> s;
+        plan->dg_th[s] = s == 0 ? DG_H0 : DG_H >> s;
+        plan->dg_tiles_x[s] = ceil_div(d->W >> s, plan->dg_tw[s]);
+        plan->dg_tiles_y[s] = ceil_div(d->H >> s, plan->dg_th[s]);
+    }
+    return DC_OK;
 }
 
 extern "C" int dc_photo_fwd(const dc_photo_desc* d, void* stream) {

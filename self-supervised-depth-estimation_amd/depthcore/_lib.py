@@ -62,6 +62,15 @@ class PhotoDesc(Structure):
     ]
 
 
+class PhotoPlan(Structure):
+    """Mirror of `dc_photo_plan` (include/depthcore.h: dc_photo_plan_query)."""
+    _fields_ = [(n, c_int32) for n in ("strip_f", "strip_g", "strip_p", "strips_f", "strips_g", "strips_p",
+                                       "rows_f", "rows_g", "rows_p", "rows_id",
+                                       "rowblocks_f", "rowblocks_g", "rowblocks_p", "rowblocks_id",
+                                       "sm_chunk", "nchunk", "full")] + \
+               [(n, c_int32 * MAX_SCALES) for n in ("dg_tw", "dg_th", "dg_tiles_x", "dg_tiles_y")]
+
+
 class AttnMap(Structure):
     """Mirror of `dc_attn_map`: where each input channel of an AttentionConv lives (include/depthcore.h)."""
     _fields_ = [("ptr", _F * 4), ("batch_stride", ctypes.c_longlong * 4), ("mode", c_int32 * 4)]
@@ -139,6 +148,7 @@ def _sig(lib):
         "dc_photo_fwd": (i, [POINTER(PhotoDesc), p]),
         "dc_photo_bwd": (i, [POINTER(PhotoDesc), p]),
         "dc_photo_algorithmic_bytes": (c_double, [POINTER(PhotoDesc), i]),
+        "dc_photo_plan_query": (i, [POINTER(PhotoDesc), POINTER(PhotoPlan)]),
         "dc_conv3x3_fwd_workspace": (z, [i, i, i, i, i, i]),
         "dc_conv3x3_fwd": (i, [p, i, i, p, i, p, p, p, p, i, i, i, i, i, i, p]),
         "dc_conv3x3_bwd_workspace": (z, [i, i, i, i, i, i]),
