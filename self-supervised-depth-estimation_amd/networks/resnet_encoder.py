@@ -4,8 +4,8 @@
 The reference delegates the trunk to `torchvision.models.resnet*`; torchvision is not a
 dependency here, so the ResNet v1.5 trunk is stated directly (same module names, hence the same
 state_dict keys: `encoder.conv1.weight`, `encoder.layer1.0.bn1.running_mean`, ..., `encoder.fc.*`).
-Convolutions go through `conv_impl` so that the MFMA implicit-GEMM kernels can be swapped in
-without touching the module tree.
+Convolutions go through `_conv`, which runs each on the kernel family `_route` names, so that the
+MFMA kernels take over without touching the module tree.
 """
 import os
 
@@ -50,27 +50,47 @@ GRAD_FORK = True      # residual blocks without a downsample branch: the skip's 
 SKIP_SUMS = os.environ.get("DC_GRAD_SUMS", "1") != "0"   # (DC_GRAD_SUMS=0: autograd's elementwise sums, same-box A/Bs) feature maps carry an ops.SkipSum: the decoder's skip-connection gradient is added by the map's primary consumer
 
 
+def _route(conv, x):
+    """The kernel family of one nn.Conv2d call of the trunk -- the only place that inspects a convolution to pick one:
+    "wino" stride-1 3x3 on dc_wino3x3_* (84 % of a ResNet-18 trunk's multiplies), "g1" 1x1 on the NCHW MFMA GEMMs
+    (dc_pointwise_*: Bottleneck conv1 / conv3 and every `downsample` branch), "s2" the 7x7 / 2 stem and the 3x3 / 2
+    convolutions on dc_convs2_*, "direct" everything else (dc_conv2d_direct_*, or a refusal in `_conv`).  "wino" and "g1"
+    have a data-gradient kernel with the addend epilogue.  Reads the module's attributes and x.shape / dtype / is_cuda /
+    requires_grad only (host queries, nothing of the device)."""
+    if not (x.is_cuda and x.dtype == torch.float32 and conv.groups == 1 and conv.bias is None):
+        return "direct"
+    k, s_, p_ = conv.kernel_size, conv.stride, conv.padding
+    if WINO_TRUNK and k == (3, 3) and s_ == (1, 1) and p_ == (1, 1) and conv.dilation == (1, 1) and x.shape[-1] % 2 == 0:
+        return "wino"
+    if (GEMM_1X1 and k == (1, 1) and p_ == (0, 0)
+            and (s_ == (1, 1) or (s_ == (2, 2) and x.shape[-1] % 2 == 0 and x.shape[-2] % 2 == 0))):
+        return "g1"
+    if (CONV_S2 and s_ == (2, 2) and k in ((3, 3), (7, 7)) and p_ == (k[0] // 2,) * 2 and conv.dilation == (1, 1)
+            and _ops.conv_s2_supported(x, conv.weight)
+            and ((k == (7, 7) and not x.requires_grad)        # (the stem kernels have no data gradient)
+                 or (k == (3, 3) and conv.in_channels % 4 == 0 and conv.out_channels % 32 == 0))):
+        return "s2"
+    return "direct"
+
+
+def _forkable(block, x):
+    """What every GradFork of a residual block needs: a training step on the GPU whose input wants a gradient, below 2 GiB."""
+    return (GRAD_FORK and block.training and x.is_cuda and x.requires_grad and x.dtype == torch.float32
+            and torch.is_grad_enabled() and x.numel() * 4 < 0x7fffffff)
+
+
 def _fork_for(block, x):
     """A GradFork for this call of a residual block, or None: training on the GPU, identity skip, an input that needs a
-    gradient, conv1 on a kernel with the addend epilogue (stride-1 3x3 Winograd or 1x1 GEMM) and a map below 2 GiB."""
-    c = block.conv1
-    if not (GRAD_FORK and block.downsample is None and block.training and x.is_cuda and x.requires_grad and x.dtype == torch.float32
-            and torch.is_grad_enabled() and c.stride == (1, 1) and c.groups == 1 and c.bias is None and x.numel() * 4 < 0x7fffffff):
-        return None
-    if c.kernel_size == (3, 3) and WINO_TRUNK and c.padding == (1, 1) and c.dilation == (1, 1) and x.shape[-1] % 2 == 0:
-        return _ops.GradFork()
-    if c.kernel_size == (1, 1) and GEMM_1X1 and c.padding == (0, 0):
-        return _ops.GradFork()
-    return None
+    gradient, a stride-1 conv1 on a kernel with the addend epilogue and a map below 2 GiB."""
+    ok = (block.downsample is None and _forkable(block, x) and block.conv1.stride == (1, 1)
+          and _route(block.conv1, x) in ("wino", "g1"))
+    return _ops.GradFork() if ok else None
 
 
 def _pair_fork_for(block, x):
     """A pair GradFork for a Bottleneck with a downsample branch (both consumers of x are 1x1 GEMM convolutions), or None."""
     c, d = block.conv1, block.downsample[0]
-    ok = (GRAD_FORK and GEMM_1X1 and block.training and x.is_cuda and x.requires_grad and x.dtype == torch.float32
-          and torch.is_grad_enabled() and x.numel() * 4 < 0x7fffffff
-          and all(m.kernel_size == (1, 1) and m.padding == (0, 0) and m.groups == 1 and m.bias is None for m in (c, d))
-          and c.stride == (1, 1) and d.stride in ((1, 1), (2, 2)) and (d.stride == (1, 1) or (x.shape[-1] % 2 == 0 and x.shape[-2] % 2 == 0)))
+    ok = _forkable(block, x) and c.stride == (1, 1) and _route(c, x) == "g1" and _route(d, x) == "g1"
     return _ops.GradFork(pair=True) if ok else None
 
 
@@ -78,38 +98,24 @@ def _basic_pair_fork(block, x):
     """A pair GradFork for a BasicBlock with a downsample branch (3x3 / 2 conv1 on dc_convs2_*, 1x1 / 2 `downsample` on the tiled
     GEMM whose data gradient takes addends), or None."""
     c, d = block.conv1, block.downsample[0]
-    B, Ci, H, W = x.shape
-    ok = (GRAD_FORK and GEMM_1X1 and CONV_S2 and block.training and x.is_cuda and x.requires_grad and x.dtype == torch.float32
-          and torch.is_grad_enabled() and x.numel() * 4 < 0x7fffffff and _ops._precision[0] == _ops.PRECISIONS["f32"]
-          and c.kernel_size == (3, 3) and c.stride == (2, 2) and c.padding == (1, 1) and c.groups == 1 and c.bias is None
-          and d.kernel_size == (1, 1) and d.stride == (2, 2) and d.padding == (0, 0) and d.groups == 1 and d.bias is None
-          and H % 2 == 0 and W % 2 == 0 and c.in_channels % 4 == 0 and c.out_channels % 32 == 0 and _ops.conv_s2_supported(x, c.weight))
+    ok = (_forkable(block, x) and _ops._precision[0] == _ops.PRECISIONS["f32"]
+          and c.kernel_size == (3, 3) and _route(c, x) == "s2" and d.stride == (2, 2) and _route(d, x) == "g1")
     return _ops.GradFork(pair=True) if ok else None
 
 
 def _conv(conv, x, fork=None, skip=None):
-    """nn.Conv2d call of the trunk: stride-1 3x3 on dc_wino3x3_* (84 % of a ResNet-18 trunk's multiplies), 1x1 on dc_conv1x1_*,
-    the 7x7 / 2 stem and the 3x3 / 2 convolutions on dc_convs2_*; shapes outside those kernels' 16-byte staging (odd or
-    tiny maps in tests) take dc_conv2d_direct_*.  On the GPU nothing reaches the framework's convolution."""
-    if (WINO_TRUNK and x.is_cuda and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
-            and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None and x.shape[-1] % 2 == 0
-            and x.dtype == torch.float32):
+    """nn.Conv2d call of the trunk on the kernel family `_route` names; shapes outside the tiled kernels' 16-byte staging (odd
+    or tiny maps in tests) take dc_conv2d_direct_*.  On the GPU nothing reaches the framework's convolution."""
+    route = _route(conv, x)
+    if route == "wino":
         return _ops.wino_conv3x3(x, conv.weight, fork)
-    if (GEMM_1X1 and x.is_cuda and conv.kernel_size == (1, 1) and conv.padding == (0, 0) and conv.groups == 1
-            and conv.bias is None and conv.stride in ((1, 1), (2, 2)) and x.dtype == torch.float32
-            and (conv.stride == (1, 1) or (x.shape[-1] % 2 == 0 and x.shape[-2] % 2 == 0))):
-        # Bottleneck conv1 / conv3 and every `downsample` branch: NCHW fp32-MFMA GEMMs (dc_conv1x1_*), no layout transposes
+    if route == "g1":
         return _ops.conv1x1(x, conv.weight, conv.stride[0], fork=fork, skip=skip)
-    if (CONV_S2 and x.is_cuda and conv.stride == (2, 2) and conv.kernel_size in ((3, 3), (7, 7)) and conv.groups == 1
-            and conv.padding == (conv.kernel_size[0] // 2,) * 2 and conv.dilation == (1, 1) and conv.bias is None
-            and x.dtype == torch.float32 and _ops.conv_s2_supported(x, conv.weight)
-            and ((conv.kernel_size == (7, 7) and not x.requires_grad)        # (the stem kernels have no data gradient)
-                 or (conv.kernel_size == (3, 3) and conv.in_channels % 4 == 0 and conv.out_channels % 32 == 0))):
-        # 7x7 / 2 stem and the 3x3 / 2 convolutions: implicit GEMMs on the matrix cores (dc_convs2_*)
+    if route == "s2":
         if fork is not None and (not fork.pair or conv.kernel_size != (3, 3)):
             raise _ops.DepthcoreError("GradFork handed to a strided convolution")
         return _ops.conv_s2(x, conv.weight, fork)
-    if fork is not None:  # (_fork_for mirrors the two conditions above; a fork nobody collects would lose the skip's gradient)
+    if fork is not None:  # (a fork nobody collects would lose the skip's gradient)
         raise _ops.DepthcoreError("GradFork handed to a convolution that does not run on a kernel with the addend epilogue")
     if not x.is_cuda:       # no CPU fallback anywhere in this package (layers.py): the oracle under oracle/ is the CPU statement
         raise _ops.DepthcoreError("convolution on a %s tensor: depthcore's modules compute on the GPU only" % x.device)
@@ -166,8 +172,7 @@ class BasicBlock(nn.Module):
         if self.downsample is None:
             return _bnf.bn_apply(y2, self.bn2, s2, res=x, groups=g, fork=fork, leave_link=link)
         d = self.downsample[0]
-        if (GEMM_1X1 and d.kernel_size == (1, 1) and d.padding == (0, 0) and d.groups == 1 and d.bias is None and d.stride in ((1, 1), (2, 2))
-                and (d.stride == (1, 1) or (x.shape[-1] % 2 == 0 and x.shape[-2] % 2 == 0))):
+        if _route(d, x) == "g1":
             yd, sd = _bnf.conv1x1(x, d.weight, d.stride[0], g)            # statistics epilogue on the tiled shapes
         else:
             yd, sd = _conv(d, x), None

@@ -93,6 +93,40 @@ def test_conv1x1_bias_act_vs_torch(B, Ci, Co, H, W, act):
         assert err <= 1e-5 * max(ref.abs().max().item(), 1e-6), "%s: %.3e" % (name, err)
 
 
+def test_plain_conv1x1_passes_no_fold_struct_and_the_fold_wrapper_passes_one():
+    """dc_pointwise_fwd picks its kernel family differently for bn == NULL and for a dc_bn_fold that asks for nothing
+    (csrc/pointwise.hip: pw_family): with a struct the split kernels are gated on their statistics layout for bn->groups.
+    At (2, 32, 4, 4) -> 32 channels under split mode 1 NULL takes the split kernels (Ci % 32 == 0, Co >= 32, P = 16) and
+    a struct with two groups cannot (B * P / 2 = 16 is no multiple of the 32-pixel statistics tile), so the two results
+    differ -- and ops.conv1x1 must be the former, bnfold.conv1x1 the latter, bit for bit."""
+    import ctypes
+    from depthcore import _lib, bnfold, ops
+    L = _lib.lib()
+    B, Ci, Co, H, W, s = 2, 32, 32, 4, 4, 1
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(B, Ci, H, W, generator=g).cuda()
+    w = (torch.randn(Co, Ci, 1, 1, generator=g) * (1.0 / Ci) ** 0.5).cuda()
+
+    def direct(f):
+        fp = ctypes.byref(f) if f is not None else None
+        y = torch.full((B, Co, H, W), float("nan"), device="cuda")
+        ws = torch.empty(L.dc_pointwise_workspace(_lib.PASS_FWD, fp, B, Ci, Co, H, W, s), dtype=torch.uint8, device="cuda")
+        assert L.dc_pointwise_fwd(x.data_ptr(), w.data_ptr(), None, y.data_ptr(), ws.data_ptr(), B, Ci, Co, H, W, s, 0, fp, None) == 0
+        torch.cuda.synchronize()
+        return y
+    prev = L.dc_set_gemm_split(1)
+    try:
+        fold = _lib.BnFold()
+        fold.groups = 2
+        ya, yb = direct(None), direct(fold)
+        assert torch.isfinite(ya).all() and torch.isfinite(yb).all()
+        assert not torch.equal(ya, yb), "the shape does not separate NULL from an empty fold struct"
+        assert torch.equal(ops.conv1x1(x, w), ya)
+        assert torch.equal(bnfold.conv1x1(x, w, 1, 2, want_stats=False)[0], yb)
+    finally:
+        L.dc_set_gemm_split(prev)
+
+
 # ---- split-operand GEMMs: fp32 through three bf16 pieces per operand on the bf16 matrix cores (csrc/gemm1x1_x3.hip) ----
 X3_CASES = [
     # B, Ci, Co, H, W, stride

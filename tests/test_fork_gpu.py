@@ -67,18 +67,58 @@ def test_block_with_downsample_or_eval_gets_no_fork_and_second_backward_raises()
         y.sum().backward()                                                             # one backward per forward
 
 
-@pytest.mark.parametrize("shape,planes,ds_stride", [((2, 64, 16, 64), 64, 1), ((2, 256, 16, 64), 128, 2), ((4, 512, 8, 32), 256, 2)])
-def test_pair_fork_of_bottleneck_with_downsample_equals_autograd_sum(shape, planes, ds_stride):
+@pytest.mark.parametrize("kind,shape,planes,ds_stride", [("bottleneck", (2, 64, 16, 64), 64, 1), ("bottleneck", (2, 256, 16, 64), 128, 2),
+                                                         ("bottleneck", (4, 512, 8, 32), 256, 2), ("basic", (2, 64, 16, 32), 128, 2)],
+                         ids=["shape0-64-1", "shape1-128-2", "shape2-256-2", "basic-shape3-128-2"])      # (ids from before `kind`)
+def test_pair_fork_of_bottleneck_with_downsample_equals_autograd_sum(kind, shape, planes, ds_stride):
     """x feeds conv1 AND the 1x1 `downsample` (layer1.0: stride 1; layer2-4.0: stride 2): whichever data gradient is computed
-    second adds the first (in its store epilogue for stride 1, by the library's in-place pass for stride 2)."""
+    second adds the first (in its store epilogue for stride 1, by the library's in-place pass for stride 2).  "basic": layer2-4.0
+    of resnet18 / 34 -- the 3x3 / 2 conv1 (dc_convs2_*) parks its gradient, the 1x1 / 2 `downsample` adds it."""
     from networks import resnet_encoder as RE
-    gx1, gp1, y1, made1 = _run(RE.Bottleneck, shape[1], planes, shape, True, ds_stride=ds_stride)
-    gx0, gp0, y0, made0 = _run(RE.Bottleneck, shape[1], planes, shape, False, ds_stride=ds_stride)
+    cls = RE.BasicBlock if kind == "basic" else RE.Bottleneck
+    gx1, gp1, y1, made1 = _run(cls, shape[1], planes, shape, True, ds_stride=ds_stride)
+    gx0, gp0, y0, made0 = _run(cls, shape[1], planes, shape, False, ds_stride=ds_stride)
     assert len(made1) == 1 and made1[0].pair and made1[0].arrived == 2 and made1[0].addend is None and not made0
     assert torch.equal(y1, y0)
     assert torch.equal(gx1, gx0), float((gx1 - gx0).abs().max())
     for n in gp0:
         assert torch.equal(gp1[n], gp0[n]), n
+
+
+@pytest.mark.parametrize("first", ["g1", "s2"])
+def test_pair_fork_of_conv_s2_and_conv1x1_in_both_backward_orders(first):
+    """ops.conv_s2 and ops.conv1x1 share x through a pair fork; `first` names the convolution whose backward arrives first
+    (autograd runs the node created last first).  The 1x1 arriving second adds the parked gradient in its store epilogue; the
+    strided kernel has no addend epilogue and, arriving second, adds in a pass of its own -- an order the trunk never takes.
+    One fp32 addition either way: identical to autograd's sum."""
+    from depthcore import ops
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(2, 32, 8, 16, generator=g).to(DEV)
+    w3 = (torch.randn(32, 32, 3, 3, generator=g) / 17).to(DEV)
+    w1 = (torch.randn(32, 32, 1, 1, generator=g) / 6).to(DEV)
+    cot = torch.randn(2, 32, 4, 8, generator=g).to(DEV)
+    assert ops.conv_s2_supported(x, w3)
+
+    def run(fork):
+        xl, a3, a1 = (t.clone().requires_grad_() for t in (x, w3, w1))
+        xi = xl * 1.0
+        order = []
+        convs = {"s2": lambda: ops.conv_s2(xi, a3, fork), "g1": lambda: ops.conv1x1(xi, a1, 2, fork=fork)}
+        ys = {}
+        for k in (("s2", "g1") if first == "g1" else ("g1", "s2")):      # the one created last runs its backward first
+            ys[k] = convs[k]()
+            ys[k].register_hook(lambda _, k=k: order.append(k))
+        y = ys["s2"] + ys["g1"]
+        (y * cot).sum().backward()
+        torch.cuda.synchronize()
+        assert order == [first, "s2" if first == "g1" else "g1"]
+        return y.detach(), xl.grad, a3.grad, a1.grad
+    fork = ops.GradFork(pair=True)
+    got, want = run(fork), run(None)
+    assert fork.arrived == 2 and fork.addend is None and not fork.armed
+    ops.assert_no_dangling_sums()
+    for name, a, b in zip(("y", "dx", "dw3", "dw1"), got, want):
+        assert torch.equal(a, b), (name, float((a - b).abs().max()))
 
 
 def test_decoder_output_left_out_of_the_loss_is_reported_not_lost():
