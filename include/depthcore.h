@@ -978,6 +978,41 @@ size_t dc_disp_render_ws_bytes(int N, int h, int w, int Ho, int Wo);
 int dc_disp_render(const float* disp, const uint8_t* lut, uint8_t* rgb, float* range, int N, int h, int w, int Ho, int Wo, double q,
                    void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ velodyne depth maps (raw drives)
+ * generate_depth_map of kitti_utils.py:46-98, the resize and flip of datasets/kitti_dataset.py:71-86 (get_depth) and the maps of
+ * export_gt_depth.py, for a batch of n_img scans in one call (csrc/lidar.hip).
+ *   points: n_points rows of 4 float32 (x forward, y left, z up, reflectance -- ignored: the homogeneous 1), 16-byte aligned,
+ *     all scans back to back; image i owns rows [point_off, point_off + n_points) (n_points = 0: an all-zero map).
+ *   dc_lidar_img: P = P_rect_0{cam} (3x4) * [R_rect_00 | 0; 0 1] * [R T; 0 1] (:52-62), row-major fp64; (W, H) the native size
+ *     S_rect_02; vel_depth: the depth is x_velo (:73-74, the export) instead of the projection's third row (the dataset);
+ *     flip: np.fliplr after the resize.
+ *   out (n_img, 1, Ho, Wo) float32.  rows (n_img, Ho) / cols (n_img, Wo) int32: the NATIVE row / column every output row / column
+ *     reads -- the caller's nearest-neighbour resize (the identity when the sizes agree).
+ * Per scan: keep x_velo >= 0 (:67); q = P * (x, y, z, 1) in fp64 as ((P0*x + P1*y) + P2*z) + P3, unfused; u = q0/q2, v = q1/q2;
+ * pixel (rint(u) - 1, rint(v) - 1) (:78-79, np.round: half to even), kept inside [0, W) x [0, H) (:80-81); depth = fp32(q2) or
+ * x_velo.  A pixel hit by several points holds the smallest depth (:88-95), one hit by none 0, negative depths become 0 (:96).
+ * Edge columns: the reference groups duplicates by sub2ind = y*(W-1) + x - 1 (:39-43), which is the same for (y, W-1) and
+ * (y+1, 0).  When both are hit they are ONE group: the pixel that holds the group's earliest point (file order) receives the
+ * minimum over both pixels' points, the other keeps the depth of its latest point (the fancy-index assignment of :86).
+ * Reproduced exactly; it touches columns 0 and W-1 only.
+ * Passes on `stream` (clear, project, finalize): 32-bit atomicMin of an order-preserving key per pixel, 64-bit atomicMin / Max
+ * side planes for the edge rule -- integer min / max commute, so the result is bitwise reproducible; every output element is
+ * written exactly once (no memset needed).  No allocation, no synchronisation.  workspace: 8-byte aligned,
+ * dc_lidar_workspace_bytes(n_img, max W, max H) bytes (0 for a bad shape); DC_EWORKSPACE when smaller.
+ * desc / rows / cols are passed as HOST and DEVICE copies of the same bytes; the host copies are checked before anything is
+ * launched: DC_EINVAL (nothing launched, nothing written) for n_img <= 0 or > 65535, Ho / Wo / H <= 0, W < 2 (the edge rule
+ * needs two distinct columns), a point range outside [0, n_points), a table entry outside the native size, a null or
+ * misaligned pointer. */
+typedef struct dc_lidar_img {
+    long long point_off;
+    int32_t n_points, W, H, vel_depth, flip, reserved;
+    double P[12];
+} dc_lidar_img;
+size_t dc_lidar_workspace_bytes(int n_img, int max_w, int max_h);
+int dc_lidar_depth_maps(const float* points, size_t n_points, const dc_lidar_img* desc_host, const dc_lidar_img* desc_dev, int n_img,
+                        const int32_t* rows_host, const int32_t* rows_dev, const int32_t* cols_host, const int32_t* cols_dev, int Ho,
+                        int Wo, float* out, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

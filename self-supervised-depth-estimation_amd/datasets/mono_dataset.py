@@ -62,13 +62,16 @@ class MonoDataset:
             paths.append(path)
         return paths
 
-    def metadata(self, index, do_flip=False):
+    device_depth = False      # True: the class has `depth_source`, and a loader may build "depth_gt" on the device from it
+
+    def metadata(self, index, do_flip=False, device_depth=False):
         """Everything of an item that is not a colour image: "depth_gt" (1, H, W) float32 when the dataset has ground truth
         (:198-201), "stereo_T" (4, 4) float32 when "s" is among the frames (:203-209: the baseline of 0.1 units changes sign
-        with the side and with the flip)."""
+        with the side and with the flip).  device_depth=True: the caller builds "depth_gt" itself from `depth_source` when
+        the class allows it (`device_depth`), so it is left out here."""
         folder, frame_index, side = parse_line(self.filenames[index])
         out = {}
-        if self.load_depth:
+        if self.load_depth and not (device_depth and self.device_depth):
             out["depth_gt"] = np.expand_dims(self.get_depth(folder, frame_index, side, do_flip), 0).astype(np.float32)
         if "s" in self.frame_idxs:
             stereo_T = np.eye(4, dtype=np.float32)

@@ -173,6 +173,8 @@ def _sig(lib):
         "dc_pose_ate": (i, [p, p, p, i, i, i, p]),
         "dc_disp_render_ws_bytes": (z, [i, i, i, i, i]),
         "dc_disp_render": (i, [p, p, p, p, i, i, i, i, i, c_double, p, z, p]),
+        "dc_lidar_workspace_bytes": (z, [i, i, i]),
+        "dc_lidar_depth_maps": (i, [p, z, p, p, i, p, p, p, p, i, i, p, p, z, p]),
         "dc_bn_bwd_finalize": (i, [p, i, i, c_double, p, p, p, p, p, p, i, i, p]),
         "dc_bn_bwd_apply": (i, [p, p, p, p, i, i, i, i, p]),
         "dc_conv1x1_bn_ok": (i, [i, i, i, i, i]),

@@ -18,8 +18,13 @@ permutation, the same number of steps on every rank.
 
 `cache_bytes` > 0 adds a cache of resized frames in HBM (depthcore/frame_cache.py): the host then decodes only the frames
 the cache lacks, and a warm batch is gathered from cache slots in two launches.  The batches are the same, bit for bit.
+
+A dataset with `device_depth` whose velodyne scans are present (KITTIRAWDataset) gets its "depth_gt" on the device: the pool
+threads read each item's scan into the staging buffer behind the frames, the one copy carries them and the projection's
+descriptors, and `ops.lidar_depth_maps_staged` runs on the loader's stream -- with or without the frame cache.
 """
 import collections
+import os
 import random
 from concurrent.futures import ThreadPoolExecutor
 
@@ -27,6 +32,7 @@ import numpy as np
 import torch
 from PIL import Image
 
+from . import lidar
 from .data import GpuPreprocessor, sample_item
 from .frame_cache import FrameCache
 
@@ -67,6 +73,13 @@ def _decode_into(path, dst):
                                  % (path, rgb.height, rgb.width, dst.shape[0], dst.shape[1]))
             rgb.load()
             dst[...] = _pixels(rgb)
+
+
+def _read_into(path, dst):
+    """The bytes of a file (a velodyne scan) into a uint8 view of the staging buffer."""
+    with open(path, "rb") as f:
+        if f.readinto(dst) != dst.size or f.read(1):
+            raise ValueError("%s changed size while the batch was being read" % path)
 
 
 def _image_size(path):
@@ -122,28 +135,70 @@ class BatchLoader:
             self._pool = ThreadPoolExecutor(self.threads, thread_name_prefix="depthcore-decode")
         return self._pool
 
-    def _submit(self, indices, draws, alloc):
+    def _scans(self, indices, flips, frame_bytes):
+        """The velodyne half of a job for a dataset that projects "depth_gt" on the device (`device_depth` with scans present),
+        else None: the scans go into the staging buffer behind the frames, back to back from the next 16-byte boundary, the
+        descriptors of the projection (lidar.descriptors) behind them, and `_lidar_depth` turns them into the batch's
+        "depth_gt" after the one upload -- no further copy, nothing that waits for the device."""
+        ds = self.dataset
+        if not (getattr(ds, "device_depth", False) and getattr(ds, "load_depth", False)):
+            return None
+        sources = [ds.depth_source(i) for i in indices]
+        nbytes = [os.path.getsize(path) for path, _, _ in sources]
+        if any(n % 16 for n in nbytes):
+            raise ValueError("a velodyne scan is rows of four float32: %s has %d bytes"
+                             % next((s[0], n) for s, n in zip(sources, nbytes) if n % 16))
+        calib = [lidar.velo_to_image(calib_dir, cam) for _, calib_dir, cam in sources]
+        off = (frame_bytes + 15) // 16 * 16
+        end = off + sum(nbytes)
+        width, height = ds.full_res_shape
+        desc = lidar.descriptors([n // 16 for n in nbytes], np.stack([c[0] for c in calib]), [c[1] for c in calib],
+                                 out_size=(height, width), flips=flips)
+        return {"off": off, "end": end, "total": end + desc.host.size, "paths": [s[0] for s in sources], "nbytes": nbytes, "desc": desc}
+
+    def _read_scans(self, scans, buf):
+        """One pool task per scan, reading the file at its offset of the staging buffer -> the futures."""
+        buf[scans["end"]:scans["total"]] = scans["desc"].host
+        futures, off = [], scans["off"]
+        for path, n in zip(scans["paths"], scans["nbytes"]):
+            futures.append(self._pool_().submit(_read_into, path, buf[off:off + n]))
+            off += n
+        return futures
+
+    def _lidar_depth(self, scans, dev):
+        """"depth_gt" (B, 1, 375, 1242) of an uploaded job (dev: the device copy of its staging bytes), on the current stream."""
+        from . import ops
+        points = dev[scans["off"]:scans["end"]].view(torch.float32).view(-1, 4)
+        return ops.lidar_depth_maps_staged(points, scans["desc"], dev[scans["end"]:scans["total"]])
+
+    def _submit(self, indices, draws, alloc, device_depth=True):
         """Start decoding a batch: sizes from the headers of each item's first frame, then one task per frame writing at
-        its offset of `alloc(total bytes)` (frame-major: image f * B + b).  -> job dict with the futures."""
+        its offset of `alloc(total bytes)` (frame-major: image f * B + b).  -> job dict with the futures.  device_depth:
+        the scans of a dataset with `device_depth` travel behind the frames (`_scans`) instead of a host-built "depth_gt"."""
         ds = self.dataset
         paths = [ds.frame_paths(i) for i in indices]
         sizes = [_image_size(p[0]) for p in paths]
         per_frame = sum(h * w * 3 for h, w in sizes)
-        buf = alloc(per_frame * len(ds.frame_idxs))
+        flips = [bool(d[0]) for d in draws]
+        scans = self._scans(indices, flips, per_frame * len(ds.frame_idxs)) if device_depth else None
+        buf = alloc(scans["total"] if scans else per_frame * len(ds.frame_idxs))
         futures, off = [], 0
         for f in range(len(ds.frame_idxs)):
             for b, (h, w) in enumerate(sizes):
                 dst = buf[off:off + h * w * 3].reshape(h, w, 3)
                 futures.append(self._pool_().submit(_decode_into, paths[b][f], dst))
                 off += h * w * 3
-        flips = [bool(d[0]) for d in draws]
-        meta = self._pool_().submit(lambda: [ds.metadata(i, fl) for i, fl in zip(indices, flips)])
-        return {"buf": buf[:off], "sizes": sizes, "flips": flips, "jitters": [d[1] for d in draws], "futures": futures, "meta": meta}
+        if scans:
+            futures += self._read_scans(scans, buf)
+        meta = self._pool_().submit(lambda: [ds.metadata(i, fl, device_depth=scans is not None) for i, fl in zip(indices, flips)])
+        return {"buf": buf[:scans["total"] if scans else off], "frame_bytes": off, "sizes": sizes, "flips": flips,
+                "jitters": [d[1] for d in draws], "futures": futures, "meta": meta, "scans": scans}
 
     def _submit_cached(self, indices, draws, alloc):
         """`_submit` with the frame cache on: only the frames the cache lacks are decoded, each file once however often the
         batch names it (frame 0 stands in for a missing neighbour), back to back into `alloc(total bytes)`; a batch whose
-        frames are all cached touches no file and no staging buffer.  The size of a missing frame comes from the header of
+        frames are all cached touches no image file and -- unless the dataset's scans travel with it (`_scans`: they are not
+        cached) -- no staging buffer.  The size of a missing frame comes from the header of
         its item's first missing frame.  A native width whose Lanczos table is not mirror-symmetric cannot be cached
         (FrameCache.symmetric): a batch that holds such an item goes down the uncached path whole and counts as bypassed."""
         ds, cache = self.dataset, self.cache
@@ -163,17 +218,20 @@ class BatchLoader:
         cache.stats["hits"] += hits
         cache.stats["misses"] += sum(len(item) for item in paths) - hits
         cache.stats["decoded"] += len(need)
-        total = sum(h * w * 3 for h, w in need.values())
-        buf = alloc(total)[:total] if need else None
+        flips = [bool(d[0]) for d in draws]
+        scans = self._scans(indices, flips, sum(h * w * 3 for h, w in need.values()))
+        total = scans["total"] if scans else sum(h * w * 3 for h, w in need.values())
+        buf = alloc(total)[:total] if need or scans else None
         futures, frames, off = [], [], 0
         for path, (h, w) in need.items():
             futures.append(self._pool_().submit(_decode_into, path, buf[off:off + h * w * 3].reshape(h, w, 3)))
             frames.append((path, off, h, w))
             off += h * w * 3
-        flips = [bool(d[0]) for d in draws]
-        meta = self._pool_().submit(lambda: [ds.metadata(i, fl) for i, fl in zip(indices, flips)])
+        if scans:
+            futures += self._read_scans(scans, buf)
+        meta = self._pool_().submit(lambda: [ds.metadata(i, fl, device_depth=scans is not None) for i, fl in zip(indices, flips)])
         return {"paths": paths, "frames": frames, "buf": buf, "flips": flips, "jitters": [d[1] for d in draws], "futures": futures,
-                "meta": meta}
+                "meta": meta, "scans": scans}
 
     @staticmethod
     def _finish(job):
@@ -196,7 +254,7 @@ class BatchLoader:
             if out.size < nbytes:
                 raise ValueError("decode_batch: %d bytes do not fit the given buffer of %d" % (nbytes, out.size))
             return out
-        return self._finish(self._submit(indices, draws, alloc))
+        return self._finish(self._submit(indices, draws, alloc, device_depth=False))
 
     # ---------------------------------------------------------------------------------------------------------- device half
     def _stage(self, slot, nbytes):
@@ -223,8 +281,10 @@ class BatchLoader:
             dev.copy_(self._staging[slot][:buf.size], non_blocking=True)
             self._copied[slot] = torch.cuda.Event()
             self._copied[slot].record(self._side)
-            batch = self._pre.ragged(dev, sizes, flips, jitters)
+            batch = self._pre.ragged(dev[:job["frame_bytes"]], sizes, flips, jitters)
             batch.update(self._intrinsics)
+            if job["scans"]:
+                batch["depth_gt"] = self._lidar_depth(job["scans"], dev)
             for k, v in extras.items():
                 batch[k] = torch.from_numpy(np.ascontiguousarray(v)).to(self.device)
             ready = torch.cuda.Event()
@@ -261,7 +321,7 @@ class BatchLoader:
         if any(s is None for s in slots):
             raise RuntimeError("a frame of this batch has left the cache since the batch was planned (FrameCache.clear during an epoch)")
         with torch.cuda.stream(self._side):
-            if build:
+            if build or job["scans"]:
                 dev = torch.empty(buf.size, dtype=torch.uint8, device=self.device)
                 dev.copy_(self._staging[slot][:buf.size], non_blocking=True)
                 self._copied[slot] = torch.cuda.Event()
@@ -269,6 +329,8 @@ class BatchLoader:
                 cache.build(self._pre, dev, build)
             batch = self._pre.cached(cache.arena, slots, job["flips"], job["jitters"])
             batch.update(self._intrinsics)
+            if job["scans"]:
+                batch["depth_gt"] = self._lidar_depth(job["scans"], dev)
             for k, v in extras.items():
                 batch[k] = torch.from_numpy(np.ascontiguousarray(v)).to(self.device)
             ready = torch.cuda.Event()

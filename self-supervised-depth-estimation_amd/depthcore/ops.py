@@ -878,6 +878,49 @@ def pose_ate(pred, gt_global, track_length=5):
 
 
 # ----------------------------------------------------------------------------------------------
+# velodyne depth maps: kitti_utils.generate_depth_map + KITTIRAWDataset.get_depth's resize and flip, a batch per call
+# ----------------------------------------------------------------------------------------------
+def lidar_depth_maps(points, counts, P, sizes, out_size=None, vel_depth=False, flips=None):
+    """Sparse depth maps of B velodyne scans (dc_lidar_depth_maps: three launches on the current stream, bitwise reproducible).
+      points: (N, 4) float32 device tensor, the scans back to back in file layout (column 3 is ignored), 16-byte aligned;
+      counts: B ints, the points of every scan (0 gives an all-zero map), sum <= N;
+      P: (B, 3, 4) float64 on the host (numpy or CPU tensor), lidar.velo_to_image's matrix of every scan;
+      sizes: B native (W, H);  out_size: (Ho, Wo) of the result, resized from the native size by Pillow's NEAREST rule
+        (lidar.nearest_tables) -- None: the native size, which all scans must then share;
+      vel_depth: one bool or B of them (True: the depth is x_velo, the export's convention);  flips: B bools (np.fliplr).
+    -> (B, 1, Ho, Wo) float32.  The descriptors and index tables are small host arrays (lidar.descriptors): one host-to-device
+    copy per call; a caller whose upload already carries them uses `lidar_depth_maps_staged`."""
+    from .lidar import descriptors
+    d = descriptors(counts, P, sizes, out_size, vel_depth, flips)
+    return lidar_depth_maps_staged(points, d, torch.from_numpy(d.host).to(points.device))
+
+
+def lidar_depth_maps_staged(points, d, block):
+    """`lidar_depth_maps` with the descriptors already on the device: d is lidar.descriptors(...), block a uint8 device tensor
+    holding the bytes of d.host at an 8-byte aligned address (the loader's one upload carries them behind the scans)."""
+    L = _lib.lib()
+    pts = points.detach()
+    if pts.dim() != 2 or pts.shape[1] != 4:
+        raise DepthcoreError("lidar_depth_maps: points (N, 4), got %s" % (tuple(pts.shape),))
+    if block.dtype != torch.uint8 or block.numel() != d.host.size or block.data_ptr() % 8 or block.device != pts.device:
+        raise DepthcoreError("lidar_depth_maps: the device block must be the %d descriptor bytes, 8-byte aligned, on %s"
+                             % (d.host.size, pts.device))
+    dev, n_points = pts.device, pts.shape[0]
+    if n_points == 0:                 # every scan is empty: the entry point still wants a valid pointer
+        pts = torch.zeros((1, 4), dtype=torch.float32, device=dev)
+    ws_bytes = L.dc_lidar_workspace_bytes(d.B, int(d.desc["W"].max()), int(d.desc["H"].max()))
+    if ws_bytes == 0:
+        raise DepthcoreError("lidar_depth_maps: native sizes up to %d x %d are out of range" % (d.desc["W"].max(), d.desc["H"].max()))
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    out = torch.empty((d.B, 1, d.Ho, d.Wo), dtype=torch.float32, device=dev)
+    base = ptr(block, torch.uint8)
+    check(L.dc_lidar_depth_maps(ptr(pts), n_points, d.desc.ctypes.data, base, d.B, d.rows.ctypes.data, base + d.rows_off,
+                                d.cols.ctypes.data, base + d.cols_off, d.Ho, d.Wo, ptr(out), ws.data_ptr(), ws_bytes, stream(pts)),
+          "dc_lidar_depth_maps")
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
 # depth evaluation: the prediction side of evaluate_depth.py:95-135 and its benchmark export (:159-171)
 # ----------------------------------------------------------------------------------------------
 def flip_concat(x):
