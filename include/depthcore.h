@@ -1013,6 +1013,41 @@ int dc_lidar_depth_maps(const float* points, size_t n_points, const dc_lidar_img
                         const int32_t* rows_host, const int32_t* rows_dev, const int32_t* cols_host, const int32_t* cols_dev, int Ho,
                         int Wo, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ training-log image panels (trainer.py:666-698)
+ * Composes n_panels images (n_panels, PH, PW, 3) uint8, interleaved (PIL.Image.fromarray's layout, any address), from a list of
+ * tiles (csrc/logpanel.hip).  A tile draws one source at the corner (x0, y0) of panel `panel`, enlarged by the integer
+ * nearest-neighbour factor `up`: it covers (h*up) x (w*up) pixels, and destination pixel (y, x) of the tile reads source
+ * element (y / up, x / up).  Per kind, all arithmetic in fp32, unfused (the object is built with -ffp-contract=off):
+ *   RGB   src (3,h,w) fp32 planar; per channel v <= 0 or NaN -> 0, v >= 1 -> 255, else (uint8)(v * 255.0f + 0.5f).  For every
+ *         byte k, fp32(k / 255) maps back to k: a decoded frame's tile carries the decoded bytes.
+ *   UNIT  src (h,w) fp32; the RGB rule on the one plane, written to all three channels.
+ *   MASK  src (h,w) uint8; src >= thr ? 255 : 0, written to all three channels.
+ *   NORM  src (h,w) fp32; the reference's normalize_image (utils.py) and a colour table: mi / ma the exact minimum / maximum of
+ *         the tile's h*w source values, d = ma != mi (compared as floats) ? ma - mi : 1e5f, x = (v - mi) / d, xa = x * 256.0f,
+ *         idx = xa < 0 ? 0 : min((int)xa, 255), rgb = lut[idx]; lut (256,3) uint8 on the device.  Non-finite input is outside
+ *         the contract.
+ * A pixel that no tile covers holds `background` (0..255) in all three channels.  mi / ma come from 32-bit integer atomicMin /
+ * atomicMax of order-preserving keys: no floating-point atomic, two calls give the same bytes.  At most three launches on
+ * `stream` (clear, range -- only when there is a NORM tile --, compose); no allocation, no synchronisation.
+ * ws: 4-byte aligned, dc_log_panel_ws_bytes(n_tiles) bytes (0 for n_tiles < 1; needs no GPU); DC_EWORKSPACE when ws_bytes is
+ * smaller.  The tiles are passed as HOST and DEVICE copies of the same bytes; the host copy is checked before anything is
+ * launched, without a HIP call: DC_EINVAL (nothing launched, nothing written) for n_tiles < 1, n_panels < 1 or > 65535, PH or
+ * PW < 1, background outside [0, 255], a null tiles_host / tiles_dev / lut / panels / ws / src, an unknown kind, up / h / w < 1,
+ * h*w >= 2^31 - 1, a panel index outside [0, n_panels), a tile that leaves its panel, two tiles of one panel that overlap,
+ * src_elems smaller than the tile reads (3*h*w for RGB, h*w otherwise), a src of a float kind that is not 4-byte aligned. */
+enum { DC_TILE_RGB = 0, DC_TILE_NORM = 1, DC_TILE_UNIT = 2, DC_TILE_MASK = 3 };
+typedef struct dc_panel_tile {
+    const void* src;        /* device: RGB (3,h,w) fp32 planar; NORM / UNIT (h,w) fp32; MASK (h,w) uint8 */
+    long long src_elems;    /* elements the caller guarantees behind src */
+    int32_t kind, panel;    /* DC_TILE_*, destination image */
+    int32_t h, w, up;       /* source size; nearest-neighbour factor: the tile covers (h*up) x (w*up) pixels */
+    int32_t x0, y0;         /* top-left corner inside the panel */
+    int32_t thr;            /* MASK: byte = src >= thr ? 255 : 0 */
+} dc_panel_tile;
+size_t dc_log_panel_ws_bytes(int n_tiles);
+int dc_log_panel(const dc_panel_tile* tiles_host, const dc_panel_tile* tiles_dev, int n_tiles, const uint8_t* lut,
+                 uint8_t* panels, int n_panels, int PH, int PW, int background, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

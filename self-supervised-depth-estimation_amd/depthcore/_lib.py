@@ -113,6 +113,15 @@ class ConvS2Plan(Structure):
                                        "dw_tiles_per_block", "dw_reduce", "dx", "dx_slabs")]
 
 
+TILE_RGB, TILE_NORM, TILE_UNIT, TILE_MASK = 0, 1, 2, 3
+
+
+class PanelTile(Structure):
+    """Mirror of `dc_panel_tile` (include/depthcore.h: dc_log_panel)."""
+    _fields_ = [("src", _F), ("src_elems", ctypes.c_longlong), ("kind", c_int32), ("panel", c_int32),
+                ("h", c_int32), ("w", c_int32), ("up", c_int32), ("x0", c_int32), ("y0", c_int32), ("thr", c_int32)]
+
+
 _lib = None
 
 
@@ -175,6 +184,8 @@ def _sig(lib):
         "dc_disp_render": (i, [p, p, p, p, i, i, i, i, i, c_double, p, z, p]),
         "dc_lidar_workspace_bytes": (z, [i, i, i]),
         "dc_lidar_depth_maps": (i, [p, z, p, p, i, p, p, p, p, i, i, p, p, z, p]),
+        "dc_log_panel_ws_bytes": (z, [i]),
+        "dc_log_panel": (i, [p, p, i, p, p, i, i, i, i, p, z, p]),
         "dc_bn_bwd_finalize": (i, [p, i, i, c_double, p, p, p, p, p, p, i, i, p]),
         "dc_bn_bwd_apply": (i, [p, p, p, p, i, i, i, i, p]),
         "dc_conv1x1_bn_ok": (i, [i, i, i, i, i]),

@@ -1041,6 +1041,70 @@ def render_disparity(disp, size, percentile=95.0, lut=None):
 
 
 # ----------------------------------------------------------------------------------------------
+# training-log image panels: the pictures of trainer.py:666-698, composed on the device
+# ----------------------------------------------------------------------------------------------
+TILE_KINDS = {"rgb": _lib.TILE_RGB, "norm": _lib.TILE_NORM, "unit": _lib.TILE_UNIT, "mask": _lib.TILE_MASK}
+
+
+def log_panels(tiles, n_panels, size, lut=None, background=0, buf=None):
+    """`n_panels` interleaved uint8 images (n_panels, PH, PW, 3), size = (PH, PW), composed from `tiles` (dc_log_panel: at most
+    three launches on the current stream, bitwise reproducible).  A tile is (src, kind, panel, up, x0, y0[, thr]):
+      src: a device tensor -- "rgb" (3,h,w) float32, "norm" / "unit" (h,w) float32, "mask" (h,w) uint8;
+      kind: "rgb" | "norm" | "unit" | "mask" (or the DC_TILE_* number): [0, 1] -> bytes by round-half-up per channel; the
+        reference's normalize_image and the colour table `lut` ((256,3) uint8 on the device, default magma); [0, 1] -> grey;
+        src >= thr ? 255 : 0;
+      panel, (x0, y0): the destination image and the tile's top-left corner in it; up: integer nearest-neighbour factor, the
+        tile covers (h*up) x (w*up) pixels.
+    Tiles of one panel must not overlap and must lie inside it; a pixel no tile covers holds `background`.  `buf`: a uint8
+    device tensor of at least n_panels*PH*PW*3 bytes to compose into (the result is a view of it); None allocates.  The tile
+    descriptors are a small host array: one host-to-device copy per call.  No gradient."""
+    L = _lib.lib()
+    PH, PW = int(size[0]), int(size[1])
+    n = len(tiles)
+    if n < 1:
+        raise DepthcoreError("log_panels: no tiles")
+    desc = (_lib.PanelTile * n)()
+    keep, dev = [], None
+    for i, t in enumerate(tiles):
+        src, kind, panel, up, x0, y0 = t[:6]
+        thr = t[6] if len(t) > 6 else 0
+        kind = TILE_KINDS.get(kind, kind)
+        if kind not in TILE_KINDS.values():
+            raise DepthcoreError("log_panels: tile %d: unknown kind %r" % (i, t[1]))
+        s = _c(src.detach())
+        p = ptr(s, torch.uint8 if kind == _lib.TILE_MASK else torch.float32)
+        if s.dim() != (3 if kind == _lib.TILE_RGB else 2) or (kind == _lib.TILE_RGB and s.shape[0] != 3):
+            raise DepthcoreError("log_panels: tile %d: a %s tile reads %s, got %s"
+                                 % (i, t[1], "(3,h,w)" if kind == _lib.TILE_RGB else "(h,w)", tuple(s.shape)))
+        dev = s.device if dev is None else dev
+        if s.device != dev:
+            raise DepthcoreError("log_panels: tile %d lives on %s, the others on %s" % (i, s.device, dev))
+        keep.append(s)
+        d = desc[i]
+        d.src, d.src_elems, d.kind, d.panel = p, s.numel(), kind, int(panel)
+        d.h, d.w, d.up, d.x0, d.y0, d.thr = int(s.shape[-2]), int(s.shape[-1]), int(up), int(x0), int(y0), int(thr)
+    if lut is None:
+        lut = magma_lut(dev)
+    if tuple(lut.shape) != (256, 3) or lut.dtype != torch.uint8 or lut.device != dev:
+        raise DepthcoreError("log_panels: lut must be a (256,3) uint8 tensor on %s, got %s %s on %s"
+                             % (dev, tuple(lut.shape), lut.dtype, lut.device))
+    nbytes = max(int(n_panels), 0) * max(PH, 0) * max(PW, 0) * 3
+    if buf is None:
+        buf = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    if buf.dtype != torch.uint8 or buf.device != dev or buf.numel() < nbytes or not buf.is_contiguous():
+        raise DepthcoreError("log_panels: buf must be a contiguous uint8 tensor of at least %d bytes on %s" % (nbytes, dev))
+    # one upload: [descriptors | the range keys' workspace] (sizeof(dc_panel_tile) = 48 keeps the keys 8-byte aligned)
+    nd, nws = ctypes.sizeof(desc), L.dc_log_panel_ws_bytes(n)
+    host = torch.zeros(nd + nws, dtype=torch.uint8)
+    ctypes.memmove(host.data_ptr(), ctypes.addressof(desc), nd)
+    block = host.to(dev)
+    base = block.data_ptr()
+    check(L.dc_log_panel(ctypes.addressof(desc), base, n, ptr(_c(lut), torch.uint8), buf.data_ptr(), int(n_panels), PH, PW,
+                         int(background), base + nd, nws, stream(buf)), "dc_log_panel")
+    return buf[:nbytes].view(int(n_panels), PH, PW, 3)
+
+
+# ----------------------------------------------------------------------------------------------
 # a1 nn.MaxPool2d(3, 2, 1) of the ResNet stem
 # ----------------------------------------------------------------------------------------------
 class _MaxPool(torch.autograd.Function):

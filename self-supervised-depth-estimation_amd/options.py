@@ -103,6 +103,7 @@ _BUILD = [
     ("gru", str, None, [None, "v5"]),            # front-end of trainer_gru.py (run_gru_v5; sequences of len_sequence frames)
     ("splits_dir", str, os.path.join(_HERE, "splits"), None),  # evaluate_depth.py: <splits_dir>/<eval_split>/{test_files.txt, gt_depths.npz} (none ship here)
     ("eval_json", str, None, None),              # evaluate_depth.py: also write the results to this JSON file
+    ("log_images", int, 0, None),                # items per log step whose image panel is written to <log_path>/<mode>/images/ (Trainer.log_images); 0 = off, the reference writes 4
     ("frame_cache_gb", float, 0.0, None),        # train.py: GiB of HBM for the training loader's cache of resized frames (depthcore/frame_cache.py); 0 = off
 ]
 

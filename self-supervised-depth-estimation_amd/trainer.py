@@ -6,7 +6,9 @@ compute_losses` keeps working.  The loop around it -- `train()` / `run_epoch()` 
 (reference trainer.py:210-254, 444-463, 654-671) with checkpoints every `save_frequency` epochs -- is fed by
 `depthcore.loader.BatchLoader` over the `datasets/` package: frames are decoded on host threads and the per-item
 data step (flip, Lanczos pyramid, ColorJitter, ToTensor) runs on the device.  Scalars are appended to
-`<log_path>/<mode>/scalars.jsonl`; there is no tensorboard writer and no image logging.
+`<log_path>/<mode>/scalars.jsonl`; there is no tensorboard writer.  With `opt.log_images = N > 0` every log step also writes
+one JPEG panel per item for the first N items of the batch -- frames, warped predictions, coloured disparities, automask --
+composed on the device (`Trainer.log_images`, depthcore/logimg.py) to `<log_path>/<mode>/images/`.
 
 Two equivalent loss paths, both on hand-written gfx950 kernels:
   * fused (default): generate_images_pred + compute_losses are ONE forward op and ONE backward op
@@ -462,7 +464,9 @@ class Trainer:
         return [torch.randn(B, nch, self.opt.height >> (s if v1 else 0), self.opt.width >> (s if v1 else 0)).to(self.device)
                 for s in self.opt.scales]
 
-    def fused_losses(self, inputs, outputs, materialize=None):
+    def fused_losses(self, inputs, outputs, materialize=None, draw_noise=True):
+        """`draw_noise=False` (log_images): never the CPU generator of cpu_tiebreak_noise -- the kernels' own stateless noise
+        of this step's seed stands in, which the warped images do not depend on."""
         o = self.opt
         materialize = o.materialize_logs if materialize is None else materialize
         B = inputs[("color", 0, 0)].shape[0]
@@ -473,8 +477,8 @@ class Trainer:
         cfg = ops.PhotoConfig(
             inputs[("color", 0, 0)], inputs[("color", -1, 0)], inputs[("color", 1, 0)],
             [inputs[("color", 0, s)] for s in o.scales], inputs[("K", 0)], inputs[("inv_K", 0)],
-            noise=self._noise(B, 1 if o.avg_reprojection else 2), min_depth=o.min_depth, max_depth=o.max_depth,
-            smoothness=o.disparity_smoothness, disable_automasking=o.disable_automasking,
+            noise=self._noise(B, 1 if o.avg_reprojection else 2) if draw_noise else None, min_depth=o.min_depth,
+            max_depth=o.max_depth, smoothness=o.disparity_smoothness, disable_automasking=o.disable_automasking,
             avg_reprojection=o.avg_reprojection, no_ssim=o.no_ssim, materialize=materialize, packed=packed,
             rng_seed=self._seed_dev if self._seed_dev is not None else self.step * 1000003 + self.rank)
         masks, bce = self._predictive_masks(outputs, full_res=True)
@@ -515,7 +519,7 @@ class Trainer:
             masks = [interpolate_bilinear(m, [o.height, o.width]) for m in masks]
         return masks, [0.2 * (-torch.clamp(torch.log(m), min=-100.0)).mean() for m in masks]
 
-    def fused_losses_v1(self, inputs, outputs, materialize=None):
+    def fused_losses_v1(self, inputs, outputs, materialize=None, draw_noise=True):
         """`opt.v1_multiscale` (trainer.py:470-472, 541-544) on the fused kernels: every scale warps and compares at its OWN
         resolution -- its own images, intrinsics, identity losses and tie-break noise -- so the step is one fused call per
         scale, each a single-scale problem of size (H >> s, W >> s) (the kernels' scale-0 wave: the upsample is the identity),
@@ -523,7 +527,7 @@ class Trainer:
         o = self.opt
         materialize = o.materialize_logs if materialize is None else materialize
         B = inputs[("color", 0, 0)].shape[0]
-        noise = self._noise(B, 1 if o.avg_reprojection else 2)
+        noise = self._noise(B, 1 if o.avg_reprojection else 2) if draw_noise else None
         masks, bce = self._predictive_masks(outputs, full_res=False)
         losses, total = {}, 0
         for i, s in enumerate(o.scales):
@@ -726,9 +730,15 @@ class Trainer:
                     if "depth_gt" in inputs:
                         self.compute_depth_losses(inputs, outputs, losses)
                     self.log("train", losses, step)
+                    log_images = getattr(self.opt, "log_images", 0) > 0
+                    if log_images:
+                        self.log_images("train", inputs, outputs, step)
                     if not self.opt.fusion:            # Trainer.val refuses the sequence front-ends
-                        _, val_losses = self.val(self._next_val_batch())
+                        val_inputs = self._next_val_batch()
+                        val_outputs, val_losses = self.val(val_inputs)
                         self.log("val", val_losses, step)
+                        if log_images:
+                            self.log_images("val", val_inputs, val_outputs, step)
         cache = getattr(self.train_loader, "cache", None)
         if cache is not None:
             print("epoch {:>3} | frame cache: {} of {} slots | {}".format(
@@ -761,7 +771,7 @@ class Trainer:
 
     def log(self, mode, losses, step=None):
         """The scalars of trainer.py:666-671 (`writer.add_scalar(l, v, self.step)`), one JSON object per call appended to
-        `<log_path>/<mode>/scalars.jsonl`: {"step": ..., name: value, ...}.  No images."""
+        `<log_path>/<mode>/scalars.jsonl`: {"step": ..., name: value, ...}.  The images are log_images'."""
         folder = os.path.join(self.log_path, mode)
         os.makedirs(folder, exist_ok=True)
         row = {"step": int(self.step if step is None else step)}
@@ -769,6 +779,63 @@ class Trainer:
             row[name] = float(v.detach()) if torch.is_tensor(v) else float(v)
         with open(os.path.join(folder, "scalars.jsonl"), "a") as f:
             f.write(json.dumps(row) + "\n")
+
+    def log_images(self, mode, inputs, outputs, step=None, return_sources=False):
+        """The pictures of trainer.py:673-698 for the first min(opt.log_images, B) items of the batch, one panel per item
+        (depthcore/logimg.py: frames, warped predictions, one row per scale with the coloured disparity and the automask or the
+        predictive masks), composed on the device by one dc_log_panel call and brought to the host by ONE device-to-host copy
+        into a pinned buffer kept on the trainer; written with Pillow to `<log_path>/<mode>/images/<step:07d>_<j>.jpg` at
+        quality 90.  -> the panels as a host array (n, PH, PW, 3) uint8; with `return_sources` also
+        {(item, row, column): the float or uint8 tensor the tile was read from}.
+        The warped predictions are outputs[("color", f, 0)] when the step produced them (the layer-by-layer loss, or
+        materialize_logs); otherwise they are recomputed under no_grad for the logged items only, by the trainer's own fused
+        loss on the sliced tensors with materialize=True -- the automask still shows the step's own argmin.
+        Training is left where it was: no random number is drawn (neither the CPU generator of cpu_tiebreak_noise nor the device
+        seed moves), self.step, the Winograd weight cache, captured graphs and every module are untouched.  Under hip_graph the
+        tensors read are the replay's static outputs; the call itself runs outside the captured step."""
+        from PIL import Image
+        from depthcore import logimg
+        o = self.opt
+        B = inputs[("color", 0, 0)].shape[0]
+        n = min(int(getattr(o, "log_images", 0)), B)
+        if n < 1:
+            raise ValueError("log_images: opt.log_images is %r, nothing to draw" % getattr(o, "log_images", 0))
+        if o.gru:
+            raise NotImplementedError("image logging for the ConvGRU front-end: its training loop is refused as well")
+        step = self.step if step is None else step
+        if 0 in o.scales and ("color", -1, 0) not in outputs:
+            inputs, outputs = self._logged_predictions(inputs, outputs, B, n)
+        PH, PW = logimg.panel_size(o)
+        nbytes = n * PH * PW * 3
+        bufs = getattr(self, "_log_bufs", None)
+        if bufs is None or bufs[0].numel() != nbytes:
+            bufs = self._log_bufs = (torch.empty(nbytes, dtype=torch.uint8, device=self.device),
+                                     torch.empty(nbytes, dtype=torch.uint8, pin_memory=True))
+        panels, sources = logimg.training_panels(o, inputs, outputs, range(n), buf=bufs[0], return_sources=True)
+        bufs[1].copy_(panels.view(-1), non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        host = bufs[1].numpy().reshape(n, PH, PW, 3).copy()          # (the pinned buffer is the next call's as well)
+        folder = os.path.join(self.log_path, mode, "images")
+        os.makedirs(folder, exist_ok=True)
+        for j in range(n):
+            Image.fromarray(host[j]).save(os.path.join(folder, "{:07d}_{}.jpg".format(int(step), j)), quality=90)
+        return (host, sources) if return_sources else host
+
+    def _logged_predictions(self, inputs, outputs, B, n):
+        """(inputs, outputs) cut to the first n items, with the warped images the fused step did not write: the trainer's own
+        loss call (per-scale poses of posecnn, one call per scale under v1_multiscale) on the slices, materialize=True, no
+        gradient, no noise drawn.  The step's argmin / disparities / masks are kept as they are."""
+        def cut(v):
+            if isinstance(v, dict):
+                return {k: cut(x) for k, x in v.items()}
+            return v[:n].detach() if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == B else v
+        ins, outs = cut(dict(inputs)), cut(dict(outputs))
+        redo = dict(outs)
+        with torch.no_grad():
+            (self.fused_losses_v1 if self.opt.v1_multiscale else self.fused_losses)(ins, redo, materialize=True, draw_noise=False)
+        for f in (-1, 1):
+            outs[("color", f, 0)] = redo[("color", f, 0)]
+        return ins, outs
 
     # ------------------------------------------------------------------ trainer.py:700-763
     @property
