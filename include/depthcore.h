@@ -895,6 +895,40 @@ typedef struct dc_cached_img {
 int dc_data_cached_levels(const uint8_t* arena, size_t arena_bytes, const dc_cached_img* desc_host, const dc_cached_img* desc_dev,
                           int n_img, int height, int width, int num_scales, float* const* color, float* const* color_aug,
                           float* packed, const int* steps, const float* params, unsigned long long* sums, void* stream);
+/* Sequence item (datasets/kitti_dataset_seq.py:100-175): n + 2 consecutive frames of one drive, read as three windows of n
+ * frames -- centre 1..n, left 0..n-1, right 2..n+1.  Per frame and level the reference's chain is
+ *     r = resize(u[s-1]);  m = mirror(r) if flip;  u[s] = ColorJitter_fresh(m) if jittered;  ("color", s) = u[s] / 255
+ * with u[-1] the decoded frame: the mirror ACCUMULATES over the levels and level s + 1 is resized from the JITTERED level s.
+ * frames: the UNMIRRORED level 0, (n + 2, H, W, 3) uint8 (dc_data_resize_axis x2 of the native frames).
+ *   steps == params == NULL: n_img = n + 2 images, one per frame -- the windows are the slices [1:n+1], [0:n], [2:n+2] of
+ *     every output, nothing is made twice.
+ *   steps / params (3n, S, 4), encoded per (image, level) as dc_data_jitter encodes an image: n_img = 3n images, window-major
+ *     (i = w * n + j, w in the order centre, left, right); image i gathers frame j + (1, 0, 2)[w].  Both or neither.
+ *   color[s] (n_img, 3, H>>s, W>>s) float32 (HOST array of S device pointers); packed (n_img, H, W, 4) RGBx of level 0, 16-byte
+ *     aligned.  The bytes are those of dc_data_resize_axis (width, then height), dc_data_flip, dc_data_jitter and
+ *     dc_data_to_tensor / dc_data_to_rgbx applied level after level; sums are integers, so two calls give the same bits.
+ *   tab_host / tab_dev: host and device copies of the concatenated dc_resample_table results, for s = 1..S-1 in turn
+ *     [bounds (W>>s, 2) | kk (W>>s, 13) | bounds (H>>s, 2) | kk (H>>s, 13)] of W>>(s-1) -> W>>s and H>>(s-1) -> H>>s
+ *     (tab_len ints = dc_seq_plan.table_len; may be NULL for S == 1).  Every tap is checked on the host copy.
+ *   scratch: 16-byte aligned, dc_seq_plan.scratch_bytes; DC_EWORKSPACE when smaller.
+ * dc_data_seq_plan (HOST, no GPU): one workgroup per image carries the image from level `tail_start` -- the first whose uint8
+ *   form and pass buffer fit the LDS budget -- down to level S-1 on chip, in one launch; the levels before it go through HBM
+ *   with the whole machine on each.  lds_budget bytes: 0 = the library's default of 12 KiB, which at training sizes leaves
+ *   every level to the HBM path (measured faster there: a tail puts one compute unit on an image); larger values are clamped
+ *   to the 160 KiB a gfx950 workgroup may hold.  tail_start == S: no level fits.  The bytes do not depend on the split.
+ * Everything is validated before the first launch: DC_EINVAL (nothing launched, nothing written) for a NULL pointer, n < 1,
+ * S outside 1..DC_MAX_SCALES, H or W not divisible by 2^(S-1), a misaligned packed / scratch, only one of steps / params, a
+ * tab_len that is not the plan's, a tap outside its axis.  No allocation, no synchronisation; on `stream`: one launch for the
+ * tail, and per level in front of it one finish pass, a luma-sum pass when jittered and, from level 1 on, the two resize passes
+ * (192 x 640, four levels through HBM: 10 launches un-jittered, 14 and a memset jittered). */
+typedef struct dc_seq_plan {
+    long long lds_bytes, table_len, scratch_bytes;
+    int n_img, tail_start;
+} dc_seq_plan;
+int dc_data_seq_plan(int n, int H, int W, int S, int jitter, int lds_budget, dc_seq_plan* plan);
+int dc_data_seq_levels(const uint8_t* frames, int n, int H, int W, int S, int flip, float* const* color, float* packed,
+                       const int* steps, const float* params, const int* tab_host, const int* tab_dev, size_t tab_len,
+                       void* scratch, size_t scratch_bytes, int lds_budget, void* stream);
 
 /* ------------------------------------------------------------------ depth metrics (validation)
  * Trainer.compute_depth_losses (trainer.py:624-652, called at :248 and from val at :460) and the KITTI Eigen protocol of

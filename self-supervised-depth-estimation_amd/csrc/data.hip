@@ -9,7 +9,8 @@
 //     (exact 64-bit sum); hue = uint8 shift of H between Pillow's float/double RGB<->HSV conversions;
 //   * ToTensor: CHW float32, true division by 255.
 // HBM-bound byte work: no LDS staging needed beyond what L2 gives the overlapping filter taps; one thread per output pixel.
-#include "dc_common.h"
+// The per-pixel arithmetic (clip, luma, blend, HSV, the jitter step) lives in data_dev.h, shared with seqdata.hip.
+#include "data_dev.h"
 
 #include <math.h>
 
@@ -18,13 +19,6 @@
 #pragma clang fp contract(off)   // Pillow's C is compiled without fused multiply-adds; every rounding below is load-bearing
 
 namespace dc {
-
-constexpr int kPrecisionBits = 32 - 8 - 2;   // Resample.c PRECISION_BITS
-
-__device__ __forceinline__ uint8_t clip8(int acc) {
-    const int v = acc >> kPrecisionBits;
-    return (uint8_t)min(max(v, 0), 255);
-}
 
 // src (n, H, Wi, 3) -> dst (n, H, Wo, 3); flip[img] != 0 reads the row mirrored (FLIP_LEFT_RIGHT before the resize)
 __global__ __launch_bounds__(256) void data_resize_x_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int H, int Wi, int Wo,
@@ -144,67 +138,6 @@ __global__ __launch_bounds__(256) void data_ragged_y_kernel(const uint8_t* __res
     *o = clip8(a);
 }
 
-// ------------------------------------------------------------------------------------------------------------- ColorJitter
-__device__ __forceinline__ int luma(int r, int g, int b) { return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16; }   // Convert.c L24
-
-// Blend.c: (UINT8)(in1 + alpha * (in2 - in1)), in1 = degenerate; outside [0, 1]: clip, then truncate
-__device__ __forceinline__ uint8_t blend(int d, int x, float a, bool interp) {
-    float m = a * (float)(x - d);
-    asm volatile("" : "+v"(m));   // the product is rounded before the add: HIP's __fmul_rn / __fadd_rn are plain operators that
-    const float t = (float)d + m;  // the compiler fuses, and a fused multiply-add differs whenever a * (x - d) is near an integer
-    if (interp) return (uint8_t)(int)t;
-    return t <= 0.f ? 0 : (t >= 255.f ? 255 : (uint8_t)(int)t);
-}
-
-// Convert.c rgb2hsv_row: float variables, double literals (see oracle/data_ref.py)
-__device__ __forceinline__ void rgb2hsv(int r, int g, int b, int& uh, int& us, int& uv) {
-    const int maxc = max(r, max(g, b)), minc = min(r, min(g, b));
-    uv = maxc;
-    if (minc == maxc) {
-        uh = 0;
-        us = 0;
-        return;
-    }
-    const float cr = (float)(maxc - minc);
-    const float s = cr / (float)maxc;
-    const float rc = (float)(maxc - r) / cr, gc = (float)(maxc - g) / cr, bc = (float)(maxc - b) / cr;
-    float h;
-    if (r == maxc)
-        h = bc - gc;
-    else if (g == maxc)
-        h = (float)(2.0 + (double)rc - (double)bc);
-    else
-        h = (float)(4.0 + (double)gc - (double)rc);
-    double hd = (double)h / 6.0 + 1.0;          // in [5/6, 11/6]
-    hd = hd >= 1.0 ? hd - 1.0 : hd;             // fmod(., 1.0), exact
-    h = (float)hd;
-    uh = min(max((int)((double)h * 255.0), 0), 255);
-    us = min(max((int)((double)s * 255.0), 0), 255);
-}
-
-// Convert.c hsv2rgb
-__device__ __forceinline__ void hsv2rgb(int h, int s, int v, int& r, int& g, int& b) {
-    if (s == 0) {
-        r = g = b = v;
-        return;
-    }
-    const double fh = (double)(float)h * 6.0 / 255.0;
-    const int i = (int)floor(fh);
-    const double f = (double)(float)(fh - (double)(float)i);
-    const double fs = (double)(float)((double)(float)s / 255.0);
-    const double vf = (double)(float)v;
-    const int p = min(max((int)round(vf * (1.0 - fs)), 0), 255);
-    const int q = min(max((int)round(vf * (1.0 - fs * f)), 0), 255);
-    const int t = min(max((int)round(vf * (1.0 - fs * (1.0 - f))), 0), 255);
-    switch (i % 6) {
-        case 0: r = v, g = t, b = p; break;
-        case 1: r = q, g = v, b = p; break;
-        case 2: r = p, g = v, b = t; break;
-        case 3: r = p, g = q, b = v; break;
-        case 4: r = t, g = p, b = v; break;
-        default: r = v, g = p, b = q; break;
-    }
-}
 
 // exact sum of the L image, only for images whose op at this step is CONTRAST
 __global__ __launch_bounds__(256) void data_luma_sum_kernel(const uint8_t* __restrict__ img, int npix, const int* __restrict__ steps, int step,
@@ -220,24 +153,6 @@ __global__ __launch_bounds__(256) void data_luma_sum_kernel(const uint8_t* __res
     if ((threadIdx.x & 63) == 0) atomicAdd(&sums[im], a);
 }
 
-// one ColorJitter operation on one pixel (the arithmetic of the in-place kernel below and of the fused chain kernels)
-__device__ __forceinline__ void jitter_op(int& r, int& g, int& b, int op, float a, int mean) {
-    if (op == DC_JITTER_HUE) {
-        int h, s, v;
-        rgb2hsv(r, g, b, h, s, v);
-        h = (h + (int)a) & 0xFF;
-        hsv2rgb(h, s, v, r, g, b);
-    } else if (op >= 0) {
-        const bool interp = a >= 0.f && a <= 1.f;
-        int d0 = 0;
-        if (op == DC_JITTER_CONTRAST) d0 = mean;
-        else if (op == DC_JITTER_SATURATION) d0 = luma(r, g, b);
-        r = blend(d0, r, a, interp);
-        g = blend(d0, g, a, interp);
-        b = blend(d0, b, a, interp);
-    }
-}
-__device__ __forceinline__ int luma_mean(unsigned long long sum, int npix) { return (int)((double)sum / (double)npix + 0.5); }   // int(ImageStat mean + 0.5)
 
 __global__ __launch_bounds__(256) void data_jitter_kernel(uint8_t* __restrict__ img, int npix, const int* __restrict__ steps,
                                                          const float* __restrict__ params, int step,
@@ -261,18 +176,6 @@ __global__ __launch_bounds__(256) void data_jitter_kernel(uint8_t* __restrict__ 
 // the chain).  Pass 1 re-applies the operations in front of the contrast step and sums L (exact integers; skipped for an
 // image without a contrast step); pass 2 recomputes the whole chain per pixel and writes BOTH float tensors of ToTensor --
 // ("color", s) from the untouched pixel and ("color_aug", s) from the jittered one.  Per scale: 2 launches instead of 14.
-struct JChain { int op[4]; float a[4]; int c; };
-__device__ __forceinline__ JChain jchain_load(const int* steps, const float* params, int im) {
-    JChain ch;
-    ch.c = -1;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        ch.op[k] = steps ? steps[im * 4 + k] : DC_JITTER_NONE;
-        ch.a[k] = steps ? params[im * 4 + k] : 0.f;
-        if (ch.op[k] == DC_JITTER_CONTRAST && ch.c < 0) ch.c = k;
-    }
-    return ch;
-}
 __global__ __launch_bounds__(256) void data_chain_sum_kernel(const uint8_t* __restrict__ img, int npix, const int* __restrict__ steps,
                                                             const float* __restrict__ params, unsigned long long* __restrict__ sums) {
     const int im = blockIdx.y;

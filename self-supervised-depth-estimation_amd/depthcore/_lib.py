@@ -122,6 +122,12 @@ class PanelTile(Structure):
                 ("h", c_int32), ("w", c_int32), ("up", c_int32), ("x0", c_int32), ("y0", c_int32), ("thr", c_int32)]
 
 
+class SeqPlan(Structure):
+    """Mirror of `dc_seq_plan` (include/depthcore.h: dc_data_seq_plan)."""
+    _fields_ = [("lds_bytes", ctypes.c_longlong), ("table_len", ctypes.c_longlong), ("scratch_bytes", ctypes.c_longlong),
+                ("n_img", c_int32), ("tail_start", c_int32)]
+
+
 _lib = None
 
 
@@ -291,6 +297,8 @@ def _sig(lib):
         "dc_data_jitter_to_tensor": (i, [p, p, p, i, i, p, p, p, p]),
         "dc_data_ragged_resize_axis": (i, [p, z, p, z, p, p, i, i, i, p, p, i, p, p, z, p, z, p]),
         "dc_data_cached_levels": (i, [p, z, p, p, i, i, i, i, p, p, p, p, p, p, p]),
+        "dc_data_seq_plan": (i, [i, i, i, i, i, i, POINTER(SeqPlan)]),
+        "dc_data_seq_levels": (i, [p, i, i, i, i, i, p, p, p, p, p, p, z, p, z, i, p]),
         "dc_attnconv_fwd": (i, [POINTER(AttnMap), POINTER(AttnParams), POINTER(AttnMap), p, i, i, i, i, i, i, p]),
         "dc_attnconv_param_count": (i, [i]),
         "dc_attnconv_bwd_workspace": (z, [i, i, i, i]),

@@ -69,6 +69,35 @@ def sample_item(is_train=True, rng=random, brightness=(0.8, 1.2), contrast=(0.8,
     return bool(do_flip), jitter
 
 
+WINDOW_FIRST = (1, 0, 2)      # first frame of the centre, left and right window of a sequence item, in the reference's order
+WINDOW_FRAMES = (0, -1, 1)    # and the frame id each window is handed out under
+
+
+def sample_sequence(is_train, rng, n, num_scales=4, brightness=(0.8, 1.2), contrast=(0.8, 1.2), saturation=(0.8, 1.2), hue=(-0.1, 0.1)):
+    """The random draws of one sequence item in the reference's order (datasets/kitti_dataset_seq.py:104-131, :159-175):
+    do_flip FIRST, then do_color_aug (the opposite of `sample_item`), then -- only when do_color_aug -- one fresh
+    ColorJitter draw per window (centre, left, right), per frame j of the window and per level s, in that nesting: the
+    four factors, then the shuffle of the order, as `sample_item` draws them.
+    -> (do_flip, jitters) with jitters = None or jitters[w][j][s] = (order, factors)."""
+    do_flip = is_train and rng.random() > 0.5
+    do_color_aug = is_train and rng.random() > 0.5
+    jitters = None
+    if do_color_aug:
+        jitters = []
+        for _ in WINDOW_FIRST:
+            window = []
+            for _ in range(n):
+                levels = []
+                for _ in range(num_scales):
+                    factors = [rng.uniform(*brightness), rng.uniform(*contrast), rng.uniform(*saturation), rng.uniform(*hue)]
+                    order = [0, 1, 2, 3]
+                    rng.shuffle(order)
+                    levels.append((tuple(order), tuple(factors)))
+                window.append(levels)
+            jitters.append(window)
+    return bool(do_flip), jitters
+
+
 def hue_shift(hue_factor):
     """torchvision functional_pil.adjust_hue: `np.uint8(hue_factor * 255)` (truncation toward zero, wrap to 8 bits)."""
     return int(hue_factor * 255) & 0xFF
@@ -85,6 +114,7 @@ class GpuPreprocessor:
             raise _lib.DepthcoreError("GpuPreprocessor needs a GPU device; there is no CPU path")
         self._tables = {}
         self._ragged = {}
+        self._seq_tab = None
 
     def _table(self, in_size, out_size):
         key = (in_size, out_size)
@@ -339,6 +369,79 @@ class GpuPreprocessor:
                 pk = packed.view(Fn, B, self.height, self.width, 4)
                 for i, f in enumerate(self.frame_idxs):
                     out[("color_packed", f, 0)] = pk[i]
+        return out
+
+    # ---- sequence items: n + 2 consecutive frames read as three windows of n (datasets/kitti_dataset_seq.py) ---------------
+    seq_lds_budget = 0      # dc_data_seq_plan's LDS budget in bytes; 0 = the library's default.  Moves the on-chip tail's start.
+
+    def _seq_tables(self):
+        """Host and device copies of the halving tables of levels 1.. (the layout dc_data_seq_levels reads), made once."""
+        if self._seq_tab is None:
+            parts = []
+            for s in range(1, self.num_scales):
+                for size in (self.width, self.height):
+                    bounds, kk = resample_table(size >> (s - 1), size >> s)
+                    parts += [bounds.reshape(-1), kk.reshape(-1)]
+            host = np.concatenate(parts) if parts else np.zeros(0, np.int32)
+            self._seq_tab = (host, torch.from_numpy(host).to(self.device) if parts else None)
+        return self._seq_tab
+
+    def sequence_plan(self, n, jitter=False):
+        """dc_data_seq_plan for this preprocessor's sizes: where the on-chip tail starts, its LDS, the scratch it needs."""
+        plan = _lib.SeqPlan()
+        check(_lib.lib().dc_data_seq_plan(int(n), self.height, self.width, self.num_scales, 1 if jitter else 0, int(self.seq_lds_budget),
+                                          plan), "dc_data_seq_plan")
+        return plan
+
+    def sequence(self, native, flip=False, jitters=None):
+        """One sequence item.  native: (n + 2, Hn, Wn, 3) uint8 device tensor, consecutive frames of one drive; flip: the
+        item's do_flip; jitters: None or jitters[w][j][s] = (order, factors) (`sample_sequence`).  The frames are resized
+        to level 0 once (no resize when the native size is the target's, as torchvision's Resize returns the image), then
+        one dc_data_seq_levels call makes every level with the reference's chain -- the mirror accumulating from level to
+        level, each level resized from the jittered one before it.
+        -> the ALREADY STACKED dict `Trainer._process_batch` takes: ("color", f, s) (n, 3, h, w) for f in 0, -1, 1,
+        ("color_aug", f, s) the same tensor objects (the reference has no such key: both networks and the loss read
+        "color"), ("color_packed", f, 0) (n, H, W, 4).  Without jitters the three windows are slices [1:n+1], [0:n], [2:n+2]
+        of ONE (n + 2)-frame pyramid; with jitters every window has its own images."""
+        if native.dtype != torch.uint8 or native.dim() != 4 or native.shape[-1] != 3 or not native.is_cuda or not native.is_contiguous():
+            raise _lib.DepthcoreError("native frames must be a contiguous (n + 2, H, W, 3) uint8 device tensor")
+        n = native.shape[0] - 2
+        if n < 1:
+            raise _lib.DepthcoreError("a sequence item has n + 2 >= 3 frames, got %d" % native.shape[0])
+        L, S, dev, H, W = _lib.lib(), self.num_scales, native.device, self.height, self.width
+        aug = jitters is not None
+        n_img = 3 * n if aug else n + 2
+        steps = params = None
+        if aug:
+            if len(jitters) != 3 or any(len(win) != n or any(len(lv) != S for lv in win) for win in jitters):
+                raise _lib.DepthcoreError("jitters[w][j][s]: 3 windows of %d frames of %d levels" % (n, S))
+            host = np.zeros(n_img * S * 8, np.int32)          # [steps (3n, S, 4) int32 | params (3n, S, 4) float32]: one copy
+            st_h, pr_h = host[:n_img * S * 4].reshape(n_img, S, 4), host[n_img * S * 4:].view(np.float32).reshape(n_img, S, 4)
+            for w, win in enumerate(jitters):
+                for j, levels in enumerate(win):
+                    for s, (order, factors) in enumerate(levels):
+                        for k, op in enumerate(order):
+                            st_h[w * n + j, s, k] = op
+                            pr_h[w * n + j, s, k] = float(hue_shift(factors[op])) if op == HUE else factors[op]
+            host_dev = torch.from_numpy(host).to(dev)
+            steps, params = host_dev.data_ptr(), host_dev.data_ptr() + n_img * S * 16
+        level0 = self._resize(native, H, W, None)
+        plan = self.sequence_plan(n, aug)
+        tab_host, tab_dev = self._seq_tables()
+        scratch = torch.empty(max(int(plan.scratch_bytes), 16), dtype=torch.uint8, device=dev)
+        color = [torch.empty((n_img, 3, H >> s, W >> s), dtype=torch.float32, device=dev) for s in range(S)]
+        packed = torch.empty((n_img, H, W, 4), dtype=torch.float32, device=dev)
+        ptrs = _lib.c_void_p * S
+        check(L.dc_data_seq_levels(level0.data_ptr(), n, H, W, S, 1 if flip else 0, ptrs(*[c.data_ptr() for c in color]), packed.data_ptr(),
+                                   steps, params, tab_host.ctypes.data if tab_dev is not None else None,
+                                   tab_dev.data_ptr() if tab_dev is not None else None, tab_host.size, scratch.data_ptr(), scratch.numel(),
+                                   int(self.seq_lds_budget), stream(native)), "dc_data_seq_levels")
+        out = {}
+        for w, (first, f) in enumerate(zip(WINDOW_FIRST, WINDOW_FRAMES)):
+            lo = w * n if aug else first
+            for s in range(S):
+                out[("color", f, s)] = out[("color_aug", f, s)] = color[s][lo:lo + n]
+            out[("color_packed", f, 0)] = packed[lo:lo + n]
         return out
 
     def intrinsics(self, K, batch):

@@ -22,6 +22,9 @@ the cache lacks, and a warm batch is gathered from cache slots in two launches. 
 A dataset with `device_depth` whose velodyne scans are present (KITTIRAWDataset) gets its "depth_gt" on the device: the pool
 threads read each item's scan into the staging buffer behind the frames, the one copy carries them and the projection's
 descriptors, and `ops.lidar_depth_maps_staged` runs on the loader's stream -- with or without the frame cache.
+
+`SequenceLoader` is the same machine for the ConvGRU front-end's items (datasets/kitti_dataset_seq.py): one item of n + 2
+consecutive frames per step, already stacked over its n positions (GpuPreprocessor.sequence), its n scans behind the frames.
 """
 import collections
 import os
@@ -33,7 +36,7 @@ import torch
 from PIL import Image
 
 from . import lidar
-from .data import GpuPreprocessor, sample_item
+from .data import GpuPreprocessor, sample_item, sample_sequence
 from .frame_cache import FrameCache
 
 MAX_THREADS = 16      # decode threads: bounded by the option and by this, never by the machine's core count
@@ -88,18 +91,15 @@ def _image_size(path):
             return img.height, img.width
 
 
-class BatchLoader:
-    def __init__(self, dataset, batch_size, num_workers=12, device="cuda", seed=0, shuffle=True, rank=0, world_size=1, prefetch=2,
-                 cache_bytes=0):
-        """cache_bytes > 0: keep resized frames on the device (depthcore/frame_cache.py) in an arena of that many bytes --
-        a frame is decoded the first time a batch needs it and served from its slot afterwards.  0: no cache."""
-        self.dataset, self.batch_size = dataset, int(batch_size)
-        self.cache = None
-        if cache_bytes:
-            self.cache = FrameCache(dataset.height, dataset.width, dataset.num_scales, cache_bytes,
-                                    len(dataset.frame_idxs) * self.batch_size, device)
-        self.is_train = bool(dataset.is_train)
-        self.seed, self.shuffle, self.rank, self.world_size = int(seed), bool(shuffle), int(rank), int(world_size)
+class _StagedLoader:
+    """What BatchLoader and SequenceLoader share: the decode pool, the two pinned staging buffers, the velodyne scans that
+    travel behind the frames, and the epoch iteration with its prefetch.  A subclass gives `dataset`, `__len__`, `plan`
+    (-> [arguments of `_submit`]), `_submit(*plan entry, alloc=)` (-> job dict with "futures") and `_upload(job, slot)`
+    (-> (batch dict, event)); `cache` is None unless the subclass has a frame cache and a `_submit_cached`."""
+    cache = None
+
+    def _init_staging(self, num_workers, device, seed, shuffle, prefetch):
+        self.seed, self.shuffle = int(seed), bool(shuffle)
         self.prefetch = max(0, min(int(prefetch), 2))        # two staging buffers: at most two batches ahead
         self.device = torch.device(device)
         self.epoch = 0
@@ -109,41 +109,19 @@ class BatchLoader:
         self._staging, self._copied = [None, None], [None, None]
         self._jobs = collections.deque()
 
-    # ------------------------------------------------------------------------------------------------------------ host half
-    def __len__(self):
-        """Steps per epoch: the same on every rank (drop_last over the rank's shard)."""
-        return len(self.dataset) // self.world_size // self.batch_size
-
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
-
-    def plan(self, epoch=None):
-        """The epoch's batches: [(indices, draws)], draws = one `sample_item` result per item, in item order."""
-        rng = epoch_rng(self.seed, self.epoch if epoch is None else epoch)
-        order = list(range(len(self.dataset)))
-        if self.shuffle:
-            rng.shuffle(order)
-        order = order[self.rank::self.world_size][:len(self) * self.batch_size]
-        batches = []
-        for i in range(len(self)):
-            indices = order[i * self.batch_size:(i + 1) * self.batch_size]
-            batches.append((indices, [sample_item(self.is_train, rng) for _ in indices]))
-        return batches
 
     def _pool_(self):
         if self._pool is None:
             self._pool = ThreadPoolExecutor(self.threads, thread_name_prefix="depthcore-decode")
         return self._pool
 
-    def _scans(self, indices, flips, frame_bytes):
-        """The velodyne half of a job for a dataset that projects "depth_gt" on the device (`device_depth` with scans present),
-        else None: the scans go into the staging buffer behind the frames, back to back from the next 16-byte boundary, the
-        descriptors of the projection (lidar.descriptors) behind them, and `_lidar_depth` turns them into the batch's
-        "depth_gt" after the one upload -- no further copy, nothing that waits for the device."""
-        ds = self.dataset
-        if not (getattr(ds, "device_depth", False) and getattr(ds, "load_depth", False)):
-            return None
-        sources = [ds.depth_source(i) for i in indices]
+    def _scan_job(self, sources, flips, frame_bytes):
+        """The velodyne half of a job: sources = [(scan path, calibration folder, camera)], one map each.  The scans go into
+        the staging buffer behind the frames, back to back from the next 16-byte boundary, the descriptors of the projection
+        (lidar.descriptors) behind them, and `_lidar_depth` turns them into "depth_gt" after the one upload -- no further
+        copy, nothing that waits for the device."""
         nbytes = [os.path.getsize(path) for path, _, _ in sources]
         if any(n % 16 for n in nbytes):
             raise ValueError("a velodyne scan is rows of four float32: %s has %d bytes"
@@ -151,7 +129,7 @@ class BatchLoader:
         calib = [lidar.velo_to_image(calib_dir, cam) for _, calib_dir, cam in sources]
         off = (frame_bytes + 15) // 16 * 16
         end = off + sum(nbytes)
-        width, height = ds.full_res_shape
+        width, height = self.dataset.full_res_shape
         desc = lidar.descriptors([n // 16 for n in nbytes], np.stack([c[0] for c in calib]), [c[1] for c in calib],
                                  out_size=(height, width), flips=flips)
         return {"off": off, "end": end, "total": end + desc.host.size, "paths": [s[0] for s in sources], "nbytes": nbytes, "desc": desc}
@@ -170,6 +148,104 @@ class BatchLoader:
         from . import ops
         points = dev[scans["off"]:scans["end"]].view(torch.float32).view(-1, 4)
         return ops.lidar_depth_maps_staged(points, scans["desc"], dev[scans["end"]:scans["total"]])
+
+    def _stage(self, slot, nbytes):
+        """Pinned staging buffer `slot`, free again: the copy that last read it has completed."""
+        if self._copied[slot] is not None:
+            self._copied[slot].synchronize()
+            self._copied[slot] = None
+        if self._staging[slot] is None or self._staging[slot].numel() < nbytes:
+            self._staging[slot] = torch.empty(nbytes + nbytes // 8, dtype=torch.uint8).pin_memory()
+        return self._staging[slot].numpy()
+
+    @staticmethod
+    def _pending(job):
+        """The pool tasks of a submitted job."""
+        return job["futures"] + ([job["meta"]] if job.get("meta") is not None else [])
+
+    def __iter__(self):
+        """One epoch (`set_epoch`) of batches: dicts of device tensors only, the same keys and shapes every step."""
+        for job in self._jobs:                      # an abandoned iteration: let its decodes finish before the buffers go on
+            if "futures" in job:
+                for fut in self._pending(job):
+                    fut.result()
+        self._jobs.clear()
+        batches = self.plan()
+        nxt = 0
+        submit = self._submit if self.cache is None else self._submit_cached
+
+        def submit_until(last):
+            # batch j decodes into staging buffer j % 2: `_stage` waits for the copy of batch j - 2, which has been issued by
+            # then (batch j - 2 is the one being handed out, or an earlier one)
+            nonlocal nxt
+            while nxt < len(batches) and nxt <= last:
+                slot = nxt % 2
+                job = submit(*batches[nxt], alloc=lambda nbytes, slot=slot: self._stage(slot, nbytes))
+                job["slot"] = slot
+                self._jobs.append(job)
+                nxt += 1
+
+        for step in range(len(batches)):
+            submit_until(step)
+            cur = self._jobs.popleft()
+            if "futures" in cur:
+                cur = dict(zip(("batch", "ready"), self._upload(cur, cur["slot"])))
+            submit_until(step + self.prefetch)
+            # the next batch's copy and data step go out now if its frames are already decoded: they run under this step
+            if self._jobs and "futures" in self._jobs[0] and all(f.done() for f in self._pending(self._jobs[0])):
+                job = self._jobs[0]
+                self._jobs[0] = dict(zip(("batch", "ready"), self._upload(job, job["slot"])))
+            consumer = torch.cuda.current_stream(self.device)
+            consumer.wait_event(cur["ready"])
+            for t in cur["batch"].values():
+                t.record_stream(consumer)
+            yield cur["batch"]
+
+    def close(self):
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
+            self._pool = None
+
+
+class BatchLoader(_StagedLoader):
+    def __init__(self, dataset, batch_size, num_workers=12, device="cuda", seed=0, shuffle=True, rank=0, world_size=1, prefetch=2,
+                 cache_bytes=0):
+        """cache_bytes > 0: keep resized frames on the device (depthcore/frame_cache.py) in an arena of that many bytes --
+        a frame is decoded the first time a batch needs it and served from its slot afterwards.  0: no cache."""
+        self.dataset, self.batch_size = dataset, int(batch_size)
+        self.cache = None
+        if cache_bytes:
+            self.cache = FrameCache(dataset.height, dataset.width, dataset.num_scales, cache_bytes,
+                                    len(dataset.frame_idxs) * self.batch_size, device)
+        self.is_train = bool(dataset.is_train)
+        self.rank, self.world_size = int(rank), int(world_size)
+        self._init_staging(num_workers, device, seed, shuffle, prefetch)
+
+    # ------------------------------------------------------------------------------------------------------------ host half
+    def __len__(self):
+        """Steps per epoch: the same on every rank (drop_last over the rank's shard)."""
+        return len(self.dataset) // self.world_size // self.batch_size
+
+    def plan(self, epoch=None):
+        """The epoch's batches: [(indices, draws)], draws = one `sample_item` result per item, in item order."""
+        rng = epoch_rng(self.seed, self.epoch if epoch is None else epoch)
+        order = list(range(len(self.dataset)))
+        if self.shuffle:
+            rng.shuffle(order)
+        order = order[self.rank::self.world_size][:len(self) * self.batch_size]
+        batches = []
+        for i in range(len(self)):
+            indices = order[i * self.batch_size:(i + 1) * self.batch_size]
+            batches.append((indices, [sample_item(self.is_train, rng) for _ in indices]))
+        return batches
+
+    def _scans(self, indices, flips, frame_bytes):
+        """The velodyne half of a job for a dataset that projects "depth_gt" on the device (`device_depth` with scans present),
+        else None (`_scan_job`: one scan per item)."""
+        ds = self.dataset
+        if not (getattr(ds, "device_depth", False) and getattr(ds, "load_depth", False)):
+            return None
+        return self._scan_job([ds.depth_source(i) for i in indices], flips, frame_bytes)
 
     def _submit(self, indices, draws, alloc, device_depth=True):
         """Start decoding a batch: sizes from the headers of each item's first frame, then one task per frame writing at
@@ -257,15 +333,6 @@ class BatchLoader:
         return self._finish(self._submit(indices, draws, alloc, device_depth=False))
 
     # ---------------------------------------------------------------------------------------------------------- device half
-    def _stage(self, slot, nbytes):
-        """Pinned staging buffer `slot`, free again: the copy that last read it has completed."""
-        if self._copied[slot] is not None:
-            self._copied[slot].synchronize()
-            self._copied[slot] = None
-        if self._staging[slot] is None or self._staging[slot].numel() < nbytes:
-            self._staging[slot] = torch.empty(nbytes + nbytes // 8, dtype=torch.uint8).pin_memory()
-        return self._staging[slot].numpy()
-
     def _upload(self, job, slot):
         """One host-to-device copy + the data step, on the loader's stream -> (batch dict, event that completes it)."""
         ds = self.dataset
@@ -337,45 +404,79 @@ class BatchLoader:
             ready.record(self._side)
         return batch, ready
 
-    def __iter__(self):
-        """One epoch (`set_epoch`) of batches: dicts of device tensors only, the same keys and shapes every step."""
-        for job in self._jobs:                      # an abandoned iteration: let its decodes finish before the buffers go on
-            if "futures" in job:
-                for fut in job["futures"] + [job["meta"]]:
-                    fut.result()
-        self._jobs.clear()
-        batches = self.plan()
-        nxt = 0
-        submit = self._submit if self.cache is None else self._submit_cached
 
-        def submit_until(last):
-            # batch j decodes into staging buffer j % 2: `_stage` waits for the copy of batch j - 2, which has been issued by
-            # then (batch j - 2 is the one being handed out, or an earlier one)
-            nonlocal nxt
-            while nxt < len(batches) and nxt <= last:
-                slot = nxt % 2
-                job = submit(*batches[nxt], alloc=lambda nbytes, slot=slot: self._stage(slot, nbytes))
-                job["slot"] = slot
-                self._jobs.append(job)
-                nxt += 1
 
-        for step in range(len(batches)):
-            submit_until(step)
-            cur = self._jobs.popleft()
-            if "futures" in cur:
-                cur = dict(zip(("batch", "ready"), self._upload(cur, cur["slot"])))
-            submit_until(step + self.prefetch)
-            # the next batch's copy and data step go out now if its frames are already decoded: they run under this step
-            if self._jobs and "futures" in self._jobs[0] and all(f.done() for f in self._jobs[0]["futures"] + [self._jobs[0]["meta"]]):
-                job = self._jobs[0]
-                self._jobs[0] = dict(zip(("batch", "ready"), self._upload(job, job["slot"])))
-            consumer = torch.cuda.current_stream(self.device)
-            consumer.wait_event(cur["ready"])
-            for t in cur["batch"].values():
-                t.record_stream(consumer)
-            yield cur["batch"]
+class SequenceLoader(_StagedLoader):
+    """One sequence item per step for the ConvGRU front-end (reference trainer_gru.py:206-240: DataLoader(batch_size=1) over
+    KITTIDataset_v1).  dataset: datasets.KITTISequenceDataset.  `plan(epoch)` is a function of (seed, epoch) alone: the
+    (shuffled) order of the items, then one `sample_sequence` per item in that order.  The n + 2 frames are decoded on the
+    pool into a pinned buffer, the n centre scans -- when the dataset has them -- read behind them, one copy moves both, and
+    the data step (GpuPreprocessor.sequence, then the projection through camera 2 with the mirror applied once) runs on the
+    loader's own stream.  Every GPU call comes from the consuming thread.  No frame cache."""
 
-    def close(self):
-        if self._pool is not None:
-            self._pool.shutdown(wait=True)
-            self._pool = None
+    def __init__(self, dataset, num_workers=12, device="cuda", seed=0, shuffle=True, prefetch=2):
+        self.dataset, self.batch_size = dataset, 1
+        self.is_train = bool(dataset.is_train)
+        self._init_staging(num_workers, device, seed, shuffle, prefetch)
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def plan(self, epoch=None):
+        """The epoch's items: [(index, (do_flip, jitters))]."""
+        ds = self.dataset
+        rng = epoch_rng(self.seed, self.epoch if epoch is None else epoch)
+        order = list(range(len(ds)))
+        if self.shuffle:
+            rng.shuffle(order)
+        return [(i, sample_sequence(self.is_train, rng, ds.n, ds.num_scales)) for i in order]
+
+    def _submit(self, index, draw, alloc, device_depth=True):
+        """Start decoding an item: the size from the header of its first frame, one task per frame writing at its offset of
+        `alloc(total bytes)`, the scans behind them (device_depth=False: frames only).  -> job dict with the futures."""
+        ds = self.dataset
+        paths = ds.frame_paths(index)
+        h, w = _image_size(paths[0])
+        frame_bytes = len(paths) * h * w * 3
+        flip, jitters = bool(draw[0]), draw[1]
+        scans = None
+        if ds.load_depth and device_depth:
+            scans = self._scan_job([(p, ds.calib_dir(index), 2) for p in ds.scan_paths(index)], [flip] * ds.n, frame_bytes)
+        total = scans["total"] if scans else frame_bytes
+        buf = alloc(total)[:total]
+        futures = [self._pool_().submit(_decode_into, path, buf[k * h * w * 3:(k + 1) * h * w * 3].reshape(h, w, 3))
+                   for k, path in enumerate(paths)]
+        if scans:
+            futures += self._read_scans(scans, buf)
+        return {"buf": buf, "frame_bytes": frame_bytes, "shape": (len(paths), h, w, 3), "flip": flip, "jitters": jitters,
+                "futures": futures, "scans": scans}
+
+    def decode_item(self, index, draw=(False, None)):
+        """Host half of one item -> (frames (n + 2, Hn, Wn, 3) uint8, flip, jitters); the scans are left to the device half."""
+        job = self._submit(index, draw, lambda nbytes: np.empty(nbytes, np.uint8), device_depth=False)
+        for fut in job["futures"]:
+            fut.result()
+        return job["buf"].reshape(job["shape"]), job["flip"], job["jitters"]
+
+    def _upload(self, job, slot):
+        """One host-to-device copy + the data step, on the loader's stream -> (batch dict, event that completes it)."""
+        ds = self.dataset
+        if self._pre is None:
+            self._pre = GpuPreprocessor(ds.height, ds.width, ds.num_scales, ds.frame_idxs, self.device)
+            self._intrinsics = self._pre.intrinsics(ds.K, ds.n)
+            self._side = torch.cuda.Stream(self.device)
+        for fut in job["futures"]:
+            fut.result()
+        buf = job["buf"]
+        with torch.cuda.stream(self._side):
+            dev = torch.empty(buf.size, dtype=torch.uint8, device=self.device)
+            dev.copy_(self._staging[slot][:buf.size], non_blocking=True)
+            self._copied[slot] = torch.cuda.Event()
+            self._copied[slot].record(self._side)
+            batch = self._pre.sequence(dev[:job["frame_bytes"]].view(job["shape"]), job["flip"], job["jitters"])
+            batch.update(self._intrinsics)
+            if job["scans"]:
+                batch["depth_gt"] = self._lidar_depth(job["scans"], dev)
+            ready = torch.cuda.Event()
+            ready.record(self._side)
+        return batch, ready

@@ -22,7 +22,8 @@ losses inside the kernels and get their gradient there; the BCE term stays a tor
 through the depth encoder + decoder and fused by `networks.Fusion_v3` (BASELINE configs[4]).
 `opt.gru = "v5"` switches it to trainer_gru.py:595-644 (`run_gru_v5`, BASELINE configs[3]): a batch is ONE sequence of
 `opt.len_sequence` frames (dict keys carry the sequence index: ("color", f, s, j), ("K", s, j)), the encoder features of the
-sequence pass through `networks.ConvGRUBlocks_v5`, and the loss runs on the sequence stacked along the batch.
+sequence pass through `networks.ConvGRUBlocks_v5`, and the loss runs on the sequence stacked along the batch.  Its data
+come from `build_sequence_loaders` (items already stacked by the data step) and its loop is `train_sequences` (train_gru.py).
 `opt.model = "rn_encoder_with_attention"` (or `"rn_fusion"` together with `opt.fusion = "v3"`) builds the depth encoder as
 `networks.ResnetEncoderAttention` (trainer_dpt.py:78-92); every other value, the default included, builds `ResnetEncoder`.
 """
@@ -263,12 +264,17 @@ class Trainer:
         statistics), optimiser state, self.step, the device noise seed, captured graphs -- and the Winograd weight cache is
         invalidated again.  With opt.cpu_tiebreak_noise the loss draws its tie-break noise from the CPU generator, as the
         reference's val does: later training steps then see shifted noise, exactly as there.
-        The sequence front-ends (Fusion_v3, ConvGRU) raise NotImplementedError."""
-        if self.opt.fusion or self.opt.gru:
+        Fusion_v3 raises NotImplementedError, and so does the ConvGRU front-end, whose items go through `val_sequence`."""
+        if self.opt.gru:
+            raise NotImplementedError("val takes an item batch; the ConvGRU front-end validates a sequence item: use val_sequence")
+        if self.opt.fusion:
             raise NotImplementedError(
-                "val for the %s front-end: its depth output is not the depth of frame 0 of a batch (Fusion_v3 refines the decoder "
-                "output of frame -2; run_gru_v5 stacks a sequence along the batch), so the trainer protocol's depth_gt pairing of "
-                "trainer.py:624-652 does not apply" % ("Fusion_v3" if self.opt.fusion else "ConvGRU"))
+                "val for the Fusion_v3 front-end: its depth output is not the depth of frame 0 of a batch (Fusion_v3 refines the "
+                "decoder output of frame -2), so the trainer protocol's depth_gt pairing of trainer.py:624-652 does not apply")
+        return self._validate(inputs)
+
+    def _validate(self, inputs):
+        """The body of `val` and `val_sequence`: one minibatch in eval mode under no_grad, training state left untouched."""
         self.set_eval()
         try:
             with torch.no_grad():
@@ -282,6 +288,15 @@ class Trainer:
         finally:
             self.set_train()
         return outputs, losses
+
+    def val_sequence(self, inputs):
+        """`val` for the ConvGRU front-end on one sequence item (a SequenceLoader's dict, or the per-position dict of
+        synthetic_sequence_batch): what trainer_gru.py:1110-1138 computes -- the depth of the n stacked centre frames against
+        the item's "depth_gt" (n, 1, 375, 1242), which is the "trainer" protocol of `compute_depth_losses` with the batch
+        being the sequence.  Leaves training where it was, as `val` does; returns (outputs, losses)."""
+        if not self.opt.gru:
+            raise ValueError("val_sequence validates the ConvGRU front-end (opt.gru); use val")
+        return self._validate(inputs)
 
     def compute_depth_losses(self, inputs, outputs, losses):
         """Depth metrics for monitoring (trainer.py:624-652): depth upsampled to gt's size (375 x 1242 in the reference), clamped
@@ -327,7 +342,7 @@ class Trainer:
         for key, ipt in inputs.items():
             if ipt.device != self.device:
                 inputs[key] = ipt.to(self.device)
-        if self.opt.gru:
+        if self.opt.gru and ("color", 0, 0) not in inputs:       # a SequenceLoader's item is stacked already (views, no copy)
             inputs = self._stack_sequence(inputs)
         if self.opt.pose_model_type == "shared":
             # trainer.py:263-279: every frame goes through the depth encoder (ONE pass, the frames stacked along the batch --
@@ -663,8 +678,8 @@ class Trainer:
         import datasets
         from depthcore.loader import BatchLoader
         if self.opt.gru:
-            raise NotImplementedError("training loops for the ConvGRU front-end need the reference's sequence dataset "
-                                      "(datasets/kitti_dataset_seq.py), which this project does not have")
+            raise NotImplementedError("these are the item-batch loaders; the ConvGRU front-end reads sequence items: "
+                                      "use build_sequence_loaders")
         if self.opt.dataset not in self.DATASETS:
             raise ValueError("dataset %r: one of %s" % (self.opt.dataset, sorted(self.DATASETS)))
         cls = getattr(datasets, self.DATASETS[self.opt.dataset])
@@ -686,6 +701,87 @@ class Trainer:
         self._val_iter = None
         return self.train_loader, self.val_loader
 
+    def build_sequence_loaders(self, prefetch=2):
+        """The two loaders of trainer_gru.py:206-240 for the ConvGRU front-end: `<splits_dir>/<split>/{train,val}_sequences.txt`
+        list drives ("date/drive" per line, as the reference's splits/eigen_zhou/*_sequences.txt; none ship with the project),
+        the items are drawn ONCE here (datasets.generate_sequences with opt.train_n_tuples / opt.test_n_tuples), and each list
+        gets a depthcore.loader.SequenceLoader -- the training one shuffled and augmented, the validation one neither
+        (trainer_gru.py:234)."""
+        import random
+
+        import datasets
+        from depthcore.loader import SequenceLoader
+        if not self.opt.gru:
+            raise ValueError("build_sequence_loaders serves the ConvGRU front-end (opt.gru); the item-batch loaders are build_loaders'")
+        if self.opt.batch_size != 1 or list(self.opt.frame_ids) != [0, -1, 1]:
+            raise ValueError("sequence training takes batch_size 1 and frame_ids [0, -1, 1], got %r and %r"
+                             % (self.opt.batch_size, self.opt.frame_ids))
+        if self.world_size != 1:
+            raise NotImplementedError("sequence training runs on one rank")
+        ext = ".png" if self.opt.png else ".jpg"
+        n = self.opt.len_sequence
+        loaders = []
+        for mode, n_tuples in (("train", self.opt.train_n_tuples), ("val", self.opt.test_n_tuples)):
+            path = os.path.join(self.opt.splits_dir, self.opt.split, "%s_sequences.txt" % mode)
+            if not os.path.isfile(path):
+                raise FileNotFoundError("%s not found: no split files ship with the project, point --splits_dir at yours" % path)
+            with open(path) as f:
+                drives = [line.strip() for line in f.read().splitlines() if line.strip()]
+            items = datasets.generate_sequences(self.opt.data_path, drives, n, n_tuples, random.Random("depthcore.sequences/%s" % mode))
+            ds = datasets.KITTISequenceDataset(self.opt.data_path, self.opt.height, self.opt.width, n, items, mode == "train", img_ext=ext)
+            loaders.append(SequenceLoader(ds, self.opt.num_workers, self.device, seed=int(mode == "val"), shuffle=mode == "train",
+                                          prefetch=prefetch))
+        self.train_loader, self.val_loader = loaders
+        self._val_iter = None
+        return self.train_loader, self.val_loader
+
+    @staticmethod
+    def is_sequence_log_step(batch_idx, step, log_frequency):
+        """trainer_gru.py:334-338: every log_frequency-th item of an epoch for the whole run -- this trainer has no
+        `step < 2000` term -- or every 2000th step.  `step` counts the steps taken before this one."""
+        return batch_idx % log_frequency == 0 or step % 2000 == 0
+
+    def train_sequences(self):
+        """The ConvGRU front-end's training pipeline (trainer_gru.py:287-311) over `build_sequence_loaders`: per epoch
+        `start_epoch` (which freezes the initial hidden states when (epoch + 1) == opt.h_s_epoch), one `train_step` per
+        sequence item, a checkpoint every opt.save_frequency epochs.  The learning-rate scheduler exists and is NEVER stepped:
+        both of the reference's calls are commented out (trainer_gru.py:316, :330), so the whole run is at opt.learning_rate."""
+        if not self.opt.gru:
+            raise ValueError("train_sequences trains the ConvGRU front-end (opt.gru); use train")
+        if self.train_loader is None:
+            self.build_sequence_loaders()
+        self.epoch = 0
+        self.step = 0
+        self.start_time = time.time()
+        self.num_total_steps = len(self.train_loader) * self.opt.num_epochs
+        self.save_opts()
+        for epoch in range(self.opt.num_epochs):
+            self.start_epoch(epoch)
+            self.run_sequence_epoch()
+            if (self.epoch + 1) % self.opt.save_frequency == 0:
+                self.save_model()
+
+    def run_sequence_epoch(self):
+        """One epoch of trainer_gru.py:313-347.  At its log steps the reference prints `log_time`; the lines it has commented
+        out there -- depth metrics, `log("train")`, `val()` -- are what runs here: the metrics when the item carries
+        "depth_gt", the scalars, and one item of the cycling validation loader through `val_sequence`."""
+        self.set_train()
+        self.train_loader.set_epoch(self.epoch)
+        with self.on_step_stream():
+            for batch_idx, inputs in enumerate(self.train_loader):
+                before_op_time = time.time()
+                outputs, losses = self.train_step(inputs)
+                duration = time.time() - before_op_time
+                step = self.step - 1                   # train_step has counted this step already
+                if self.is_sequence_log_step(batch_idx, step, self.opt.log_frequency):
+                    self.log_time(batch_idx, duration, float(losses["loss"].detach()), step)
+                    losses = dict(losses)
+                    if "depth_gt" in inputs:
+                        self.compute_depth_losses(inputs, outputs, losses)
+                    self.log("train", losses, step)
+                    _, val_losses = self.val_sequence(self._next_val_batch())
+                    self.log("val", val_losses, step)
+
     @staticmethod
     def is_log_step(batch_idx, step, log_frequency):
         """trainer.py:241-245, verbatim: often during the first 2000 steps, then every 2000th.  `step` counts the steps
@@ -697,8 +793,8 @@ class Trainer:
     def train(self):
         """Run the entire training pipeline (trainer.py:210-219)."""
         if self.opt.gru:
-            raise NotImplementedError("train() covers the vanilla and Fusion_v3 front-ends; the ConvGRU loop needs the "
-                                      "reference's sequence dataset")
+            raise NotImplementedError("train() covers the vanilla and Fusion_v3 front-ends; the ConvGRU front-end trains "
+                                      "through train_sequences() (train_gru.py)")
         if self.train_loader is None:
             self.build_loaders()
         self.epoch = 0
@@ -801,7 +897,7 @@ class Trainer:
         if n < 1:
             raise ValueError("log_images: opt.log_images is %r, nothing to draw" % getattr(o, "log_images", 0))
         if o.gru:
-            raise NotImplementedError("image logging for the ConvGRU front-end: its training loop is refused as well")
+            raise NotImplementedError("image logging for the ConvGRU front-end: train_sequences logs scalars only")
         step = self.step if step is None else step
         if 0 in o.scales and ("color", -1, 0) not in outputs:
             inputs, outputs = self._logged_predictions(inputs, outputs, B, n)
