@@ -731,6 +731,29 @@ int dc_gather_copy(const float* const* src, float* const* dst, const size_t* n, 
 int dc_gru_residual_fwd(const float* f, const float* H, float* out, int n, size_t M, void* stream);
 int dc_gru_residual_bwd(const float* g, float* d_H, int n, size_t M, void* stream);
 
+/* Inference form of a v5 cell step for B independent streams (evaluate_depth_gru_fusion.py:504-554 `evaluate_v5_seq`, run for
+ * several scenes in lockstep: depthcore.evaluate.SequencePredictor), EVERY feature level in one launch.  `lv` is a HOST array
+ * of nlev <= 8 descriptors that travels as a kernel argument; the buffers may hold more than B rows (a prefix is stepped, the
+ * rows behind it are not touched).  Without a trace or a backward the state is rewritten in place:
+ *   dc_gru_infer_rh:    rh = gates[:, :C] * h
+ *   dc_gru_infer_tail:  h_next = (1 - u) * h + u * cnm,  u = gates[:, C:];   out = f + (h_next + h) / 2;   h <- h_next
+ *                       (h is written after it was read, the same element by the same thread; nothing else may alias)
+ *   dc_gru_infer_init:  state[l][b] = h0[l] for b < B: M[l] floats of level l's learned initial state, broadcast over B rows
+ * Products and sums are not contracted: bit for bit the elementwise expression in fp32.
+ * DC_EINVAL: a NULL pointer among those the entry uses, nlev outside 1..8, B <= 0, a tensor of 2^31 elements or more. */
+typedef struct dc_gru_infer_level {
+    const float* gates;   /* (B, 2C, P) sigmoid(conv_gates(cat(x, h)))                      */
+    const float* cnm;     /* (B, C, P)  tanh(conv_can(cat(x, r*h)))   (tail only)            */
+    const float* f;       /* (B, C, P)  encoder features of this step (tail only)            */
+    float* h;             /* (B, C, P)  state: read by both, REWRITTEN IN PLACE by the tail  */
+    float* rh;            /* (B, C, P)  r * h                          (rh only)             */
+    float* out;           /* (B, C, P)  f + (h_next + h) / 2           (tail only)           */
+    int32_t C, P;
+} dc_gru_infer_level;
+int dc_gru_infer_rh(const dc_gru_infer_level* lv, int nlev, int B, void* stream);
+int dc_gru_infer_tail(const dc_gru_infer_level* lv, int nlev, int B, void* stream);
+int dc_gru_infer_init(const float* const* h0, float* const* state, const size_t* M, int nlev, int B, void* stream);
+
 /* ------------------------------------------------------------------ transformed-weight cache of the Winograd kernels */
 /* ------------------------------------------------------------------ reduced-precision networks (BASELINE configs[4]) */
 /* "Networks in reduced precision, loss in fp32" (trainer_fusion_v3.py:311-330 under mixed precision; the reference itself

@@ -128,6 +128,11 @@ class SeqPlan(Structure):
                 ("n_img", c_int32), ("tail_start", c_int32)]
 
 
+class GruInferLevel(Structure):
+    """Mirror of `dc_gru_infer_level` (include/depthcore.h: dc_gru_infer_rh / _tail)."""
+    _fields_ = [("gates", _F), ("cnm", _F), ("f", _F), ("h", _F), ("rh", _F), ("out", _F), ("C", c_int32), ("P", c_int32)]
+
+
 _lib = None
 
 
@@ -251,6 +256,9 @@ def _sig(lib):
         "dc_gather_copy": (i, [p, p, p, i, p]),
         "dc_gru_residual_fwd": (i, [p, p, p, i, z, p]),
         "dc_gru_residual_bwd": (i, [p, p, i, z, p]),
+        "dc_gru_infer_rh": (i, [POINTER(GruInferLevel), i, i, p]),
+        "dc_gru_infer_tail": (i, [POINTER(GruInferLevel), i, i, p]),
+        "dc_gru_infer_init": (i, [p, p, p, i, i, p]),
         "dc_set_matrix_precision": (i, [i]),
         "dc_get_matrix_precision": (i, []),
         "dc_clear_error": (i, []),

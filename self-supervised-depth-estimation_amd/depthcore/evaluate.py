@@ -286,3 +286,217 @@ def render_disparities(disps, sizes, percentile=95.0, lut=None, chunk=64):
             for k, i in enumerate(ids):
                 images[i] = rgb[k]
     return images, ranges
+
+
+# ---- recurrent front-ends: ConvGRU v5 (evaluate_depth_gru_fusion.py:504-554) and Fusion_v3 (evaluate_depth_fusion_v3.py:131-165) ----
+class _EvalMode:
+    """predict_disparities' contract as a context: the networks in eval mode under no_grad, every submodule's `training` flag
+    restored on exit (also when the body raises)."""
+
+    def __init__(self, *nets):
+        self.nets = nets
+
+    def __enter__(self):
+        self.flags = [(m, m.training) for net in self.nets for m in net.modules()]
+        self.grad = torch.no_grad()
+        for net in self.nets:
+            net.eval()
+        self.grad.__enter__()
+
+    def __exit__(self, *exc):
+        self.grad.__exit__(*exc)
+        for m, t in self.flags:
+            m.training = t
+        return False
+
+
+def _frames_ok(x, what, shape=None):
+    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32 or not x.is_cuda or \
+            (shape is not None and tuple(x.shape[2:]) != tuple(shape)):
+        raise _lib.DepthcoreError("%s: frames must be a (B,3,h,w) float32 device tensor%s, got %s" % (
+            what, "" if shape is None else " with (h,w) = %s" % (tuple(shape),),
+            "%s %s on %s" % (tuple(x.shape), x.dtype, x.device) if torch.is_tensor(x) else type(x).__name__))
+
+
+def lockstep_groups(lengths, streams):
+    """The schedule that advances independent sequences together: -> [(ids, widths)], one entry per group of up to `streams`
+    sequences.  `ids` are indices into `lengths`, sorted by length (descending, stable) over ALL sequences and then cut into
+    consecutive groups, so a group's members are of similar length; widths[t] is how many of them still have a frame t.  The
+    sequences alive at a step are a PREFIX of ids, which is why a step's tensors are prefix slices: no gather, no mask."""
+    if streams <= 0:
+        raise ValueError("streams must be positive")
+    if any(n <= 0 for n in lengths):
+        raise ValueError("every sequence needs at least one frame")
+    order = sorted(range(len(lengths)), key=lambda i: -lengths[i])
+    groups = []
+    for g0 in range(0, len(order), streams):
+        ids = order[g0:g0 + streams]
+        groups.append((ids, [sum(1 for i in ids if lengths[i] > t) for t in range(lengths[ids[0]])]))
+    return groups
+
+
+class SequencePredictor:
+    """Streaming inference of the ConvGRU v5 front-end for up to `streams` independent sequences that advance together
+    (evaluate_depth_gru_fusion.py:519-548 is one stream): `step(frames)` takes frame t of streams 0..B-1 and returns their
+    scaled disparities; the hidden states live here, one (S, C_k, h_k, w_k) buffer per level, and are carried to the next call.
+
+    One step at batch B: the encoder; the five gate convolutions (dc_conv3x3_fwd over cat(features, state[:B]), sigmoid); ONE
+    dc_gru_infer_rh; the five candidate convolutions; ONE dc_gru_infer_tail, which rewrites state[:B] in place and leaves
+    features + (h_cur + h_prev) / 2; the decoder; dc_disp_to_depth_fwd.  The state buffers are copies (dc_gru_infer_init) of
+    the learned `h0_layer1`, which are never written; the gates / r*h / candidate / fused buffers are allocated once, here."""
+
+    def __init__(self, encoder, gru, decoder, streams=16, min_depth=0.1, max_depth=100.0):
+        if streams <= 0:
+            raise ValueError("streams must be positive")
+        self.encoder, self.gru, self.decoder = encoder, gru, decoder
+        self.streams, self.min_depth, self.max_depth = int(streams), float(min_depth), float(max_depth)
+        cells = gru.cells()
+        dev = cells[0].h0_layer1.device
+        if dev.type != "cuda":
+            raise _lib.DepthcoreError("SequencePredictor runs on depthcore kernels only (the ConvGRU is on %s); there is no CPU path" % dev)
+
+        def buf(mult=1):
+            return [torch.empty((self.streams, mult * c.h0_layer1.shape[1]) + tuple(c.h0_layer1.shape[2:]), dtype=torch.float32, device=dev)
+                    for c in cells]
+        self.state, self.gates, self.rh, self.cnm, self.out = buf(), buf(2), buf(), buf(), buf()
+        self._ws = None
+        self.reset()
+
+    def reset(self):
+        """Every stream back to the learned initial states (as they are now: a later optimiser step is seen by the next reset)."""
+        ops.gru_infer_init([c.h0_layer1 for c in self.gru.cells()], self.state)
+
+    def _workspace(self, B):
+        L = _lib.lib()
+        need = 1
+        for s in self.state:
+            C, H, W = s.shape[1:]
+            need = max(need, L.dc_conv3x3_fwd_workspace(C, C, B, 2 * C, H, W), L.dc_conv3x3_fwd_workspace(C, C, B, C, H, W))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.state[0].device)
+        return self._ws.data_ptr()
+
+    def _fuse(self, features):
+        L = _lib.lib()
+        feats = [f if f.is_contiguous() else f.contiguous() for f in features]
+        B = feats[0].shape[0]
+        if len(feats) != len(self.state) or any(tuple(f.shape) != (B,) + tuple(s.shape[1:]) for f, s in zip(feats, self.state)):
+            raise _lib.DepthcoreError("encoder features %s do not match the ConvGRU's states %s" % (
+                [tuple(f.shape) for f in feats], [tuple(s.shape[1:]) for s in self.state]))
+        if not 1 <= B <= self.streams:
+            raise _lib.DepthcoreError("a step of %d frames on a predictor of %d streams" % (B, self.streams))
+        ops._use_precision(ops._precision[0])                    # the caller's ops.matrix_precision, as ops.conv3x3_block
+        ws = self._workspace(B)
+        st = stream(feats[0])
+        for kind, dst, x1, act in (("conv_gates", self.gates, self.state, ops.ACT_SIGMOID), ("conv_can", self.cnm, self.rh, ops.ACT_TANH)):
+            for cell, f, s1, y in zip(self.gru.cells(), feats, x1, dst):
+                conv = getattr(cell.cgru_1, kind)
+                C, H, W = f.shape[1:]
+                w, b = conv.weight.detach(), conv.bias.detach()
+                # rnn.py:125-134: act(conv(cat(x, h))) / act(conv(cat(x, r*h))), the call ops._GruLevel.forward makes at batch 1
+                check(L.dc_conv3x3_fwd(ptr(f), C, 0, ptr(s1), C, ptr(w), ptr(b), ptr(y), ws, B, w.shape[0], H, W, act, ops.PAD_ZERO, st),
+                      "dc_conv3x3_fwd")
+            if kind == "conv_gates":
+                ops.gru_infer_rh(self.gates, self.state, self.rh, B)
+        ops.gru_infer_tail(self.gates, self.cnm, feats, self.state, self.out, B)
+        return [o[:B] for o in self.out]
+
+    def fuse(self, features):
+        """The recurrent part of a step on its own: the encoder features of frame t of streams 0..B-1 -> features + (h_cur +
+        h_prev) / 2 per level, as VIEWS of this predictor's buffers (the next call overwrites them); the states advance."""
+        with torch.no_grad():
+            return self._fuse(features)
+
+    def _step(self, frames):
+        _frames_ok(frames, "SequencePredictor.step")
+        x = frames if frames.is_contiguous() else frames.contiguous()
+        disp = self.decoder(self._fuse(self.encoder(x)))[("disp", 0)]
+        dst = torch.empty((x.shape[0], 1) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
+        _scaled_disparity(disp, dst, False, self.min_depth, self.max_depth)
+        return dst
+
+    def step(self, frames):
+        """frames (B,3,h,w), B <= streams: frame t of streams 0..B-1 -> (B,1,h,w) scaled disparities; their states advance, the
+        states of the streams behind B stay.  predict_disparities' contract holds for every call."""
+        with _EvalMode(self.encoder, self.gru, self.decoder):
+            return self._step(frames)
+
+
+def predict_disparities_lockstep(encoder, gru, decoder, lengths, batch_fn, min_depth=0.1, max_depth=100.0, streams=16):
+    """The ConvGRU v5 evaluation of several independent scenes that advance in lockstep.  lengths[c]: the frames of scene c;
+    batch_fn(t, ids) -> the (len(ids),3,h,w) float32 device tensor that holds frame t of the scenes `ids`, in that order (called
+    once per step, so a caller that decodes images holds one step's frames at a time).  -> a list with one (n_c,1,h,w) tensor of
+    scaled disparities per scene, in the order of `lengths`.  Schedule: lockstep_groups; contract: predict_disparities'."""
+    groups = lockstep_groups(list(lengths), streams)
+    outs = [None] * len(lengths)
+    with _EvalMode(encoder, gru, decoder):
+        sp = SequencePredictor(encoder, gru, decoder, min(streams, max(len(lengths), 1)), min_depth, max_depth)
+        for g, (ids, widths) in enumerate(groups):
+            if g:
+                sp.reset()
+            steps = [sp._step(batch_fn(t, ids[:B])) for t, B in enumerate(widths)]
+            for c in ids:
+                outs[c] = torch.empty((lengths[c],) + tuple(steps[0].shape[1:]), dtype=torch.float32, device=steps[0].device)
+            pairs = [(steps[t][b], outs[c][t]) for t, B in enumerate(widths) for b, c in enumerate(ids[:B])]
+            ops.copy_segments([p[0] for p in pairs], [p[1] for p in pairs])
+    return outs
+
+
+def predict_disparities_sequences(encoder, gru, decoder, scenes, min_depth=0.1, max_depth=100.0, streams=16):
+    """evaluate_v5_seq (evaluate_depth_gru_fusion.py:504-554) for a list of scenes -> a list of (n_c,1,h,w) scaled disparities
+    in input order.  scenes[c]: the frames of one scene in order, a (n_c,3,h,w) float32 device tensor at the networks'
+    resolution, or a sized iterable that yields them as (1,3,h,w) tensors.  Every scene starts from the learned initial states
+    and its state is carried from frame to frame; the scenes are independent of each other, so up to `streams` of them run as
+    one batch (predict_disparities_lockstep).  Memory beyond the inputs and the result is O(streams)."""
+    scenes = list(scenes)
+    if not scenes:
+        raise ValueError("predict_disparities_sequences: no scenes")
+    lengths = [s.shape[0] if torch.is_tensor(s) else len(s) for s in scenes]
+    for s in scenes:
+        if torch.is_tensor(s):
+            _frames_ok(s, "predict_disparities_sequences")
+    its = [None if torch.is_tensor(s) else iter(s) for s in scenes]
+
+    def batch(t, ids):
+        rows = [scenes[c][t:t + 1] if its[c] is None else next(its[c]) for c in ids]
+        for r in rows:
+            _frames_ok(r, "predict_disparities_sequences", rows[0].shape[2:])
+        return rows[0] if len(rows) == 1 else ops.stack_frames([rows])[0]
+    return predict_disparities_lockstep(encoder, gru, decoder, lengths, batch, min_depth, max_depth, streams)
+
+
+def predict_disparities_fusion(encoder, decoder, fusion, triplets, min_depth=0.1, max_depth=100.0, post_process=False, batch_size=16):
+    """evaluate_depth_fusion_v3.py:131-165 -> (N,1,h,w) scaled disparities on the device.
+
+    `triplets`: (3,N,3,h,w) float32 device tensor, frames [-2, -1, 0] of N test files frame-major (triplets[j, i] is frame j - 2
+    of file i), or an iterable of such (3,B,3,h,w) batches (batch_size is then the iterable's).  A batch goes through
+    encoder -> decoder -> Fusion_v3 stacked along the batch as Trainer._depth_branch stacks it.  post_process: the mirrored
+    triplets are a fusion call of their own and the two results are blended by ops.post_process_disparity (the reference
+    concatenates [x; flip(x)] BEFORE the networks, so that Fusion_v3's three chunks mix frames and mirrored frames).
+    Contract: predict_disparities'."""
+    if batch_size <= 0:
+        raise ValueError("batch_size must be positive")
+    if torch.is_tensor(triplets):
+        if triplets.dim() != 5 or triplets.shape[0] != 3:
+            raise _lib.DepthcoreError("predict_disparities_fusion: triplets must be (3,N,3,h,w), got %s" % (tuple(triplets.shape),))
+        triplets = [triplets[:, i0:i0 + batch_size] for i0 in range(0, triplets.shape[1], batch_size)]
+    outs = []
+    with _EvalMode(encoder, decoder, fusion):
+        for t in triplets:
+            if t.dim() != 5 or t.shape[0] != 3:
+                raise _lib.DepthcoreError("predict_disparities_fusion: a batch must be (3,B,3,h,w), got %s" % (tuple(t.shape),))
+            B = t.shape[1]
+            x = t.reshape((3 * B,) + tuple(t.shape[2:])) if t.is_contiguous() else ops.stack_frames([[t[0], t[1], t[2]]])[0]
+            _frames_ok(x, "predict_disparities_fusion")
+            if post_process:
+                both = ops.flip_concat(x)                                   # [x; flip_w(x)]: rows 3B.. are the mirrored stack
+                disps = [fusion(decoder(encoder(half)))[("disp", 0)] for half in (both[:3 * B], both[3 * B:])]
+                outs.append(ops.post_process_disparity(ops.stack_frames([disps])[0], min_depth, max_depth))
+            else:
+                disp = fusion(decoder(encoder(x)))[("disp", 0)]
+                dst = torch.empty_like(disp)
+                _scaled_disparity(disp, dst, False, min_depth, max_depth)
+                outs.append(dst)
+    if not outs:
+        raise ValueError("predict_disparities_fusion: no triplets")
+    return outs[0] if len(outs) == 1 else ops.stack_frames([outs])[0]

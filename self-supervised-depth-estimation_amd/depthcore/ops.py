@@ -1815,3 +1815,78 @@ def gru_level_sequence(features, h0, conv_gates, conv_can):
     """features (n,C,H,W) of one sequence, h0 (1,C,H,W) -> features + (H[1:] + H[:-1]) / 2, H the hidden states of the cell
     (conv_gates / conv_can: its two nn.Conv2d) run over the frames in order (trainer_gru.py:607-639 at one level)."""
     return _GruLevel.apply(features, h0, conv_gates.weight, conv_gates.bias, conv_can.weight, conv_can.bias)
+
+
+# ---- inference form of the cell step: B independent streams, every level in one launch (dc_gru_infer_*) ---------------------
+def _infer_rows(name, B, *groups):
+    """The tensors of an inference step, one list per kind and one entry per level: contiguous float32 device tensors whose
+    leading dimension holds the streams.  No autograd here: a tensor that requires grad is detached.  -> (lists, B)."""
+    nlev = len(groups[0])
+    if not 1 <= nlev <= 8 or any(len(g) != nlev for g in groups):
+        raise DepthcoreError("%s: 1..8 levels, one tensor per level and kind" % name)
+    groups = [[t.detach() for t in g] for g in groups]
+    rows = min(t.shape[0] for g in groups for t in g)
+    B = rows if B is None else int(B)
+    if not 1 <= B <= rows:
+        raise DepthcoreError("%s: B = %d streams of buffers that hold %d" % (name, B, rows))
+    return groups, B
+
+
+def _infer_levels(gates, h, cnm=None, f=None, rh=None, out=None):
+    """The dc_gru_infer_level array of a step's tensors (shapes checked: gates (S,2C,H,W), the others (S,C,H,W))."""
+    lv = (_lib.GruInferLevel * len(h))()
+    for k, hh in enumerate(h):
+        if hh.dim() != 4 or tuple(gates[k].shape[1:]) != (2 * hh.shape[1],) + tuple(hh.shape[2:]):
+            raise DepthcoreError("level %d: gates %s do not match state %s" % (k, tuple(gates[k].shape), tuple(hh.shape)))
+        C, P = hh.shape[1], hh.shape[2] * hh.shape[3]
+        lv[k].gates, lv[k].h, lv[k].C, lv[k].P = ptr(gates[k]), ptr(hh), C, P
+        for field, ts in (("cnm", cnm), ("f", f), ("rh", rh), ("out", out)):
+            if ts is not None:
+                if ts[k].shape[1:] != hh.shape[1:]:
+                    raise DepthcoreError("level %d: %s %s does not match state %s" % (k, field, tuple(ts[k].shape), tuple(hh.shape)))
+                setattr(lv[k], field, ptr(ts[k]))
+    return lv
+
+
+def gru_infer_rh(gates, h, rh, B=None):
+    """rh[k][:B] = gates[k][:B, :C] * h[k][:B] for every level k, one launch (dc_gru_infer_rh).  Lists with one tensor per
+    level; B: the streams stepped, a prefix of the buffers' rows (default: all).  Writes into `rh`; no autograd."""
+    (gates, h, rh), B = _infer_rows("gru_infer_rh", B, gates, h, rh)
+    check(_lib.lib().dc_gru_infer_rh(_infer_levels(gates, h, rh=rh), len(h), B, stream(h[0])), "dc_gru_infer_rh")
+    return rh
+
+
+def gru_infer_tail(gates, cnm, f, h, out, B=None):
+    """The rest of a cell step after the candidate convolution, every level in one launch (dc_gru_infer_tail): with
+    u = gates[k][:B, C:], h_next = (1 - u) * h + u * cnm, out[k][:B] = f[k] + (h_next + h) / 2, and h[k][:B] IS OVERWRITTEN by
+    h_next.  `f[k]` may hold just the B rows; no autograd."""
+    (gates, cnm, f, h, out), B = _infer_rows("gru_infer_tail", B, gates, cnm, f, h, out)
+    check(_lib.lib().dc_gru_infer_tail(_infer_levels(gates, h, cnm=cnm, f=f, out=out), len(h), B, stream(h[0])), "dc_gru_infer_tail")
+    return out
+
+
+def gru_infer_init(h0, state, B=None):
+    """state[k][b] = h0[k][0] for b < B, every level in one launch (dc_gru_infer_init): the learned initial states (1,C,H,W)
+    broadcast over the streams of the state buffers (S,C,H,W).  `h0` is only read."""
+    (h0, state), _ = _infer_rows("gru_infer_init", 1, h0, state)
+    rows = min(s.shape[0] for s in state)
+    B = rows if B is None else int(B)
+    if not 1 <= B <= rows or any(a.shape[0] != 1 or a.shape[1:] != s.shape[1:] for a, s in zip(h0, state)):
+        raise DepthcoreError("gru_infer_init: h0 (1,C,H,W) into B <= S rows of state (S,C,H,W)")
+    n = len(state)
+    check(_lib.lib().dc_gru_infer_init((ctypes.c_void_p * n)(*[ptr(a) for a in h0]), (ctypes.c_void_p * n)(*[ptr(s) for s in state]),
+                                       (ctypes.c_size_t * n)(*[a.numel() for a in h0]), n, B, stream(state[0])), "dc_gru_infer_init")
+    return state
+
+
+def copy_segments(srcs, dsts):
+    """dsts[i].copy_(srcs[i]) for contiguous float32 device tensors of pairwise equal size, 96 pairs per launch
+    (dc_gather_copy): the rows of a lockstep step go to their scenes' outputs this way."""
+    L = _lib.lib()
+    if len(srcs) != len(dsts) or any(s.numel() != d.numel() or s.numel() == 0 for s, d in zip(srcs, dsts)):
+        raise DepthcoreError("copy_segments: pairs of tensors of equal, non-zero size")
+    for i in range(0, len(srcs), 96):
+        s, d = srcs[i:i + 96], dsts[i:i + 96]
+        k = len(s)
+        check(L.dc_gather_copy((ctypes.c_void_p * k)(*[ptr(t.detach()) for t in s]), (ctypes.c_void_p * k)(*[ptr(t) for t in d]),
+                               (ctypes.c_size_t * k)(*[t.numel() for t in s]), k, stream(d[0])), "dc_gather_copy")

@@ -14,7 +14,8 @@ and writes the outputs.  Where it differs from the reference:
     ResnetEncoderAttention(--num_layers) with --model rn_encoder_with_attention / rn_fusion (trainer_dpt.py:78-92); weights
     saved from the other class are refused.  load_networks() without a `model` option (test_simple.py) takes the class the
     checkpoint was saved from;
-  - the Fusion_v3 and ConvGRU front-ends are not evaluated (NotImplementedError).
+  - the Fusion_v3 and ConvGRU front-ends are refused here (NotImplementedError), as in the reference, where they have scripts
+    of their own: evaluate_depth_fusion_v3.py and evaluate_depth_gru.py next to this file.
 """
 import json
 import os
@@ -100,10 +101,8 @@ def evaluate(opt):
     if opt.eval_split.startswith("odom"):
         raise ValueError("eval_split %r is pose evaluation: run evaluate_pose.py" % opt.eval_split)
     if getattr(opt, "fusion", None) or getattr(opt, "gru", None):
-        raise NotImplementedError(
-            "evaluating the %s front-end: the reference's evaluate_depth_fusion_v3.py concatenates the flipped stack so that "
-            "Fusion_v3's three frame chunks mix frames, and evaluate_depth_gru_fusion.py runs a ConvGRU other than v5"
-            % ("Fusion_v3" if opt.fusion else "ConvGRU"))
+        raise NotImplementedError("evaluating the %s front-end: run %s (this script scores the plain encoder + decoder)"
+                                  % (("Fusion_v3", "evaluate_depth_fusion_v3.py") if opt.fusion else ("ConvGRU", "evaluate_depth_gru.py")))
     assert sum((opt.eval_mono, opt.eval_stereo)) == 1, \
         "Please choose mono or stereo evaluation by setting either --eval_mono or --eval_stereo"
     device = torch.device("cuda", torch.cuda.current_device())
@@ -118,13 +117,30 @@ def evaluate(opt):
         pred_disps = E.predict_disparities(encoder, decoder, image_batches(paths, height, width, opt.batch_size, device),
                                            opt.min_depth, opt.max_depth, opt.post_process, opt.batch_size)
     else:
-        print("-> Loading predictions from {}".format(opt.ext_disp_to_eval))
-        host = np.load(opt.ext_disp_to_eval)
-        if opt.eval_eigen_to_benchmark:
-            host = host[np.load(os.path.join(opt.splits_dir, "benchmark", "eigen_to_benchmark_ids.npy"))]
-        host = np.ascontiguousarray(host, np.float32)
-        pred_disps = torch.from_numpy(host.reshape(host.shape[0], 1, host.shape[-2], host.shape[-1])).to(device)
+        pred_disps = load_external_disparities(opt, device)
 
+    return finish(opt, pred_disps)
+
+
+def load_external_disparities(opt, device):
+    """--ext_disp_to_eval (evaluate_depth.py:138-147): saved disparities, in test_files.txt order, onto the device."""
+    print("-> Loading predictions from {}".format(opt.ext_disp_to_eval))
+    host = np.load(opt.ext_disp_to_eval)
+    if opt.eval_eigen_to_benchmark:
+        host = host[np.load(os.path.join(opt.splits_dir, "benchmark", "eigen_to_benchmark_ids.npy"))]
+    host = np.ascontiguousarray(host, np.float32)
+    return torch.from_numpy(host.reshape(host.shape[0], 1, host.shape[-2], host.shape[-1])).to(device)
+
+
+def load_gt_depths(opt):
+    split_dir = os.path.join(opt.splits_dir, opt.eval_split)
+    return np.load(os.path.join(split_dir, "gt_depths.npz"), fix_imports=True, encoding="latin1", allow_pickle=True)["data"]
+
+
+def finish(opt, pred_disps, load_gt=load_gt_depths):
+    """evaluate_depth.py:149-236 from the predictions on: --save_pred_disps, --no_eval, the benchmark export, scoring, the table
+    and --eval_json.  pred_disps (N,1,h,w) on the device in test_files.txt order; load_gt(opt) -> the ground truths in that
+    order, called only when something is scored.  Shared by evaluate_depth_gru.py and evaluate_depth_fusion_v3.py."""
     if opt.save_pred_disps:
         output_path = os.path.join(opt.load_weights_folder, "disps_{}_split.npy".format(opt.eval_split))
         print("-> Saving predicted disparities to ", output_path)
@@ -145,7 +161,7 @@ def evaluate(opt):
         print("-> No ground truth is available for the KITTI benchmark, so not evaluating. Done.")
         return None
 
-    gt_depths = np.load(os.path.join(split_dir, "gt_depths.npz"), fix_imports=True, encoding="latin1", allow_pickle=True)["data"]
+    gt_depths = load_gt(opt)
     print("-> Evaluating")
     if opt.eval_stereo:
         print("   Stereo evaluation - disabling median scaling, scaling by {}".format(STEREO_SCALE_FACTOR))
