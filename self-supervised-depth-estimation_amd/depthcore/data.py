@@ -9,7 +9,14 @@ Random draws stay on the host (`sample_item`), in the reference's order.  There 
 packed back to back (what a shuffled KITTI loader delivers, depthcore/loader.py) and makes scale 0 with two launches over
 the whole batch (`dc_data_ragged_resize_axis`, tests/test_data_ragged_gpu.py); `GpuPreprocessor.cached` takes frames whose
 resized pyramids already sit in cache slots (depthcore/frame_cache.py) and makes the same dict without any resize, in two
-launches (`dc_data_cached_levels`, tests/test_data_cached_gpu.py).
+launches (`dc_data_cached_levels`, tests/test_data_cached_gpu.py); `GpuPreprocessor.sequence` takes the n + 2 frames of one
+ConvGRU item (`dc_data_seq_levels`, tests/test_seq_data_gpu.py).
+
+Each shared piece is written once: `jitter_rows` is the rule that turns ColorJitter draws into the kernels' (steps, params)
+rows and `jitter_tables` lays them out for a frame-major batch (`_levels`, `cached`; `sequence` lays out its own (window,
+frame, level) rows with `jitter_rows`); `_levels` is the one level loop behind scale 0 (`__call__` and `ragged` differ only
+in how they make scale 0); `_inputs` is the one builder of the output dict (`_levels`, `cached`); `ragged_resize` is the
+two-pass resize of images of different sizes (`ragged` for scale 0, `FrameCache.build` for every level of a slot).
 """
 import random
 
@@ -103,6 +110,30 @@ def hue_shift(hue_factor):
     return int(hue_factor * 255) & 0xFF
 
 
+def jitter_rows(draws):
+    """ColorJitter draws [(order, factors)] as the kernels read them, one row per draw (an order names all four
+    transforms, as `sample_item` and `sample_sequence` draw it): -> (steps (m, 4), the ops in the order they are applied;
+    params (m, 4) float32, the parameter of each step -- the factor of its op, or for HUE its `hue_shift`)."""
+    steps = np.array([order for order, _ in draws], np.intp).reshape(-1, 4)
+    by_op = np.array([(f[BRIGHTNESS], f[CONTRAST], f[SATURATION], hue_shift(f[HUE])) for _, f in draws], np.float32).reshape(-1, 4)
+    return steps, by_op[np.arange(len(steps))[:, None], steps]
+
+
+def jitter_tables(jitters, Fn, B, out=None):
+    """The jitter tables of a frame-major batch (image f * B + b is frame f of item b): jitters holds one entry per item,
+    None or (order, factors), and an item's draw applies to all of its Fn frames.  -> None when no item is jittered, else
+    (steps (Fn * B, 4) int32, params (Fn * B, 4) float32), `NO_OP` steps and zero params for the unjittered items.
+    out: (steps, params) contiguous arrays of the caller's to fill instead of new ones (views of one upload buffer)."""
+    if jitters is None or all(j is None for j in jitters):
+        return None
+    steps, params = out if out is not None else (np.empty((Fn * B, 4), np.int32), np.empty((Fn * B, 4), np.float32))
+    steps[...] = NO_OP
+    params[...] = 0
+    items = [b for b, j in enumerate(jitters) if j is not None]
+    steps.reshape(Fn, B, 4)[:, items], params.reshape(Fn, B, 4)[:, items] = jitter_rows([jitters[b] for b in items])
+    return steps, params
+
+
 class GpuPreprocessor:
     """inputs-dict builder: native frames (uint8 HWC on the device) -> ("color" / "color_aug", frame, scale) float tensors."""
 
@@ -164,51 +195,10 @@ class GpuPreprocessor:
         Fn, B, Hn, Wn, _ = native.shape
         if Fn != len(self.frame_idxs):
             raise _lib.DepthcoreError("%d frame slabs for frame_idxs %r" % (Fn, self.frame_idxs))
-        L = _lib.lib()
-        n = Fn * B
         flip = None
         if flips is not None and any(flips):
             flip = torch.tensor([1 if flips[b] else 0 for _ in range(Fn) for b in range(B)], dtype=torch.uint8).to(native.device)
-        steps = params = sums = None
-        if jitters is not None and any(j is not None for j in jitters):
-            st_h = np.full((n, 4), NO_OP, np.int32)
-            pr_h = np.zeros((n, 4), np.float32)
-            for b, j in enumerate(jitters):
-                if j is None:
-                    continue
-                order, factors = j
-                for k, op in enumerate(order):
-                    val = float(hue_shift(factors[op])) if op == HUE else factors[op]
-                    for f in range(Fn):
-                        st_h[f * B + b, k] = op
-                        pr_h[f * B + b, k] = val
-            steps = torch.from_numpy(st_h).to(native.device)
-            params = torch.from_numpy(pr_h).to(native.device)
-            sums = torch.empty(n, dtype=torch.int64, device=native.device)
-        out = {}
-        img = native.view(n, Hn, Wn, 3)
-        for s in range(self.num_scales):
-            h, w = self.height // (2 ** s), self.width // (2 ** s)
-            img = self._resize(img, h, w, flip if s == 0 else None)
-            color = torch.empty((n, 3, h, w), dtype=torch.float32, device=img.device)
-            aug = torch.empty_like(color) if steps is not None else None
-            check(L.dc_data_jitter_to_tensor(img.data_ptr(), color.data_ptr(), aug.data_ptr() if aug is not None else None, n, h * w,
-                                             steps.data_ptr() if aug is not None else None, params.data_ptr() if aug is not None else None,
-                                             sums.data_ptr() if aug is not None else None, stream(img)), "dc_data_jitter_to_tensor")
-            color = color.view(Fn, B, 3, h, w)
-            color_aug = aug.view(Fn, B, 3, h, w) if aug is not None else color
-            for i, f in enumerate(self.frame_idxs):
-                out[("color", f, s)] = color[i]
-                out[("color_aug", f, s)] = color_aug[i]
-            if s == 0:
-                # the photometric kernels gather from pixel-interleaved RGBx: written here, once per item, from the same uint8
-                # level (same division by 255 -> the same values as ("color", f, 0)) instead of repacked in every training step
-                packed = torch.empty((n, h, w, 4), dtype=torch.float32, device=img.device)
-                check(L.dc_data_to_rgbx(img.data_ptr(), packed.data_ptr(), n, h * w, stream(img)), "dc_data_to_rgbx")
-                packed = packed.view(Fn, B, h, w, 4)
-                for i, f in enumerate(self.frame_idxs):
-                    out[("color_packed", f, 0)] = packed[i]
-        return out
+        return self._levels(self._resize(native.view(Fn * B, Hn, Wn, 3), self.height, self.width, flip), Fn, B, jitters)
 
     # ---- ragged batches: items of different native sizes (a shuffled KITTI batch mixes five) --------------------------------
     def _ragged_tables(self, axis, in_sizes, out_size):
@@ -244,6 +234,24 @@ class GpuPreprocessor:
             kk_dev.data_ptr() if tab is not None else None, kk_dev.numel() if tab is not None else 0, stream(src)),
             "dc_data_ragged_resize_axis")
 
+    def ragged_resize(self, src, src_off, sizes, dst, dst_off, h, w, flips=None):
+        """Images of different sizes -> (h, w, 3) each, in two launches (dc_data_ragged_resize_axis): the width pass into a
+        mid buffer, carrying the mirror, then the height pass into dst.  src, dst: 1-D uint8 device tensors (they may be the
+        same one: no launch reads and writes one buffer); image i is (Hn, Wn, 3) = sizes[i] at byte src_off[i] of src and
+        lands at byte dst_off[i] of dst; flips: one entry per image, or None."""
+        hn, wn = np.array(sizes, np.int64).reshape(-1, 2).T
+        xtab, xdev = self._ragged_tables(1, wn.tolist(), w)
+        ytab, ydev = self._ragged_tables(0, hn.tolist(), h)
+        mid_end = np.cumsum(hn * (w * 3))
+        dx, dy = np.zeros(len(hn), RAGGED_IMG), np.zeros(len(hn), RAGGED_IMG)
+        dx["src_off"], dx["dst_off"], dx["Hi"], dx["Wi"], dx["table"] = src_off, mid_end - hn * (w * 3), hn, wn, xtab
+        if flips is not None:
+            dx["flip"] = np.asarray(flips, bool)
+        dy["src_off"], dy["dst_off"], dy["Hi"], dy["Wi"], dy["table"] = dx["dst_off"], dst_off, hn, w, ytab
+        mid = torch.empty(int(mid_end[-1]), dtype=torch.uint8, device=src.device)
+        self._ragged_pass(src, mid, dx, w, 1, xdev)
+        self._ragged_pass(mid, dst, dy, h, 0, ydev)
+
     def ragged(self, packed_u8, sizes, flips=None, jitters=None):
         """`__call__` for a batch whose items have DIFFERENT native sizes.  packed_u8: 1-D uint8 device tensor holding the
         decoded frames back to back, frame-major like `__call__` (image f * B + b is frame f of item b, (Hn_b, Wn_b, 3));
@@ -256,21 +264,11 @@ class GpuPreprocessor:
         if B == 0 or (flips is not None and len(flips) != B) or (jitters is not None and len(jitters) != B):
             raise _lib.DepthcoreError("sizes, flips and jitters have one entry per item")
         n, h, w = Fn * B, self.height, self.width
-        xtab, xdev = self._ragged_tables(1, [int(s[1]) for s in sizes], w)
-        ytab, ydev = self._ragged_tables(0, [int(s[0]) for s in sizes], h)
-        dx, dy = np.zeros(n, RAGGED_IMG), np.zeros(n, RAGGED_IMG)
-        src_off = mid_off = 0
-        for f in range(Fn):
-            for b, (hn, wn) in enumerate(sizes):
-                i = f * B + b
-                dx[i] = (src_off, mid_off, hn, wn, xtab[b], 1 if flips is not None and flips[b] else 0)
-                dy[i] = (mid_off, i * h * w * 3, hn, w, ytab[b], 0)
-                src_off += int(hn) * int(wn) * 3
-                mid_off += int(hn) * w * 3
-        mid = torch.empty(mid_off, dtype=torch.uint8, device=packed_u8.device)
+        sizes = np.tile(np.array(sizes, np.int64).reshape(B, 2), (Fn, 1))
+        nbytes = sizes[:, 0] * sizes[:, 1] * 3
         img = torch.empty((n, h, w, 3), dtype=torch.uint8, device=packed_u8.device)
-        self._ragged_pass(packed_u8, mid, dx, w, 1, xdev)
-        self._ragged_pass(mid, img, dy, h, 0, ydev)
+        self.ragged_resize(packed_u8, np.cumsum(nbytes) - nbytes, sizes, img.view(-1), np.arange(n) * (h * w * 3), h, w,
+                           np.tile(np.asarray(flips, bool), Fn) if flips is not None else None)
         return self._levels(img, Fn, B, jitters)
 
     def _levels(self, img, Fn, B, jitters):
@@ -278,40 +276,43 @@ class GpuPreprocessor:
         L = _lib.lib()
         n = Fn * B
         steps = params = sums = None
-        if jitters is not None and any(j is not None for j in jitters):
-            st_h = np.full((n, 4), NO_OP, np.int32)
-            pr_h = np.zeros((n, 4), np.float32)
-            for b, j in enumerate(jitters):
-                if j is None:
-                    continue
-                order, factors = j
-                for k, op in enumerate(order):
-                    st_h[b::B, k] = op
-                    pr_h[b::B, k] = float(hue_shift(factors[op])) if op == HUE else factors[op]
-            steps = torch.from_numpy(st_h).to(img.device)
-            params = torch.from_numpy(pr_h).to(img.device)
+        tables = jitter_tables(jitters, Fn, B)
+        aug = tables is not None
+        if aug:
+            steps, params = (torch.from_numpy(t).to(img.device) for t in tables)
             sums = torch.empty(n, dtype=torch.int64, device=img.device)
-        out = {}
+        color, color_aug = [], []
         for s in range(self.num_scales):
             h, w = self.height // (2 ** s), self.width // (2 ** s)
             if s:
                 img = self._resize(img, h, w, None)
-            color = torch.empty((n, 3, h, w), dtype=torch.float32, device=img.device)
-            aug = torch.empty_like(color) if steps is not None else None
-            check(L.dc_data_jitter_to_tensor(img.data_ptr(), color.data_ptr(), aug.data_ptr() if aug is not None else None, n, h * w,
-                                             steps.data_ptr() if aug is not None else None, params.data_ptr() if aug is not None else None,
-                                             sums.data_ptr() if aug is not None else None, stream(img)), "dc_data_jitter_to_tensor")
-            color = color.view(Fn, B, 3, h, w)
-            color_aug = aug.view(Fn, B, 3, h, w) if aug is not None else color
-            for i, f in enumerate(self.frame_idxs):
-                out[("color", f, s)] = color[i]
-                out[("color_aug", f, s)] = color_aug[i]
+            color.append(torch.empty((n, 3, h, w), dtype=torch.float32, device=img.device))
+            if aug:
+                color_aug.append(torch.empty_like(color[s]))
+            check(L.dc_data_jitter_to_tensor(img.data_ptr(), color[s].data_ptr(), color_aug[s].data_ptr() if aug else None, n, h * w,
+                                             steps.data_ptr() if aug else None, params.data_ptr() if aug else None,
+                                             sums.data_ptr() if aug else None, stream(img)), "dc_data_jitter_to_tensor")
             if s == 0:
+                # the photometric kernels gather from pixel-interleaved RGBx: written here, once per item, from the same uint8
+                # level (same division by 255 -> the same values as ("color", f, 0)) instead of repacked in every training step
                 packed = torch.empty((n, h, w, 4), dtype=torch.float32, device=img.device)
                 check(L.dc_data_to_rgbx(img.data_ptr(), packed.data_ptr(), n, h * w, stream(img)), "dc_data_to_rgbx")
-                packed = packed.view(Fn, B, h, w, 4)
+        return self._inputs(color, color_aug if aug else None, packed, B)
+
+    def _inputs(self, color, color_aug, packed, B):
+        """The dict of `__call__` from frame-major tensors: color[s] (Fn * B, 3, h, w) per level, color_aug the same or None
+        (no item is jittered: "color_aug" is "color"), packed (Fn * B, height, width, 4) for level 0."""
+        Fn, out = len(self.frame_idxs), {}
+        for s, c in enumerate(color):
+            c = c.view((Fn, B) + c.shape[1:])
+            a = color_aug[s].view_as(c) if color_aug is not None else c
+            for i, f in enumerate(self.frame_idxs):
+                out[("color", f, s)] = c[i]
+                out[("color_aug", f, s)] = a[i]
+            if s == 0:
+                pk = packed.view((Fn, B) + packed.shape[1:])
                 for i, f in enumerate(self.frame_idxs):
-                    out[("color_packed", f, 0)] = packed[i]
+                    out[("color_packed", f, 0)] = pk[i]
         return out
 
     def cached(self, arena, slots, flips=None, jitters=None):
@@ -337,15 +338,7 @@ class GpuPreprocessor:
         if flips is not None:
             desc["flip"] = np.tile(np.asarray(flips, bool), Fn)
         if aug:
-            st_h, pr_h = host[n * 16:n * 32].view(np.int32).reshape(n, 4), host[n * 32:].view(np.float32).reshape(n, 4)
-            st_h[...] = NO_OP
-            for b, j in enumerate(jitters):
-                if j is None:
-                    continue
-                order, factors = j
-                for k, op in enumerate(order):
-                    st_h[b::B, k] = op
-                    pr_h[b::B, k] = float(hue_shift(factors[op])) if op == HUE else factors[op]
+            jitter_tables(jitters, Fn, B, out=(host[n * 16:n * 32].view(np.int32).reshape(n, 4), host[n * 32:].view(np.float32).reshape(n, 4)))
         host_dev = torch.from_numpy(host).to(dev)
         base = host_dev.data_ptr()
         sums = torch.empty(n * S, dtype=torch.int64, device=dev) if aug else None
@@ -358,18 +351,7 @@ class GpuPreprocessor:
             ptrs(*[c.data_ptr() for c in color]), ptrs(*[c.data_ptr() for c in color_aug]) if aug else None, packed.data_ptr(),
             base + n * 16 if aug else None, base + n * 32 if aug else None, sums.data_ptr() if aug else None, stream(arena)),
             "dc_data_cached_levels")
-        out = {}
-        for s in range(S):
-            c = color[s].view(Fn, B, 3, self.height >> s, self.width >> s)
-            a = color_aug[s].view(Fn, B, 3, self.height >> s, self.width >> s) if aug else c
-            for i, f in enumerate(self.frame_idxs):
-                out[("color", f, s)] = c[i]
-                out[("color_aug", f, s)] = a[i]
-            if s == 0:
-                pk = packed.view(Fn, B, self.height, self.width, 4)
-                for i, f in enumerate(self.frame_idxs):
-                    out[("color_packed", f, 0)] = pk[i]
-        return out
+        return self._inputs(color, color_aug, packed, B)
 
     # ---- sequence items: n + 2 consecutive frames read as three windows of n (datasets/kitti_dataset_seq.py) ---------------
     seq_lds_budget = 0      # dc_data_seq_plan's LDS budget in bytes; 0 = the library's default.  Moves the on-chip tail's start.
@@ -415,14 +397,10 @@ class GpuPreprocessor:
         if aug:
             if len(jitters) != 3 or any(len(win) != n or any(len(lv) != S for lv in win) for win in jitters):
                 raise _lib.DepthcoreError("jitters[w][j][s]: 3 windows of %d frames of %d levels" % (n, S))
-            host = np.zeros(n_img * S * 8, np.int32)          # [steps (3n, S, 4) int32 | params (3n, S, 4) float32]: one copy
-            st_h, pr_h = host[:n_img * S * 4].reshape(n_img, S, 4), host[n_img * S * 4:].view(np.float32).reshape(n_img, S, 4)
-            for w, win in enumerate(jitters):
-                for j, levels in enumerate(win):
-                    for s, (order, factors) in enumerate(levels):
-                        for k, op in enumerate(order):
-                            st_h[w * n + j, s, k] = op
-                            pr_h[w * n + j, s, k] = float(hue_shift(factors[op])) if op == HUE else factors[op]
+            # [steps (3n, S, 4) int32 | params (3n, S, 4) float32]: one copy; image w * n + j, level s holds jitters[w][j][s]
+            host = np.empty(n_img * S * 8, np.int32)
+            host[:n_img * S * 4].reshape(-1, 4)[...], host[n_img * S * 4:].view(np.float32).reshape(-1, 4)[...] = jitter_rows(
+                [draw for win in jitters for levels in win for draw in levels])
             host_dev = torch.from_numpy(host).to(dev)
             steps, params = host_dev.data_ptr(), host_dev.data_ptr() + n_img * S * 16
         level0 = self._resize(native, H, W, None)

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .data import RAGGED_IMG, resample_table, slot_layout
+from .data import resample_table, slot_layout
 
 
 def tables_symmetric(bounds, kk, in_size):
@@ -114,28 +114,15 @@ class FrameCache:
 
     def build(self, pre, packed_u8, frames):
         """Fill slots from decoded native frames with the existing kernels, flip 0.  packed_u8: 1-D uint8 device tensor;
-        frames: [(byte offset in packed_u8, Hn, Wn, slot)].  Scale 0 goes straight into the slot with the two
-        dc_data_ragged_resize_axis passes (width, then height); each further level takes two more, level s-1 in the arena ->
-        a mid buffer -> level s in the arena: source and destination are never the same buffer within one launch."""
+        frames: [(byte offset in packed_u8, Hn, Wn, slot)].  Scale 0 goes straight into the slot with the two passes of
+        `pre.ragged_resize` (width, then height); each further level takes two more, level s-1 in the arena -> a mid
+        buffer -> level s in the arena: source and destination are never the same buffer within one launch."""
         if not frames:
             return
-        arena, n = self.arena, len(frames)
-        base = [slot * self.slot_bytes for _, _, _, slot in frames]
+        arena = self.arena
+        base = np.array([slot for _, _, _, slot in frames], np.int64) * self.slot_bytes
+        src, src_off, sizes = packed_u8, [off for off, _, _, _ in frames], [(hn, wn) for _, hn, wn, _ in frames]
         for s in range(self.num_scales):
             h, w = self.height >> s, self.width >> s
-            if s == 0:
-                src, sizes, src_off = packed_u8, [(hn, wn) for _, hn, wn, _ in frames], [off for off, _, _, _ in frames]
-            else:
-                src, sizes = arena, [(self.height >> (s - 1), self.width >> (s - 1))] * n
-                src_off = [b + self.level_offsets[s - 1] for b in base]
-            xtab, xdev = pre._ragged_tables(1, [wn for _, wn in sizes], w)
-            ytab, ydev = pre._ragged_tables(0, [hn for hn, _ in sizes], h)
-            dx, dy = np.zeros(n, RAGGED_IMG), np.zeros(n, RAGGED_IMG)
-            mid_off = 0
-            for i, (hn, wn) in enumerate(sizes):
-                dx[i] = (src_off[i], mid_off, hn, wn, xtab[i], 0)
-                dy[i] = (mid_off, base[i] + self.level_offsets[s], hn, w, ytab[i], 0)
-                mid_off += int(hn) * w * 3
-            mid = torch.empty(mid_off, dtype=torch.uint8, device=arena.device)
-            pre._ragged_pass(src, mid, dx, w, 1, xdev)
-            pre._ragged_pass(mid, arena, dy, h, 0, ydev)
+            pre.ragged_resize(src, src_off, sizes, arena, base + self.level_offsets[s], h, w)
+            src, src_off, sizes = arena, base + self.level_offsets[s], [(h, w)] * len(frames)

@@ -9,6 +9,10 @@ nothing forks after the GPU has been initialised.
 Two halves:
   * host -- `plan` (which items, which random draws) and `decode_batch` (files -> one packed uint8 buffer): no GPU needed;
   * device -- upload + data step on a side stream of the loader's own, handed to the consumer's stream with an event.
+    `_StagedLoader._device_half` is that half for every kind of job, and the one place that states its order: the copy
+    and the event that frees the staging buffer, the data step, the intrinsics, "depth_gt", the extras, the batch's
+    event.  A loader's `_upload` only says what its data step is (`ragged`; slots + `FrameCache.build` + `cached`;
+    `sequence`); `_wait` joins a job's pool tasks, `_device_state` makes the preprocessor and the stream on first use.
 Every GPU call is made by the consuming thread (the pool threads only decode), so a training step that is being captured
 into a hipGraph never meets a launch or an allocation of another thread.
 
@@ -25,6 +29,9 @@ descriptors, and `ops.lidar_depth_maps_staged` runs on the loader's stream -- wi
 
 `SequenceLoader` is the same machine for the ConvGRU front-end's items (datasets/kitti_dataset_seq.py): one item of n + 2
 consecutive frames per step, already stacked over its n positions (GpuPreprocessor.sequence), its n scans behind the frames.
+
+`decode_packed` is the evaluation scripts' host half: the files of a split decoded on the calling thread and packed the way
+`GpuPreprocessor.ragged` reads them (evaluate_depth.py, evaluate_depth_gru.py, evaluate_depth_fusion_v3.py).
 """
 import collections
 import os
@@ -78,6 +85,18 @@ def _decode_into(path, dst):
             dst[...] = _pixels(rgb)
 
 
+def decode_packed(paths):
+    """The image files of an evaluation split decoded to RGB on the calling thread and packed back to back, in the order
+    given -> (packed 1-D uint8, sizes [(Hn, Wn)]): what `GpuPreprocessor.ragged` takes once it is on the device."""
+    imgs = []
+    for path in paths:
+        if not os.path.exists(path):
+            raise FileNotFoundError("image %s of the split does not exist" % path)
+        with open(path, "rb") as f:
+            imgs.append(np.asarray(Image.open(f).convert("RGB")))
+    return np.concatenate([im.reshape(-1) for im in imgs]), [im.shape[:2] for im in imgs]
+
+
 def _read_into(path, dst):
     """The bytes of a file (a velodyne scan) into a uint8 view of the staging buffer."""
     with open(path, "rb") as f:
@@ -93,9 +112,10 @@ def _image_size(path):
 
 class _StagedLoader:
     """What BatchLoader and SequenceLoader share: the decode pool, the two pinned staging buffers, the velodyne scans that
-    travel behind the frames, and the epoch iteration with its prefetch.  A subclass gives `dataset`, `__len__`, `plan`
-    (-> [arguments of `_submit`]), `_submit(*plan entry, alloc=)` (-> job dict with "futures") and `_upload(job, slot)`
-    (-> (batch dict, event)); `cache` is None unless the subclass has a frame cache and a `_submit_cached`."""
+    travel behind the frames, the device half of a job (`_wait`, `_device_state`, `_device_half`) and the epoch iteration
+    with its prefetch.  A subclass gives `dataset`, `__len__`, `plan` (-> [arguments of `_submit`]),
+    `_submit(*plan entry, alloc=)` (-> job dict with "buf", "futures", "scans") and `_upload(job, slot)` (-> (batch dict,
+    event), through `_device_half`); `cache` is None unless the subclass has a frame cache and a `_submit_cached`."""
     cache = None
 
     def _init_staging(self, num_workers, device, seed, shuffle, prefetch):
@@ -162,6 +182,46 @@ class _StagedLoader:
     def _pending(job):
         """The pool tasks of a submitted job."""
         return job["futures"] + ([job["meta"]] if job.get("meta") is not None else [])
+
+    @staticmethod
+    def _wait(job):
+        """Wait for the pool tasks of a job -> its extras: the results of the `meta` task (if any) stacked over the items."""
+        for fut in job["futures"]:
+            fut.result()
+        metas = job["meta"].result() if job.get("meta") is not None else []
+        return {k: np.stack([m[k] for m in metas]) for k in (metas[0] if metas else {})}
+
+    def _device_state(self, batch):
+        """The preprocessor, the intrinsics repeated over `batch` and the loader's own stream, made on first use."""
+        if self._pre is None:
+            ds = self.dataset
+            self._pre = GpuPreprocessor(ds.height, ds.width, ds.num_scales, ds.frame_idxs, self.device)
+            self._intrinsics = self._pre.intrinsics(ds.K, batch)
+            self._side = torch.cuda.Stream(self.device)
+
+    def _device_half(self, job, slot, extras, data_step, copy=True):
+        """The device half of a job whose pool tasks are done, all of it in order on the loader's stream -> (batch dict,
+        event that completes it).  copy: the job's bytes go up from staging buffer `slot` in one copy, and the event that
+        frees the buffer (`_stage`) is recorded right behind it; `data_step(device bytes, or None without a copy)` -> the
+        batch; then the intrinsics, "depth_gt" from the job's scans, the extras, and -- last -- the batch's event.  That
+        order is what keeps a batch valid while it is held and a cache slot written before any batch reads it."""
+        with torch.cuda.stream(self._side):
+            dev = None
+            if copy:
+                nbytes = job["buf"].size
+                dev = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+                dev.copy_(self._staging[slot][:nbytes], non_blocking=True)
+                self._copied[slot] = torch.cuda.Event()
+                self._copied[slot].record(self._side)
+            batch = data_step(dev)
+            batch.update(self._intrinsics)
+            if job["scans"]:
+                batch["depth_gt"] = self._lidar_depth(job["scans"], dev)
+            for k, v in extras.items():
+                batch[k] = torch.from_numpy(np.ascontiguousarray(v)).to(self.device)
+            ready = torch.cuda.Event()
+            ready.record(self._side)
+        return batch, ready
 
     def __iter__(self):
         """One epoch (`set_epoch`) of batches: dicts of device tensors only, the same keys and shapes every step."""
@@ -254,21 +314,28 @@ class BatchLoader(_StagedLoader):
         ds = self.dataset
         paths = [ds.frame_paths(i) for i in indices]
         sizes = [_image_size(p[0]) for p in paths]
-        per_frame = sum(h * w * 3 for h, w in sizes)
+        files = [(paths[b][f], h, w) for f in range(len(ds.frame_idxs)) for b, (h, w) in enumerate(sizes)]
+        return dict(self._job(indices, draws, files, alloc, device_depth), sizes=sizes)
+
+    def _job(self, indices, draws, files, alloc, device_depth=True):
+        """What `_submit` and `_submit_cached` share: files = [(path, Hn, Wn)] are decoded back to back into
+        `alloc(total bytes)` (never called when there is nothing to stage), one pool task each, the scans behind them, and
+        one more task collects the items' metadata.  -> job dict."""
+        ds = self.dataset
         flips = [bool(d[0]) for d in draws]
-        scans = self._scans(indices, flips, per_frame * len(ds.frame_idxs)) if device_depth else None
-        buf = alloc(scans["total"] if scans else per_frame * len(ds.frame_idxs))
+        frame_bytes = sum(h * w * 3 for _, h, w in files)
+        scans = self._scans(indices, flips, frame_bytes) if device_depth else None
+        total = scans["total"] if scans else frame_bytes
+        buf = alloc(total)[:total] if total else None
         futures, off = [], 0
-        for f in range(len(ds.frame_idxs)):
-            for b, (h, w) in enumerate(sizes):
-                dst = buf[off:off + h * w * 3].reshape(h, w, 3)
-                futures.append(self._pool_().submit(_decode_into, paths[b][f], dst))
-                off += h * w * 3
+        for path, h, w in files:
+            futures.append(self._pool_().submit(_decode_into, path, buf[off:off + h * w * 3].reshape(h, w, 3)))
+            off += h * w * 3
         if scans:
             futures += self._read_scans(scans, buf)
         meta = self._pool_().submit(lambda: [ds.metadata(i, fl, device_depth=scans is not None) for i, fl in zip(indices, flips)])
-        return {"buf": buf[:scans["total"] if scans else off], "frame_bytes": off, "sizes": sizes, "flips": flips,
-                "jitters": [d[1] for d in draws], "futures": futures, "meta": meta, "scans": scans}
+        return {"buf": buf, "frame_bytes": frame_bytes, "flips": flips, "jitters": [d[1] for d in draws], "futures": futures,
+                "meta": meta, "scans": scans}
 
     def _submit_cached(self, indices, draws, alloc):
         """`_submit` with the frame cache on: only the frames the cache lacks are decoded, each file once however often the
@@ -294,28 +361,11 @@ class BatchLoader(_StagedLoader):
         cache.stats["hits"] += hits
         cache.stats["misses"] += sum(len(item) for item in paths) - hits
         cache.stats["decoded"] += len(need)
-        flips = [bool(d[0]) for d in draws]
-        scans = self._scans(indices, flips, sum(h * w * 3 for h, w in need.values()))
-        total = scans["total"] if scans else sum(h * w * 3 for h, w in need.values())
-        buf = alloc(total)[:total] if need or scans else None
-        futures, frames, off = [], [], 0
+        frames, off = [], 0
         for path, (h, w) in need.items():
-            futures.append(self._pool_().submit(_decode_into, path, buf[off:off + h * w * 3].reshape(h, w, 3)))
             frames.append((path, off, h, w))
             off += h * w * 3
-        if scans:
-            futures += self._read_scans(scans, buf)
-        meta = self._pool_().submit(lambda: [ds.metadata(i, fl, device_depth=scans is not None) for i, fl in zip(indices, flips)])
-        return {"paths": paths, "frames": frames, "buf": buf, "flips": flips, "jitters": [d[1] for d in draws], "futures": futures,
-                "meta": meta, "scans": scans}
-
-    @staticmethod
-    def _finish(job):
-        for fut in job["futures"]:
-            fut.result()
-        metas = job["meta"].result()
-        extras = {k: np.stack([m[k] for m in metas]) for k in (metas[0] if metas else {})}
-        return job["buf"], job["sizes"], job["flips"], job["jitters"], extras
+        return dict(self._job(indices, draws, [(path, h, w) for path, _, h, w in frames], alloc), paths=paths, frames=frames)
 
     def decode_batch(self, indices, draws=None, out=None):
         """Host half of one batch: -> (packed uint8 buffer, sizes [(Hn, Wn)] per item, flips, jitters, extras).  The buffer
@@ -330,33 +380,18 @@ class BatchLoader(_StagedLoader):
             if out.size < nbytes:
                 raise ValueError("decode_batch: %d bytes do not fit the given buffer of %d" % (nbytes, out.size))
             return out
-        return self._finish(self._submit(indices, draws, alloc, device_depth=False))
+        job = self._submit(indices, draws, alloc, device_depth=False)
+        extras = self._wait(job)
+        return job["buf"], job["sizes"], job["flips"], job["jitters"], extras
 
     # ---------------------------------------------------------------------------------------------------------- device half
     def _upload(self, job, slot):
-        """One host-to-device copy + the data step, on the loader's stream -> (batch dict, event that completes it)."""
-        ds = self.dataset
-        if self._pre is None:
-            self._pre = GpuPreprocessor(ds.height, ds.width, ds.num_scales, [f for f in ds.frame_idxs], self.device)
-            self._intrinsics = self._pre.intrinsics(ds.K, self.batch_size)
-            self._side = torch.cuda.Stream(self.device)
+        """One host-to-device copy + the data step (`_device_half`) -> (batch dict, event that completes it)."""
+        self._device_state(self.batch_size)
         if "paths" in job:
             return self._upload_cached(job, slot)
-        buf, sizes, flips, jitters, extras = self._finish(job)
-        with torch.cuda.stream(self._side):
-            dev = torch.empty(buf.size, dtype=torch.uint8, device=self.device)
-            dev.copy_(self._staging[slot][:buf.size], non_blocking=True)
-            self._copied[slot] = torch.cuda.Event()
-            self._copied[slot].record(self._side)
-            batch = self._pre.ragged(dev[:job["frame_bytes"]], sizes, flips, jitters)
-            batch.update(self._intrinsics)
-            if job["scans"]:
-                batch["depth_gt"] = self._lidar_depth(job["scans"], dev)
-            for k, v in extras.items():
-                batch[k] = torch.from_numpy(np.ascontiguousarray(v)).to(self.device)
-            ready = torch.cuda.Event()
-            ready.record(self._side)
-        return batch, ready
+        return self._device_half(job, slot, self._wait(job), lambda dev: self._pre.ragged(
+            dev[:job["frame_bytes"]], job["sizes"], job["flips"], job["jitters"]))
 
     def _upload_cached(self, job, slot):
         """`_upload` of a `_submit_cached` job: the decoded frames go up in one copy and into slots -- cache slots while
@@ -365,11 +400,7 @@ class BatchLoader(_StagedLoader):
         (GpuPreprocessor.cached).  Slots are given out here, on the consuming thread, in batch order; everything runs in
         order on the loader's stream, so a slot is written before any batch reads it and the overflow slots are free again
         when the next batch builds."""
-        for fut in job["futures"]:
-            fut.result()
-        metas = job["meta"].result()
-        extras = {k: np.stack([m[k] for m in metas]) for k in (metas[0] if metas else {})}
-        cache, buf = self.cache, job["buf"]
+        extras, cache = self._wait(job), self.cache
         where, build, spilled = {}, [], 0
         for path, off, h, w in job["frames"]:
             where[path] = cache.lookup(path)
@@ -387,23 +418,11 @@ class BatchLoader(_StagedLoader):
                 slots.append(s if s is not None else cache.lookup(item[f]))
         if any(s is None for s in slots):
             raise RuntimeError("a frame of this batch has left the cache since the batch was planned (FrameCache.clear during an epoch)")
-        with torch.cuda.stream(self._side):
-            if build or job["scans"]:
-                dev = torch.empty(buf.size, dtype=torch.uint8, device=self.device)
-                dev.copy_(self._staging[slot][:buf.size], non_blocking=True)
-                self._copied[slot] = torch.cuda.Event()
-                self._copied[slot].record(self._side)
-                cache.build(self._pre, dev, build)
-            batch = self._pre.cached(cache.arena, slots, job["flips"], job["jitters"])
-            batch.update(self._intrinsics)
-            if job["scans"]:
-                batch["depth_gt"] = self._lidar_depth(job["scans"], dev)
-            for k, v in extras.items():
-                batch[k] = torch.from_numpy(np.ascontiguousarray(v)).to(self.device)
-            ready = torch.cuda.Event()
-            ready.record(self._side)
-        return batch, ready
 
+        def data_step(dev):
+            cache.build(self._pre, dev, build)
+            return self._pre.cached(cache.arena, slots, job["flips"], job["jitters"])
+        return self._device_half(job, slot, extras, data_step, copy=bool(build or job["scans"]))
 
 
 class SequenceLoader(_StagedLoader):
@@ -454,29 +473,11 @@ class SequenceLoader(_StagedLoader):
     def decode_item(self, index, draw=(False, None)):
         """Host half of one item -> (frames (n + 2, Hn, Wn, 3) uint8, flip, jitters); the scans are left to the device half."""
         job = self._submit(index, draw, lambda nbytes: np.empty(nbytes, np.uint8), device_depth=False)
-        for fut in job["futures"]:
-            fut.result()
+        self._wait(job)
         return job["buf"].reshape(job["shape"]), job["flip"], job["jitters"]
 
     def _upload(self, job, slot):
-        """One host-to-device copy + the data step, on the loader's stream -> (batch dict, event that completes it)."""
-        ds = self.dataset
-        if self._pre is None:
-            self._pre = GpuPreprocessor(ds.height, ds.width, ds.num_scales, ds.frame_idxs, self.device)
-            self._intrinsics = self._pre.intrinsics(ds.K, ds.n)
-            self._side = torch.cuda.Stream(self.device)
-        for fut in job["futures"]:
-            fut.result()
-        buf = job["buf"]
-        with torch.cuda.stream(self._side):
-            dev = torch.empty(buf.size, dtype=torch.uint8, device=self.device)
-            dev.copy_(self._staging[slot][:buf.size], non_blocking=True)
-            self._copied[slot] = torch.cuda.Event()
-            self._copied[slot].record(self._side)
-            batch = self._pre.sequence(dev[:job["frame_bytes"]].view(job["shape"]), job["flip"], job["jitters"])
-            batch.update(self._intrinsics)
-            if job["scans"]:
-                batch["depth_gt"] = self._lidar_depth(job["scans"], dev)
-            ready = torch.cuda.Event()
-            ready.record(self._side)
-        return batch, ready
+        """One host-to-device copy + the data step (`_device_half`) -> (batch dict, event that completes it)."""
+        self._device_state(self.dataset.n)
+        return self._device_half(job, slot, self._wait(job), lambda dev: self._pre.sequence(
+            dev[:job["frame_bytes"]].view(job["shape"]), job["flip"], job["jitters"]))

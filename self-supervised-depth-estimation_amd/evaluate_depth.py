@@ -31,6 +31,7 @@ import networks  # noqa: E402
 from depthcore import evaluate as E  # noqa: E402
 from depthcore import ops  # noqa: E402
 from depthcore.data import GpuPreprocessor  # noqa: E402
+from depthcore.loader import decode_packed  # noqa: E402
 from options import MonodepthOptions  # noqa: E402
 
 STEREO_SCALE_FACTOR = ops.STEREO_SCALE_FACTOR
@@ -63,10 +64,8 @@ def image_batches(paths, height, width, batch_size, device):
         return prep(native)[("color", 0, 0)]
 
     for p in paths:
-        if not os.path.exists(p):
-            raise FileNotFoundError("image %s of the split does not exist" % p)
-        with open(p, "rb") as f:
-            img = np.asarray(Image.open(f).convert("RGB"))
+        flat, [(h, w)] = decode_packed([p])
+        img = flat.reshape(h, w, 3)
         if pending and (img.shape != pending[0].shape or len(pending) == batch_size):
             yield flush()
         pending.append(img)

@@ -19,9 +19,7 @@ Where it differs from the reference, beyond evaluate_depth.py's own 
 import os
 import sys
 
-import numpy as np
 import torch
-from PIL import Image
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
@@ -30,6 +28,7 @@ import networks  # noqa: E402
 from depthcore import evaluate as E  # noqa: E402
 from depthcore import ops  # noqa: E402
 from depthcore.data import GpuPreprocessor  # noqa: E402
+from depthcore.loader import decode_packed  # noqa: E402
 from options import MonodepthOptions  # noqa: E402
 
 FRAMES = (-2, -1, 0)                  # evaluate_depth_fusion_v3.py:98, :142
@@ -48,18 +47,9 @@ def triplet_batches(lines, data_path, img_ext, height, width, batch_size, device
     GpuPreprocessor.ragged (an item's three frames share its native size; the items of a batch need not)."""
     prep = GpuPreprocessor(height, width, num_scales=1, frame_idxs=FRAMES, device=device)
     for i0 in range(0, len(lines), batch_size):
-        items = []
-        for line in lines[i0:i0 + batch_size]:
-            paths = triplet_paths(data_path, line, img_ext)
-            if not os.path.exists(paths[2]):
-                raise FileNotFoundError("image %s of the split does not exist" % paths[2])
-            imgs = []
-            for p in paths:
-                with open(p, "rb") as f:
-                    imgs.append(np.asarray(Image.open(f).convert("RGB")))
-            items.append(imgs)
-        packed = torch.from_numpy(np.concatenate([item[j].reshape(-1) for j in range(3) for item in items])).to(device)
-        out = prep.ragged(packed, [item[0].shape[:2] for item in items])
+        items = [triplet_paths(data_path, line, img_ext) for line in lines[i0:i0 + batch_size]]
+        packed, sizes = decode_packed([item[j] for j in range(3) for item in items])
+        out = prep.ragged(torch.from_numpy(packed).to(device), sizes[:len(items)])
         stacked = ops.stack_frames([[out[("color", f, 0)] for f in FRAMES]])[0]
         yield stacked.view((3, len(items)) + tuple(stacked.shape[1:]))
 

@@ -28,7 +28,6 @@ import sys
 
 import numpy as np
 import torch
-from PIL import Image
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
@@ -37,6 +36,7 @@ import networks  # noqa: E402
 from depthcore import evaluate as E  # noqa: E402
 from depthcore import ops  # noqa: E402
 from depthcore.data import GpuPreprocessor  # noqa: E402
+from depthcore.loader import decode_packed  # noqa: E402
 from options import MonodepthOptions  # noqa: E402
 
 
@@ -78,14 +78,8 @@ def load_networks(opt, device):
 
 def frame_batch(prep, paths, device):
     """One lockstep step's frames: PIL decode, packed back to back, GpuPreprocessor.ragged (no flip, no jitter) -> (B,3,h,w)."""
-    imgs = []
-    for p in paths:
-        if not os.path.exists(p):
-            raise FileNotFoundError("image %s of the split does not exist" % p)
-        with open(p, "rb") as f:
-            imgs.append(np.asarray(Image.open(f).convert("RGB")))
-    packed = torch.from_numpy(np.concatenate([im.reshape(-1) for im in imgs])).to(device)
-    return prep.ragged(packed, [im.shape[:2] for im in imgs])[("color", 0, 0)]
+    packed, sizes = decode_packed(paths)
+    return prep.ragged(torch.from_numpy(packed).to(device), sizes)[("color", 0, 0)]
 
 
 def predict(opt, device):

@@ -146,3 +146,30 @@ def test_slot_outside_the_arena_is_refused():
     with pytest.raises(_lib.DepthcoreError):
         pre.cached(arena, [0, 1], flips=[True])
     assert pre.cached(arena, [2, 0])[("color", 0, 3)].shape == (2, 3, 4, 8)
+
+
+def test_frame_cache_build_equals_the_uint8_chain_of_call():
+    """FrameCache.build through GpuPreprocessor.ragged_resize: two frames of different native sizes into an overflow slot
+    and slot 0, out of order; level s of each slot equals, byte for byte, the uint8 level that `__call__(..., flips=None)`
+    converts -- `_resize` applied level after level -- and the slot between them is not touched."""
+    from depthcore.data import GpuPreprocessor, slot_layout
+    from depthcore.frame_cache import FrameCache
+    h, w, S = 32, 64, 4
+    sizes = [(47, 155), (45, 150)]
+    offsets, slot_bytes = slot_layout(h, w, S)
+    native = [data_case_image(hn, wn, 900 + k) for k, (hn, wn) in enumerate(sizes)]
+    packed = torch.from_numpy(np.concatenate([img.reshape(-1) for img in native])).to(_dev())
+    cache = FrameCache(h, w, S, 3 * slot_bytes, 1, _dev())
+    assert cache.capacity == 2 and cache.overflow_slot(0) == 2
+    cache.arena.fill_(7)
+    frames = [(0, 47, 155, 2), (47 * 155 * 3, 45, 150, 0)]
+    pre = GpuPreprocessor(h, w, num_scales=S, frame_idxs=(0,), device=_dev())
+    cache.build(pre, packed, frames)
+    arena = cache.arena
+    for (off, hn, wn, slot), img in zip(frames, native):
+        level = torch.from_numpy(img[None]).to(_dev())
+        for s in range(S):
+            level = pre._resize(level, h >> s, w >> s, None)
+            got = arena[slot * slot_bytes + offsets[s]:][:level.numel()]
+            assert torch.equal(got, level.view(-1)), (slot, s)
+    assert bool((arena[slot_bytes:2 * slot_bytes] == 7).all())

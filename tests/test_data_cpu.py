@@ -116,3 +116,30 @@ def test_sample_item_draw_order():
             assert jit is None
     assert sample_item(False) == (False, None)
     assert hue_shift(-0.1) == 231 and hue_shift(0.05) == 12 and hue_shift(0.0) == 0
+
+
+def test_jitter_tables_rows_and_out_views():
+    """Row f * B + b holds item b's draw for every frame f; an unjittered item keeps NO_OP steps and zero params; HUE
+    carries hue_shift (-0.07 -> int(-17.85) & 0xFF = 239); out= fills the caller's views in place."""
+    from depthcore.data import BRIGHTNESS, CONTRAST, HUE, NO_OP, SATURATION, jitter_tables
+    Fn, B = 3, 3
+    jitters = [((HUE, BRIGHTNESS, SATURATION, CONTRAST), (1.17, 0.83, 0.91, -0.07)), None,
+               ((BRIGHTNESS, CONTRAST, SATURATION, HUE), (0.85, 1.2, 1.1, 0.093))]
+    item0 = ([3, 0, 2, 1], [239.0, 1.17, 0.91, 0.83])
+    item2 = ([0, 1, 2, 3], [0.85, 1.2, 1.1, 23.0])             # int(0.093 * 255) = int(23.715) = 23
+    want_steps = np.array([item0[0], [NO_OP] * 4, item2[0]] * Fn, np.int32)
+    want_params = np.array([item0[1], [0.0] * 4, item2[1]] * Fn, np.float32)
+    steps, params = jitter_tables(jitters, Fn, B)
+    assert steps.dtype == np.int32 and params.dtype == np.float32 and steps.shape == params.shape == (Fn * B, 4)
+    assert np.array_equal(steps, want_steps) and np.array_equal(params, want_params)
+    for f in range(Fn):
+        assert steps[f * B + 0].tolist() == item0[0] and steps[f * B + 1].tolist() == [NO_OP] * 4 and steps[f * B + 2].tolist() == item2[0]
+    assert jitter_tables(None, Fn, B) is None and jitter_tables([None] * B, Fn, B) is None
+    # out=: views of one upload buffer, [steps | params], dirty before the call
+    host = np.full(Fn * B * 32, 0xAB, np.uint8)
+    views = (host[:Fn * B * 16].view(np.int32).reshape(-1, 4), host[Fn * B * 16:].view(np.float32).reshape(-1, 4))
+    got = jitter_tables(jitters, Fn, B, out=views)
+    assert got[0] is views[0] and got[1] is views[1]
+    assert np.array_equal(host[:Fn * B * 16].view(np.int32).reshape(-1, 4), want_steps)
+    assert np.array_equal(host[Fn * B * 16:].view(np.float32).reshape(-1, 4), want_params)
+    assert jitter_tables([None] * B, Fn, B, out=views) is None

@@ -143,3 +143,23 @@ def test_descriptors_outside_the_buffer_are_refused_before_any_launch():
         pre.ragged(short, [(47, 155)])
     with pytest.raises(_lib.DepthcoreError):
         pre.ragged(short.view(1, -1), [(47, 155)])
+
+
+@pytest.mark.parametrize("native_size", [(32, 64), (40, 64), (32, 80)])
+def test_call_equals_ragged_where_level_0_skips_a_pass(native_size):
+    """`__call__` makes level 0 with `_resize` carrying the mirror and hands it to the level loop `ragged` uses: every key
+    equals `ragged`'s on the same bytes.  (32, 64) is the target -- no resize pass, the mirror goes through dc_data_flip;
+    (40, 64) -- the height pass only, the mirror through dc_data_flip; (32, 80) -- the width pass only, carrying it."""
+    from depthcore.data import GpuPreprocessor
+    hn, wn = native_size
+    sizes, frame_idxs = [native_size] * 2, (0, -1, 1)
+    flips, jitters = [True, False], [((2, 3, 1, 0), (0.9, 1.1, 1.15, -0.04)), None]
+    _, packed = _batch(sizes, 3, 800)
+    pre = GpuPreprocessor(32, 64, num_scales=4, frame_idxs=frame_idxs, device=_dev())
+    want = pre.ragged(packed, sizes, flips, jitters)
+    got = pre(packed.view(3, 2, hn, wn, 3), flips, jitters)
+    assert len(want) == 2 * 3 * 4 + 3 and sorted(got, key=str) == sorted(want, key=str)
+    for k in want:
+        assert got[k].shape == want[k].shape and got[k].dtype == want[k].dtype and torch.equal(got[k], want[k]), k
+    assert not torch.equal(got[("color", 0, 0)][0], got[("color_aug", 0, 0)][0])        # item 0 is jittered, item 1 is not
+    assert torch.equal(got[("color", 0, 0)][1], got[("color_aug", 0, 0)][1])

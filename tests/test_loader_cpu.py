@@ -118,3 +118,29 @@ def test_decode_batch_carries_stereo_T(tmp_path):
     assert sorted(extras) == ["stereo_T"] and extras["stereo_T"].shape == (2, 4, 4)
     assert extras["stereo_T"][0, 0, 3] == np.float32(0.1) and extras["stereo_T"][1, 0, 3] == np.float32(0.1)
     ld.close()
+
+
+def test_decode_packed_offsets_sizes_and_missing_file(tmp_path):
+    """Two PNGs of different sizes -> their RGB bytes back to back in the order given, the sizes per file; a missing file
+    is named in a FileNotFoundError."""
+    import pytest
+    from PIL import Image
+
+    from depthcore.loader import decode_packed
+    rng = np.random.RandomState(3)
+    imgs = [rng.randint(0, 256, (5, 7, 3)).astype(np.uint8), rng.randint(0, 256, (4, 9, 3)).astype(np.uint8)]
+    paths = []
+    for k, img in enumerate(imgs):
+        paths.append(str(tmp_path / "d" / ("%d.png" % k)))
+        (tmp_path / "d").mkdir(exist_ok=True)
+        Image.fromarray(img).save(paths[-1])
+    packed, sizes = decode_packed([paths[1], paths[0], paths[1]])
+    assert packed.dtype == np.uint8 and packed.ndim == 1 and packed.size == 2 * 4 * 9 * 3 + 5 * 7 * 3
+    assert [tuple(s) for s in sizes] == [(4, 9), (5, 7), (4, 9)]
+    off = 0
+    for (h, w), k in zip(sizes, (1, 0, 1)):
+        assert np.array_equal(packed[off:off + h * w * 3].reshape(h, w, 3), imgs[k])
+        off += h * w * 3
+    missing = str(tmp_path / "d" / "2.png")
+    with pytest.raises(FileNotFoundError, match="image .*2.png of the split does not exist"):
+        decode_packed([paths[0], missing])

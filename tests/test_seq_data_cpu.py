@@ -180,3 +180,29 @@ def test_seq_symbols_are_part_of_the_abi():
     _lib.lib()
     assert "dc_data_seq_levels" in _lib.EXPORTS and "dc_data_seq_plan" in _lib.EXPORTS and not _lib.MISSING
     assert ctypes.sizeof(_lib.SeqPlan) == 32
+
+
+def test_jitter_rows_under_the_sequence_layout():
+    """`GpuPreprocessor.sequence` hands jitters[w][j][s], flattened in that nesting, to the per-draw helper and reads the
+    result as (3n, S, 4) tables, row w * n + j, level s: against a literal restatement, for 3 windows x n = 2 x 2 levels,
+    a negative hue and shuffled orders."""
+    from depthcore.data import HUE, hue_shift, jitter_rows
+    n, S = 2, 2
+    rng = random.Random(11)
+    jitters = [[[(tuple(rng.sample(range(4), 4)), (rng.uniform(0.8, 1.2), rng.uniform(0.8, 1.2), rng.uniform(0.8, 1.2), rng.uniform(-0.1, 0.1)))
+                 for _ in range(S)] for _ in range(n)] for _ in range(3)]
+    jitters[1][0][1] = ((2, 3, 0, 1), (1.1, 0.9, 1.05, -0.07))
+    assert any(order != (0, 1, 2, 3) for win in jitters for lv in win for order, _ in lv)
+    steps, params = jitter_rows([draw for win in jitters for levels in win for draw in levels])
+    assert steps.shape == params.shape == (3 * n * S, 4) and params.dtype == np.float32
+    steps, params = steps.reshape(3 * n, S, 4), params.reshape(3 * n, S, 4)
+    for w in range(3):
+        for j in range(n):
+            for s in range(S):
+                order, factors = jitters[w][j][s]
+                for k in range(4):
+                    assert steps[w * n + j, s, k] == order[k]
+                    want = float(hue_shift(factors[3])) if order[k] == HUE else factors[order[k]]
+                    assert params[w * n + j, s, k] == np.float32(want)
+    assert steps[1 * n + 0, 1].tolist() == [2, 3, 0, 1]
+    assert params[1 * n + 0, 1].tolist() == [np.float32(1.05), 239.0, np.float32(1.1), np.float32(0.9)]
