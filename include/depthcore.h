@@ -252,7 +252,9 @@ int dc_profile_collect(double* fwd_ms, int* fwd_launches, double* bwd_ms, int* b
  *   y = act( conv3x3( pad1( cat( up2?(x0), x1 ) ) ) + bias )
  * x0 (B,C0,H>>up0,W>>up0) nearest-upsampled x2 on the fly when up0=1, x1 (B,C1,H,W) nullable skip,
  * weight (Co,C0+C1,3,3), bias nullable; act: 0 none, 1 ELU, 2 sigmoid, 3 ReLU, 4 tanh; pad_mode: 0 ReflectionPad2d(1),
- * 1 ZeroPad2d(1).  Output (B,Co,H,W).  ws: dc_conv3x3_fwd_workspace bytes. */
+ * 1 ZeroPad2d(1).  Output (B,Co,H,W).  ws: dc_conv3x3_fwd_workspace bytes.  H, W >= 2 under ReflectionPad2d (it mirrors the
+ * second row / column); ZeroPad2d also takes maps of one row or one column (the 1 x 3 ConvGRU level of a 32 x 96 image), on the
+ * direct kernels. */
 size_t dc_conv3x3_fwd_workspace(int C0, int C1, int B, int Co, int H, int W);
 int dc_conv3x3_fwd(const float* x0, int C0, int up0, const float* x1, int C1, const float* weight,
                    const float* bias, float* y, void* ws, int B, int Co, int H, int W, int act, int pad_mode,
@@ -730,6 +732,18 @@ int dc_gru_blend_bwd_acc(const float* gates, const float* h, const float* cnm, c
 int dc_gather_copy(const float* const* src, float* const* dst, const size_t* n, int nseg, void* stream);
 int dc_gru_residual_fwd(const float* f, const float* H, float* out, int n, size_t M, void* stream);
 int dc_gru_residual_bwd(const float* g, float* d_H, int n, size_t M, void* stream);
+/* S sequences in lockstep (depthcore.ops._GruLevel with streams = S): the tensors are time-major (frame j of stream s is row
+ * j * S + s), so the residual pair above takes M = S * C * P, and the learned initial state that the S streams share gets
+ * d_h0[i] = d_H[0][i] + d_H[1][i] + ... + d_H[S-1][i] (d_H: (S, M) = the first S rows of the hidden-state gradients), added in
+ * that order by one thread per element: no atomics, two calls give the same bits.  DC_EINVAL for a NULL pointer, S < 1, M == 0. */
+int dc_gru_state_bwd(const float* d_H, float* d_h0, int S, size_t M, void* stream);
+/* HOST, per calling thread: from now on a Winograd launch of this thread whose batch is a multiple of `streams` is taken as that many
+ * independent streams stacked along the batch, and its tile variant and reduction split are those the launch of ONE stream
+ * (batch / streams) takes -- so an image's sums are ordered as in the single-stream call and a stream's results do not depend on
+ * how many streams share the launch, bit for bit.  The workspace queries made under a setting cover the launches made under it.
+ * Returns the previous value; 1 (the default) plans by the batch itself; DC_EINVAL for streams < 1.  depthcore.ops._GruLevel sets
+ * it around its forward loop and its reverse walk when streams > 1, and restores it. */
+int dc_set_wino_plan_streams(int streams);
 
 /* Inference form of a v5 cell step for B independent streams (evaluate_depth_gru_fusion.py:504-554 `evaluate_v5_seq`, run for
  * several scenes in lockstep: depthcore.evaluate.SequencePredictor), EVERY feature level in one launch.  `lv` is a HOST array
@@ -952,6 +966,22 @@ int dc_data_seq_plan(int n, int H, int W, int S, int jitter, int lds_budget, dc_
 int dc_data_seq_levels(const uint8_t* frames, int n, int H, int W, int S, int flip, float* const* color, float* packed,
                        const int* steps, const float* params, const int* tab_host, const int* tab_dev, size_t tab_len,
                        void* scratch, size_t scratch_bytes, int lds_budget, void* stream);
+/* The same data step for a STEP of `items` sequence items that train in lockstep (1..64), in the launches of one item: the
+ * launch count does not grow with `items`.  Every output is stacked TIME-MAJOR: image t * items + item, with t the frame
+ * 0..n+1 (un-jittered: n_img = items * (n + 2), the windows stay the slices [items : (n+1) items], [0 : n items],
+ * [2 items : (n+2) items] of every output) or the window slot w * n + j (jittered: n_img = 3n * items, image
+ * (w * n + j) * items + item gathers frame j + (1, 0, 2)[w] of that item).
+ *   frames: the unmirrored level 0 item-major as uploaded, (items, n + 2, H, W, 3) uint8;  flips: HOST array, one flag per item;
+ *   steps / params: (items, 3n, S, 4), each item's table as dc_data_seq_levels takes it, item-major; an item of a jittered step
+ *     that has no draw of its own carries DC_JITTER_NONE steps.  Both or neither.
+ * Each item's rows hold the bytes dc_data_seq_levels gives for that item alone; items == 1 IS dc_data_seq_levels.  The plan,
+ * the tables, the scratch and the LDS budget are those of dc_data_seq_levels with n_img and scratch_bytes scaled by `items`;
+ * the same validation (plus items outside 1..64, a NULL flips, more than 65535 images: DC_EINVAL before the first launch), no
+ * allocation, no synchronisation. */
+int dc_data_seq_batch_plan(int items, int n, int H, int W, int S, int jitter, int lds_budget, dc_seq_plan* plan);
+int dc_data_seq_batch_levels(const uint8_t* frames, int items, int n, int H, int W, int S, const int* flips, float* const* color,
+                             float* packed, const int* steps, const float* params, const int* tab_host, const int* tab_dev,
+                             size_t tab_len, void* scratch, size_t scratch_bytes, int lds_budget, void* stream);
 
 /* ------------------------------------------------------------------ depth metrics (validation)
  * Trainer.compute_depth_losses (trainer.py:624-652, called at :248 and from val at :460) and the KITTI Eigen protocol of

@@ -1194,8 +1194,12 @@ static inline bool bf16_path(int C0, int C1, int up0, int H, int W) {
 struct Block { int B, C0, up0, C1, Co, H, W, Cin; };      // up0 is 0 / 1 here, whatever the caller passed
 static inline Block block(int B, int C0, int up0, int C1, int Co, int H, int W) { return {B, C0, up0 ? 1 : 0, C1, Co, H, W, C0 + C1}; }
 // what both launches and the plan query accept, whatever the pointers are
+// (ReflectionPad2d(1) needs two rows and two columns to mirror; under ZeroPad2d a map of one row or one column is a convolution
+// like any other -- the ConvGRU cells of a 32 x 96 image see a 1 x 3 level -- and takes the direct kernels, which bound every
+// access by H and W: the Winograd, bf16 and head predicates all ask for H >= 2 themselves)
 static bool block_ok(const Block& s, int act, int pad) {
-    return s.C0 > 0 && s.C1 >= 0 && s.B > 0 && s.Co > 0 && s.H >= 2 && s.W >= 2 && !(s.up0 && ((s.H | s.W) & 1)) && act >= 0 &&
+    const int least = pad == PAD_ZERO ? 1 : 2;
+    return s.C0 > 0 && s.C1 >= 0 && s.B > 0 && s.Co > 0 && s.H >= least && s.W >= least && !(s.up0 && ((s.H | s.W) & 1)) && act >= 0 &&
            act <= ACT_LAST && pad >= 0 && pad <= 1;
 }
 
@@ -1241,7 +1245,9 @@ static void conv_plan(const Block& s, int act, int pad, unsigned want, dc_conv3x
     const bool head = wino_enabled() && dispconv_eligible(C0, C1, up0, Co, H, W);
     const bool b16_shape = bf16_path(C0, C1, up0, H, W);
     p->fwd = head ? DC_C3_FWD_HEAD : b16_shape ? DC_C3_FWD_BF16 : wino_fwd(C0, C1, B, Co, H, W) ? DC_C3_FWD_WINO : DC_C3_FWD_DIRECT;
-    if (p->fwd == DC_C3_FWD_DIRECT) { p->fwd_v2 = (W % 16 == 0) && (C1 == 0 || C0 % CK == 0); p->fwd_mr = pick_mr(Co); }
+    // (one-row / one-column maps, accepted under zero padding only, stay on the v1 kernels, which bound every access by H and W)
+    const bool rows2 = H >= 2 && W >= 2;
+    if (p->fwd == DC_C3_FWD_DIRECT) { p->fwd_v2 = rows2 && (W % 16 == 0) && (C1 == 0 || C0 % CK == 0); p->fwd_mr = pick_mr(Co); }
     // ---- backward: the head checks again before the bf16 and Winograd ones
     const bool b16 = b16_shape && wino_gp_ok(B, Co, H, W, act);
     // (the bf16 weight-gradient kernel tiles 64 output channels; a quarter- or half-filled tile still beats the fp32 direct
@@ -1255,7 +1261,7 @@ static void conv_plan(const Block& s, int act, int pad, unsigned want, dc_conv3x
     const bool fused_db = dbias && (w_dw || b16_dw) && (H * W) % 4 == 0;
     // fast path (v2 kernels): full 16-wide tiles, 16-byte aligned rows, chunks that do not straddle the concat -- CK channels in the
     // data gradient as in the forward, CW in the weight gradient: one clause more than the forward's
-    const bool fast = (W % 16 == 0) && (C1 == 0 || C0 % CK == 0) && (C1 == 0 || C0 % CW == 0);
+    const bool fast = rows2 && (W % 16 == 0) && (C1 == 0 || C0 % CK == 0) && (C1 == 0 || C0 % CW == 0);
     // the thin single-channel heads have their own plain-FMA gradients (dispconv.hip), which form g' on the fly; the weight
     // gradient's slabs borrow the padded-domain buffer
     const bool head_dx = dx0 && head;

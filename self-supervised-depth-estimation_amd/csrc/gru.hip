@@ -132,6 +132,16 @@ __global__ __launch_bounds__(256) void gru_residual_bwd_kernel(const float* __re
     }
 }
 
+// Gradient of a learned initial state shared by S lockstep streams: d_h0 = sum over the streams' rows of d_H[0:S].  One thread
+// owns an element and adds its S addends in stream order (no atomics): two calls give the same bits.
+__global__ __launch_bounds__(256) void gru_state_bwd_kernel(const float* __restrict__ d_H, float* __restrict__ d_h0, int S, size_t M) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < M; i += (size_t)gridDim.x * 256) {
+        float v = d_H[i];
+        for (int s = 1; s < S; ++s) v += d_H[(size_t)s * M + i];
+        d_h0[i] = v;
+    }
+}
+
 static inline int gru_grid(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 4096); }
 
 }  // namespace dc
@@ -178,6 +188,12 @@ extern "C" int dc_gru_residual_fwd(const float* f, const float* H, float* out, i
 extern "C" int dc_gru_residual_bwd(const float* g, float* d_H, int n, size_t M, void* stream) {
     if (!g || !d_H || n <= 0 || M == 0) return DC_EINVAL;
     hipLaunchKernelGGL(gru_residual_bwd_kernel, dim3(gru_grid((size_t)(n + 1) * M)), dim3(256), 0, (hipStream_t)stream, g, d_H, n, M);
+    DC_CHECK_LAUNCH();
+    return DC_OK;
+}
+extern "C" int dc_gru_state_bwd(const float* d_H, float* d_h0, int S, size_t M, void* stream) {
+    if (!d_H || !d_h0 || S <= 0 || M == 0 || M > (1ull << 40) / (size_t)S) return DC_EINVAL;
+    hipLaunchKernelGGL(gru_state_bwd_kernel, dim3(gru_grid(M)), dim3(256), 0, (hipStream_t)stream, d_H, d_h0, S, M);
     DC_CHECK_LAUNCH();
     return DC_OK;
 }

@@ -5,6 +5,9 @@
 // so the mirror accumulates from level to level and level s + 1 is resized from the JITTERED level s.
 //   * without jitter the three windows are overlapping slices of one (n + 2)-frame pyramid: n + 2 images are made, none twice;
 //   * with jitter every (window, frame, level) has its own draw: 3n images, image i = w * n + j gathers frame j + (1, 0, 2)[w].
+// A STEP may hold several items (dc_data_seq_batch_levels): their images are stacked time-major -- image t * items + item, t the
+// frame or the window slot -- so that one time step of all items is a contiguous slab; the frames arrive item-major, each item
+// has its own mirror flag and jitter rows, and the launches are those of one item (seq_item / seq_src / seq_jrow / seq_flip).
 // Two ways through a level, the same bytes either way (tests/test_seq_data_gpu.py runs every split):
 //   * through HBM, the whole machine on every level: the two dc_data_resize_axis passes, an integer luma-sum pass when
 //     jittered, and one finish pass (mirror, jitter, uint8 + float stores) over all images at once;
@@ -28,6 +31,7 @@ constexpr int kSeqStripRows = 8;           // output rows per strip of the tail'
 constexpr int kSeqKsize = 13;              // dc_resample_ksize(2 m, m): every level halves the one before
 constexpr int kSeqStripSrcRows = 2 * kSeqStripRows + 12;   // source rows one strip may span (2 R + 9 with Pillow's tables)
 constexpr int kSeqLdsCap = 160 * 1024 - 256;               // gfx950: 160 KiB per workgroup, less the static reduction words
+constexpr int kSeqMaxItems = 64;                          // sequence items per step (their flip flags travel as kernel arguments)
 constexpr int kSeqLdsDefault = 12 * 1024;                  // the tail's default budget: below the smallest level of 192 x 640 (see above)
 
 struct SeqTabs {   // device tables of level s (1..S-1): (size >> (s - 1)) -> (size >> s) along each axis
@@ -44,7 +48,10 @@ struct SeqArgs {
     const int* steps;              // (n_img, S, 4) or NULL
     const float* params;
     unsigned long long* sums;      // (n_img, S): the tiled levels' luma sums
-    int n, S, H, W, flip, gather;  // gather: image i reads frame seq_frame(i, n) of `src` (level 0 of a jittered sequence)
+    int n, S, H, W;
+    int items;                     // sequence items of the step: image i is frame / window slot i / items of item i % items (time-major)
+    unsigned flips[kSeqMaxItems / 32];   // one bit per item
+    int gather;                    // the launch reads level 0: image i comes from frame seq_src(a, i) of `src` (item-major, unmirrored)
     int level;                     // finish: the level; tail: its first level
     int b_off;                     // tail: byte offset of the second LDS buffer
     SeqTabs tabs;
@@ -54,15 +61,29 @@ __device__ __forceinline__ int seq_frame(int i, int n) {
     const int w = i / n, j = i - w * n;
     return j + (w == 0 ? 1 : (w == 1 ? 0 : 2));   // windows in the order centre, left, right
 }
+// The image index of a step of `items` sequence items is time-major: im = t * items + item, t = the frame (un-jittered,
+// 0..n+1) or the window slot w * n + j (jittered, 0..3n-1).  These three say what an image reads; items == 1 gives im itself.
+__device__ __forceinline__ int seq_item(const SeqArgs& a, int im) { return im % a.items; }
+__device__ __forceinline__ int seq_flip(const SeqArgs& a, int im) {
+    const int it = seq_item(a, im);
+    return (a.flips[it >> 5] >> (it & 31)) & 1;
+}
+// level-0 source frame: the frames are uploaded item-major, n + 2 per item
+__device__ __forceinline__ int seq_src(const SeqArgs& a, int im) {
+    const int t = im / a.items;
+    return seq_item(a, im) * (a.n + 2) + (a.steps ? seq_frame(t, a.n) : t);
+}
+// row of the jitter tables: item-major, 3n rows per item
+__device__ __forceinline__ int seq_jrow(const SeqArgs& a, int im) { return seq_item(a, im) * 3 * a.n + im / a.items; }
 
 // ---- levels that live in HBM -------------------------------------------------------------------------------------------
 // exact luma sum of every image in front of its contrast step at `level` (the mirror does not change a sum)
 __global__ __launch_bounds__(256) void seq_sum_kernel(const SeqArgs a) {
     const int im = blockIdx.y, s = a.level;
-    const JChain ch = jchain_load(a.steps, a.params, im * a.S + s);
+    const JChain ch = jchain_load(a.steps, a.params, seq_jrow(a, im) * a.S + s);
     if (ch.c < 0) return;
     const int npix = (a.H >> s) * (a.W >> s);
-    const uint8_t* p = a.src + (size_t)(a.gather ? seq_frame(im, a.n) : im) * npix * 3;
+    const uint8_t* p = a.src + (size_t)(a.gather ? seq_src(a, im) : im) * npix * 3;
     unsigned int acc = 0;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < npix; i += gridDim.x * 256) {
         int r = p[3 * i], g = p[3 * i + 1], b = p[3 * i + 2];
@@ -83,15 +104,16 @@ __global__ __launch_bounds__(256) void seq_sum_kernel(const SeqArgs a) {
 __global__ __launch_bounds__(256) void seq_finish_kernel(const SeqArgs a) {
     const int im = blockIdx.y, s = a.level;
     const int w = a.W >> s, npix = (a.H >> s) * w;
-    const JChain ch = jchain_load(a.steps, a.params, im * a.S + s);
+    const JChain ch = jchain_load(a.steps, a.params, seq_jrow(a, im) * a.S + s);
     const int mean = ch.c >= 0 ? luma_mean(a.sums[(size_t)im * a.S + s], npix) : 0;
-    const uint8_t* p = a.src + (size_t)(a.gather ? seq_frame(im, a.n) : im) * npix * 3;
+    const uint8_t* p = a.src + (size_t)(a.gather ? seq_src(a, im) : im) * npix * 3;
     uint8_t* u = a.u8 ? a.u8 + (size_t)im * npix * 3 : nullptr;
     float* o = a.color[s] + (size_t)im * npix * 3;
     float4* pk = (s == 0 && a.packed) ? a.packed + (size_t)im * npix : nullptr;
+    const int flip = seq_flip(a, im);
     for (int i = blockIdx.x * 256 + threadIdx.x; i < npix; i += gridDim.x * 256) {
         int src = i;
-        if (a.flip) {
+        if (flip) {
             const int y = i / w;
             src = 2 * y * w + w - 1 - i;     // (y, w - 1 - x)
         }
@@ -121,11 +143,12 @@ __global__ __launch_bounds__(kSeqThreads) void seq_tail_kernel(const SeqArgs a) 
     uint8_t* Bf = seq_lds + a.b_off;
     const int im = blockIdx.x, tid = threadIdx.x, t = a.level;
     int h = a.H >> t, w = a.W >> t;
+    const int flip = seq_flip(a, im);   // block-uniform
     if (t == 0) {
-        const uint8_t* src = a.src + (size_t)(a.gather ? seq_frame(im, a.n) : im) * h * w * 3;
+        const uint8_t* src = a.src + (size_t)(a.gather ? seq_src(a, im) : im) * h * w * 3;
         for (int i = tid; i < h * w; i += kSeqThreads) {
             int sp = i;
-            if (a.flip) {
+            if (flip) {
                 const int y = i / w;
                 sp = 2 * y * w + w - 1 - i;
             }
@@ -147,7 +170,7 @@ __global__ __launch_bounds__(kSeqThreads) void seq_tail_kernel(const SeqArgs a) 
                 const int yy = q / row, xb = q - yy * row, yo = y0 + yy;
                 const uint8_t v = resample_byte(Bf + (size_t)(by[2 * yo] - r0) * row + xb, row, by[2 * yo + 1], ky + yo * kSeqKsize);
                 const int x = xb / 3, c = xb - 3 * x;
-                A[((size_t)yo * w + (a.flip ? w - 1 - x : x)) * 3 + c] = v;
+                A[((size_t)yo * w + (flip ? w - 1 - x : x)) * 3 + c] = v;
             }
             __syncthreads();
         }
@@ -168,7 +191,7 @@ __global__ __launch_bounds__(kSeqThreads) void seq_tail_kernel(const SeqArgs a) 
                 const int yo = q / row, xb = q - yo * row;
                 const uint8_t v = resample_byte(Bf + (size_t)by[2 * yo] * row + xb, row, by[2 * yo + 1], ky + yo * kSeqKsize);
                 const int x = xb / 3, c = xb - 3 * x;
-                A[((size_t)yo * w + (a.flip ? w - 1 - x : x)) * 3 + c] = v;
+                A[((size_t)yo * w + (flip ? w - 1 - x : x)) * 3 + c] = v;
             }
             __syncthreads();
         }
@@ -176,7 +199,7 @@ __global__ __launch_bounds__(kSeqThreads) void seq_tail_kernel(const SeqArgs a) 
         if (a.steps) {
             // in place, every thread on its own pixels: the steps in front of the contrast, the block's integer luma sum,
             // then the rest -- the same bytes as the whole chain evaluated per pixel (each step ends in 8 bits)
-            const JChain ch = jchain_load(a.steps, a.params, im * a.S + s);
+            const JChain ch = jchain_load(a.steps, a.params, seq_jrow(a, im) * a.S + s);
             int mean = 0, first = 0;
             if (ch.c >= 0) {   // block-uniform
                 unsigned int acc = 0;
@@ -240,11 +263,12 @@ static bool seq_shape_ok(int n, int H, int W, int S) {
 
 using namespace dc;
 
-extern "C" int dc_data_seq_plan(int n, int H, int W, int S, int jitter, int lds_budget, dc_seq_plan* plan) {
-    if (!plan || !seq_shape_ok(n, H, W, S) || lds_budget < 0) return DC_EINVAL;
+extern "C" int dc_data_seq_batch_plan(int items, int n, int H, int W, int S, int jitter, int lds_budget, dc_seq_plan* plan) {
+    if (!plan || items < 1 || items > kSeqMaxItems || !seq_shape_ok(n, H, W, S) || lds_budget < 0) return DC_EINVAL;
+    if ((long long)items * (jitter ? 3 * n : n + 2) > 65535) return DC_EINVAL;   // one grid row per image
     const size_t budget = lds_budget ? std::min((size_t)lds_budget, (size_t)kSeqLdsCap) : (size_t)kSeqLdsDefault;
     dc_seq_plan p = {};
-    p.n_img = jitter ? 3 * n : n + 2;
+    p.n_img = items * (jitter ? 3 * n : n + 2);
     p.tail_start = S;
     for (int t = 0; t < S; ++t) {
         size_t b_off, total;
@@ -266,13 +290,18 @@ extern "C" int dc_data_seq_plan(int n, int H, int W, int S, int jitter, int lds_
     return DC_OK;
 }
 
-extern "C" int dc_data_seq_levels(const uint8_t* frames, int n, int H, int W, int S, int flip, float* const* color, float* packed,
-                                  const int* steps, const float* params, const int* tab_host, const int* tab_dev, size_t tab_len,
-                                  void* scratch, size_t scratch_bytes, int lds_budget, void* stream) {
-    if (!frames || !color || !packed || ((size_t)packed & 15) || !scratch || ((size_t)scratch & 15)) return DC_EINVAL;
-    if ((steps == nullptr) != (params == nullptr)) return DC_EINVAL;   // a sequence is jittered as a whole or not at all
+extern "C" int dc_data_seq_plan(int n, int H, int W, int S, int jitter, int lds_budget, dc_seq_plan* plan) {
+    return dc_data_seq_batch_plan(1, n, H, W, S, jitter, lds_budget, plan);
+}
+
+extern "C" int dc_data_seq_batch_levels(const uint8_t* frames, int items, int n, int H, int W, int S, const int* flips,
+                                        float* const* color, float* packed, const int* steps, const float* params, const int* tab_host,
+                                        const int* tab_dev, size_t tab_len, void* scratch, size_t scratch_bytes, int lds_budget,
+                                        void* stream) {
+    if (!frames || !flips || !color || !packed || ((size_t)packed & 15) || !scratch || ((size_t)scratch & 15)) return DC_EINVAL;
+    if ((steps == nullptr) != (params == nullptr)) return DC_EINVAL;   // a step is jittered as a whole or not at all
     dc_seq_plan plan;
-    if (dc_data_seq_plan(n, H, W, S, steps != nullptr, lds_budget, &plan) != DC_OK) return DC_EINVAL;
+    if (dc_data_seq_batch_plan(items, n, H, W, S, steps != nullptr, lds_budget, &plan) != DC_OK) return DC_EINVAL;
     for (int s = 0; s < S; ++s)
         if (!color[s]) return DC_EINVAL;
     if (S > 1 && (!tab_host || !tab_dev)) return DC_EINVAL;
@@ -280,7 +309,9 @@ extern "C" int dc_data_seq_levels(const uint8_t* frames, int n, int H, int W, in
     if (scratch_bytes < (size_t)plan.scratch_bytes) return DC_EWORKSPACE;
 
     SeqArgs a = {};
-    a.n = n, a.S = S, a.H = H, a.W = W, a.flip = flip != 0;
+    a.n = n, a.S = S, a.H = H, a.W = W, a.items = items;
+    for (int i = 0; i < items; ++i)
+        if (flips[i]) a.flips[i >> 5] |= 1u << (i & 31);
     a.steps = steps, a.params = params;
     a.packed = (float4*)packed;
     for (int s = 0; s < S; ++s) a.color[s] = color[s];
@@ -325,7 +356,7 @@ extern "C" int dc_data_seq_levels(const uint8_t* frames, int n, int H, int W, in
     for (int s = 0; s < t; ++s) {
         const int h = H >> s, w = W >> s;
         a.level = s;
-        a.gather = s == 0 && steps != nullptr;
+        a.gather = s == 0;
         a.u8 = u[s];
         if (s == 0) {
             a.src = frames;
@@ -345,7 +376,7 @@ extern "C" int dc_data_seq_levels(const uint8_t* frames, int n, int H, int W, in
         static const bool attr = set_max_dynamic_lds(seq_tail_kernel, kSeqLdsCap);
         if (!attr) return DC_ELAUNCH;
         a.level = t;
-        a.gather = t == 0 && steps != nullptr;
+        a.gather = t == 0;
         a.u8 = nullptr;
         a.src = t == 0 ? frames : u[t - 1];
         a.b_off = (int)b_off;
@@ -353,4 +384,12 @@ extern "C" int dc_data_seq_levels(const uint8_t* frames, int n, int H, int W, in
     }
     DC_CHECK_LAUNCH();
     return DC_OK;
+}
+
+extern "C" int dc_data_seq_levels(const uint8_t* frames, int n, int H, int W, int S, int flip, float* const* color, float* packed,
+                                  const int* steps, const float* params, const int* tab_host, const int* tab_dev, size_t tab_len,
+                                  void* scratch, size_t scratch_bytes, int lds_budget, void* stream) {
+    const int flips[1] = {flip};
+    return dc_data_seq_batch_levels(frames, 1, n, H, W, S, flips, color, packed, steps, params, tab_host, tab_dev, tab_len, scratch,
+                                    scratch_bytes, lds_budget, stream);
 }

@@ -698,7 +698,16 @@ static int wino_ksplit_cap(size_t nout) {
     static const size_t small = getenv("DC_WINO_KSCAP_BYTES") ? (size_t)atol(getenv("DC_WINO_KSCAP_BYTES")) : (size_t)(2u << 20);      // experiments
     return nout * 4 <= small ? 8 : 2;
 }
-static size_t wino_slab_bytes(size_t nout) { return (size_t)wino_ksplit_cap(nout) * nout * sizeof(float); }
+// dc_set_wino_plan_streams(S): the calling thread's launches whose batch is a multiple of S are S independent streams stacked along
+// the batch (the lockstep ConvGRU recurrence), and their tile variant and reduction split are the ones ONE stream's launch would
+// take (the batch / S), so that a stream's results do not depend on how many streams share the launch: the summation order of an
+// image is that of the single-stream call, bit for bit.  The grid still covers the whole batch.  1 (default): plan by the batch.
+static thread_local int tl_plan_streams = 1;
+static inline int wino_plan_batch(int B) { return tl_plan_streams > 1 && B % tl_plan_streams == 0 ? B / tl_plan_streams : B; }
+// (workspace queries do not know the batch behind `nout`: they take the cap of the smallest batch a stream count allows, an upper bound)
+static size_t wino_slab_bytes(size_t nout) {
+    return (size_t)wino_ksplit_cap(tl_plan_streams > 1 ? nout / tl_plan_streams : nout) * nout * sizeof(float);
+}
 
 static int g_wino_persist = [] { const char* f = getenv("DC_WINO_PERSIST"); return f ? atoi(f) : 0; }();      // dc_set_wino_persist
 
@@ -736,14 +745,15 @@ static WinoPlan wino_plan(int B, int K, int M, int Ho, int Wo) {
     p.nchunks = ceil_div(K, PSK);
     // Tile variant and reduction split: the cheapest of {16x32, 32x32, 32x64} x {1, 2 slabs} under wino_ps_cost
     p.MT = 32; p.G = 2; p.ksplit = 1;
-    const size_t nout = (size_t)B * M * Ho * Wo;
+    const int Bp = wino_plan_batch(B), nsub_p = p.regs_x * p.regs_y * Bp;      // what the cost model sees: one stream's launch
+    const size_t nout = (size_t)Bp * M * Ho * Wo;
     const bool can_split = (Ho * Wo) % 4 == 0 && p.nchunks >= 2;
     const int ks_cap = can_split ? wino_ksplit_cap(nout) : 1;
     double best = 1e30;
     for (int v = 0; v < 3; ++v)
         for (int ks = 1; ks <= ks_cap; ks *= 2) {
             if (ks > 1 && p.nchunks < 2 * ks) break;          // at least two chunks per split: something to pipeline
-            const double t = wino_ps_cost(v, ks, p.nsub, M, p.nchunks, nout);
+            const double t = wino_ps_cost(v, ks, nsub_p, M, p.nchunks, nout);
             if (t < best) { best = t; p.MT = v == 0 ? 16 : 32; p.G = v == 2 ? 2 : 1; p.ksplit = ks; }
         }
     if (getenv("DC_WINO_DEBUG"))       // experiments: the cost model's inputs and pick (tools/sweep_wino.py -> refits of wino_ps_cost)
@@ -965,6 +975,13 @@ extern "C" size_t dc_wino3x3_workspace(int B, int Ci, int Co, int H, int W) {
     if (B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0) return 0;
     return std::max({wino_uhat_bytes(Ci, Co), wino4_uhat_bytes(Ci, Co), c3b_weights_bytes(Ci, Co)}) +
            wino_al256(std::max(wino_slab_bytes((size_t)B * Ci * H * W), wino_slab_bytes((size_t)B * Co * H * W)));
+}
+
+extern "C" int dc_set_wino_plan_streams(int streams) {
+    if (streams < 1) return DC_EINVAL;
+    const int before = tl_plan_streams;
+    tl_plan_streams = streams;
+    return before;
 }
 
 extern "C" int dc_set_wino_persist(int mode) {

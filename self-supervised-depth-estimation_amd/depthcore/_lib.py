@@ -256,6 +256,8 @@ def _sig(lib):
         "dc_gather_copy": (i, [p, p, p, i, p]),
         "dc_gru_residual_fwd": (i, [p, p, p, i, z, p]),
         "dc_gru_residual_bwd": (i, [p, p, i, z, p]),
+        "dc_gru_state_bwd": (i, [p, p, i, z, p]),
+        "dc_set_wino_plan_streams": (i, [i]),
         "dc_gru_infer_rh": (i, [POINTER(GruInferLevel), i, i, p]),
         "dc_gru_infer_tail": (i, [POINTER(GruInferLevel), i, i, p]),
         "dc_gru_infer_init": (i, [p, p, p, i, i, p]),
@@ -307,6 +309,8 @@ def _sig(lib):
         "dc_data_cached_levels": (i, [p, z, p, p, i, i, i, i, p, p, p, p, p, p, p]),
         "dc_data_seq_plan": (i, [i, i, i, i, i, i, POINTER(SeqPlan)]),
         "dc_data_seq_levels": (i, [p, i, i, i, i, i, p, p, p, p, p, p, z, p, z, i, p]),
+        "dc_data_seq_batch_plan": (i, [i, i, i, i, i, i, i, POINTER(SeqPlan)]),
+        "dc_data_seq_batch_levels": (i, [p, i, i, i, i, i, p, p, p, p, p, p, p, z, p, z, i, p]),
         "dc_attnconv_fwd": (i, [POINTER(AttnMap), POINTER(AttnParams), POINTER(AttnMap), p, i, i, i, i, i, i, p]),
         "dc_attnconv_param_count": (i, [i]),
         "dc_attnconv_bwd_workspace": (z, [i, i, i, i]),

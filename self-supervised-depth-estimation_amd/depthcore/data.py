@@ -10,7 +10,9 @@ packed back to back (what a shuffled KITTI loader delivers, depthcore/loader.py)
 the whole batch (`dc_data_ragged_resize_axis`, tests/test_data_ragged_gpu.py); `GpuPreprocessor.cached` takes frames whose
 resized pyramids already sit in cache slots (depthcore/frame_cache.py) and makes the same dict without any resize, in two
 launches (`dc_data_cached_levels`, tests/test_data_cached_gpu.py); `GpuPreprocessor.sequence` takes the n + 2 frames of one
-ConvGRU item (`dc_data_seq_levels`, tests/test_seq_data_gpu.py).
+ConvGRU item (`dc_data_seq_levels`, tests/test_seq_data_gpu.py), and `GpuPreprocessor.sequence_batch` the items of a step that
+trains several sequences in lockstep, stacked time-major by `seq_rows` (`dc_data_seq_batch_levels`,
+tests/test_seq_batch_data_gpu.py).
 
 Each shared piece is written once: `jitter_rows` is the rule that turns ColorJitter draws into the kernels' (steps, params)
 rows and `jitter_tables` lays them out for a frame-major batch (`_levels`, `cached`; `sequence` lays out its own (window,
@@ -18,6 +20,7 @@ frame, level) rows with `jitter_rows`); `_levels` is the one level loop behind s
 in how they make scale 0); `_inputs` is the one builder of the output dict (`_levels`, `cached`); `ragged_resize` is the
 two-pass resize of images of different sizes (`ragged` for scale 0, `FrameCache.build` for every level of a slot).
 """
+import ctypes
 import random
 
 import numpy as np
@@ -78,6 +81,18 @@ def sample_item(is_train=True, rng=random, brightness=(0.8, 1.2), contrast=(0.8,
 
 WINDOW_FIRST = (1, 0, 2)      # first frame of the centre, left and right window of a sequence item, in the reference's order
 WINDOW_FRAMES = (0, -1, 1)    # and the frame id each window is handed out under
+
+
+def seq_rows(j, S, count=1):
+    """THE row rule of lockstep sequence batches: S items of n frames are stacked time-major, frame j of item s is row
+    j * S + s -- so frames j .. j + count - 1 of all S items are the contiguous rows this slice names.  Every stacked tensor
+    (colours, K / inv_K, depth_gt, features, hidden states) follows it; S = 1 is the single sequence."""
+    return slice(j * S, (j + count) * S)
+
+
+def seq_item_rows(s, S, n):
+    """The rows of item s alone, in frame order: the strided slice s, s + S, ..., s + (n - 1) * S of a time-major stack."""
+    return slice(s, s + (n - 1) * S + 1, S)
 
 
 def sample_sequence(is_train, rng, n, num_scales=4, brightness=(0.8, 1.2), contrast=(0.8, 1.2), saturation=(0.8, 1.2), hue=(-0.1, 0.1)):
@@ -420,6 +435,79 @@ class GpuPreprocessor:
             for s in range(S):
                 out[("color", f, s)] = out[("color_aug", f, s)] = color[s][lo:lo + n]
             out[("color_packed", f, 0)] = packed[lo:lo + n]
+        return out
+
+    def sequence_batch_plan(self, items, n, jitter=False):
+        """dc_data_seq_batch_plan: `sequence_plan` for a step of `items` sequence items (n_img and the scratch scale with it)."""
+        plan = _lib.SeqPlan()
+        check(_lib.lib().dc_data_seq_batch_plan(int(items), int(n), self.height, self.width, self.num_scales, 1 if jitter else 0,
+                                                int(self.seq_lds_budget), plan), "dc_data_seq_batch_plan")
+        return plan
+
+    def sequence_batch(self, packed_u8, sizes, n, flips=None, jitters=None):
+        """A step of S = len(sizes) sequence items that train in lockstep.  packed_u8: 1-D uint8 device tensor, the n + 2 native
+        frames of every item back to back, item-major; sizes: S pairs (Hn, Wn) -- an item's frames share its size; flips: one
+        do_flip per item; jitters: one `sample_sequence` draw (or None) per item -- when any item has one the whole step takes
+        the jittered layout and the items without a draw carry no-op steps, which leaves their bytes those of the plain chain.
+        Level 0 comes from `_resize` when the items share a native size and from the ragged passes (`ragged_resize`) when
+        they do not; then ONE dc_data_seq_batch_levels call, the launches of a single item's `sequence`.
+        -> the stacked dict of `sequence` with n * S rows per key, TIME-MAJOR: frame j of item s is row j * S + s
+        (`seq_rows`), and each item's rows hold the bytes `sequence` gives for that item alone.  Un-jittered the three
+        windows are the slices [S:(n+1)S], [0:nS], [2S:(n+2)S] of one (n + 2) * S-row pyramid."""
+        sizes = [(int(h), int(w)) for h, w in sizes]
+        S_it, n = len(sizes), int(n)
+        if packed_u8.dtype != torch.uint8 or packed_u8.dim() != 1 or not packed_u8.is_cuda or not packed_u8.is_contiguous():
+            raise _lib.DepthcoreError("packed frames must be a contiguous 1-D uint8 device tensor")
+        flips = [False] * S_it if flips is None else [bool(f) for f in flips]
+        jitters = [None] * S_it if jitters is None else list(jitters)
+        if S_it < 1 or n < 1 or len(flips) != S_it or len(jitters) != S_it:
+            raise _lib.DepthcoreError("sizes, flips and jitters have one entry per item, and a sequence item has n >= 1 centre frames")
+        if packed_u8.numel() != sum(h * w * 3 for h, w in sizes) * (n + 2):
+            raise _lib.DepthcoreError("packed frames: %d bytes are not n + 2 = %d frames of each of the sizes %r"
+                                      % (packed_u8.numel(), n + 2, sizes))
+        L, S, dev, H, W = _lib.lib(), self.num_scales, packed_u8.device, self.height, self.width
+        aug = any(j is not None for j in jitters)
+        per_item = 3 * n if aug else n + 2
+        n_img = per_item * S_it
+        steps = params = None
+        if aug:
+            if any(j is not None and (len(j) != 3 or any(len(win) != n or any(len(lv) != S for lv in win) for win in j)) for j in jitters):
+                raise _lib.DepthcoreError("jitters[item][w][j][s]: 3 windows of %d frames of %d levels" % (n, S))
+            # [steps (items, 3n, S, 4) int32 | params (items, 3n, S, 4) float32]: one copy; each item's rows as `sequence` lays them out
+            host = np.empty(n_img * S * 8, np.int32)
+            st, pa = host[:n_img * S * 4].reshape(S_it, -1, 4), host[n_img * S * 4:].view(np.float32).reshape(S_it, -1, 4)
+            st[...] = NO_OP
+            pa[...] = 0
+            for it, j in enumerate(jitters):
+                if j is not None:
+                    st[it], pa[it] = jitter_rows([draw for win in j for levels in win for draw in levels])
+            host_dev = torch.from_numpy(host).to(dev)
+            steps, params = host_dev.data_ptr(), host_dev.data_ptr() + n_img * S * 16
+        frames = S_it * (n + 2)
+        if len(set(sizes)) == 1:
+            level0 = self._resize(packed_u8.view((frames,) + sizes[0] + (3,)), H, W, None)
+        else:
+            per_frame = np.repeat(np.array(sizes, np.int64).reshape(S_it, 2), n + 2, axis=0)
+            nbytes = per_frame[:, 0] * per_frame[:, 1] * 3
+            level0 = torch.empty((frames, H, W, 3), dtype=torch.uint8, device=dev)
+            self.ragged_resize(packed_u8, np.cumsum(nbytes) - nbytes, per_frame, level0.view(-1), np.arange(frames) * (H * W * 3), H, W)
+        plan = self.sequence_batch_plan(S_it, n, aug)
+        tab_host, tab_dev = self._seq_tables()
+        scratch = torch.empty(max(int(plan.scratch_bytes), 16), dtype=torch.uint8, device=dev)
+        color = [torch.empty((n_img, 3, H >> s, W >> s), dtype=torch.float32, device=dev) for s in range(S)]
+        packed = torch.empty((n_img, H, W, 4), dtype=torch.float32, device=dev)
+        ptrs = _lib.c_void_p * S
+        check(L.dc_data_seq_batch_levels(level0.data_ptr(), S_it, n, H, W, S, (ctypes.c_int * S_it)(*[int(f) for f in flips]),
+                                         ptrs(*[c.data_ptr() for c in color]), packed.data_ptr(), steps, params,
+                                         tab_host.ctypes.data if tab_dev is not None else None,
+                                         tab_dev.data_ptr() if tab_dev is not None else None, tab_host.size, scratch.data_ptr(),
+                                         scratch.numel(), int(self.seq_lds_budget), stream(packed_u8)), "dc_data_seq_batch_levels")
+        out = {}
+        for w, (first, f) in enumerate(zip(WINDOW_FIRST, WINDOW_FRAMES)):
+            rows = seq_rows(w * n if aug else first, S_it, n)
+            for s in range(S):
+                out[("color", f, s)] = out[("color_aug", f, s)] = color[s][rows]
+            out[("color_packed", f, 0)] = packed[rows]
         return out
 
     def intrinsics(self, K, batch):

@@ -28,7 +28,8 @@ threads read each item's scan into the staging buffer behind the frames, the one
 descriptors, and `ops.lidar_depth_maps_staged` runs on the loader's stream -- with or without the frame cache.
 
 `SequenceLoader` is the same machine for the ConvGRU front-end's items (datasets/kitti_dataset_seq.py): one item of n + 2
-consecutive frames per step, already stacked over its n positions (GpuPreprocessor.sequence), its n scans behind the frames.
+consecutive frames per step, already stacked over its n positions (GpuPreprocessor.sequence), its n scans behind the frames;
+`items_per_step = S` delivers S such items per step, stacked time-major (GpuPreprocessor.sequence_batch).
 
 `decode_packed` is the evaluation scripts' host half: the files of a split decoded on the calling thread and packed the way
 `GpuPreprocessor.ragged` reads them (evaluate_depth.py, evaluate_depth_gru.py, evaluate_depth_fusion_v3.py).
@@ -431,26 +432,68 @@ class SequenceLoader(_StagedLoader):
     (shuffled) order of the items, then one `sample_sequence` per item in that order.  The n + 2 frames are decoded on the
     pool into a pinned buffer, the n centre scans -- when the dataset has them -- read behind them, one copy moves both, and
     the data step (GpuPreprocessor.sequence, then the projection through camera 2 with the mirror applied once) runs on the
-    loader's own stream.  Every GPU call comes from the consuming thread.  No frame cache."""
+    loader's own stream.  Every GPU call comes from the consuming thread.  No frame cache.
+    items_per_step = S > 1 (beyond the reference): a step is S consecutive items of the same permutation with the same
+    per-item draws, the last partial step dropped; their frames go up item-major in the one copy and come back stacked
+    time-major (GpuPreprocessor.sequence_batch: frame j of item s is row j * S + s), "depth_gt" of the n * S centre scans in
+    the same order from the one projection call."""
 
-    def __init__(self, dataset, num_workers=12, device="cuda", seed=0, shuffle=True, prefetch=2):
+    def __init__(self, dataset, num_workers=12, device="cuda", seed=0, shuffle=True, prefetch=2, items_per_step=1):
         self.dataset, self.batch_size = dataset, 1
+        self.items_per_step = int(items_per_step)
+        if self.items_per_step < 1:
+            raise ValueError("items_per_step must be >= 1, got %r" % (items_per_step,))
         self.is_train = bool(dataset.is_train)
         self._init_staging(num_workers, device, seed, shuffle, prefetch)
 
     def __len__(self):
-        return len(self.dataset)
+        return len(self.dataset) // self.items_per_step
 
     def plan(self, epoch=None):
-        """The epoch's items: [(index, (do_flip, jitters))]."""
+        """The epoch's items: [(index, (do_flip, jitters))]; with items_per_step = S > 1 the same list cut into runs of S:
+        [((index, ...), ((do_flip, jitters), ...))]."""
         ds = self.dataset
         rng = epoch_rng(self.seed, self.epoch if epoch is None else epoch)
         order = list(range(len(ds)))
         if self.shuffle:
             rng.shuffle(order)
-        return [(i, sample_sequence(self.is_train, rng, ds.n, ds.num_scales)) for i in order]
+        items = [(i, sample_sequence(self.is_train, rng, ds.n, ds.num_scales)) for i in order]
+        S = self.items_per_step
+        if S == 1:
+            return items
+        return [tuple(zip(*items[k * S:(k + 1) * S])) for k in range(len(items) // S)]
+
+    def _submit_step(self, indices, draws, alloc, device_depth=True):
+        """`_submit` for a step of several items: every item's n + 2 frames back to back, item-major, each item at the size
+        of its own first frame; the centre scans behind them time-major (scan j of item s is map j * S + s)."""
+        ds = self.dataset
+        paths = [ds.frame_paths(i) for i in indices]
+        sizes = [_image_size(p[0]) for p in paths]
+        frame_bytes = sum(len(p) * h * w * 3 for p, (h, w) in zip(paths, sizes))
+        flips, jitters = [bool(d[0]) for d in draws], [d[1] for d in draws]
+        scans = None
+        if ds.load_depth and device_depth:
+            per_item = [[(p, ds.calib_dir(i), 2) for p in ds.scan_paths(i)] for i in indices]
+            scans = self._scan_job([item[j] for j in range(ds.n) for item in per_item], flips * ds.n, frame_bytes)
+        total = scans["total"] if scans else frame_bytes
+        buf = alloc(total)[:total]
+        futures, off = [], 0
+        for item, (h, w) in zip(paths, sizes):
+            for path in item:
+                futures.append(self._pool_().submit(_decode_into, path, buf[off:off + h * w * 3].reshape(h, w, 3)))
+                off += h * w * 3
+        if scans:
+            futures += self._read_scans(scans, buf)
+        return {"buf": buf, "frame_bytes": frame_bytes, "sizes": sizes, "flips": flips, "jitters": jitters, "futures": futures,
+                "scans": scans}
 
     def _submit(self, index, draw, alloc, device_depth=True):
+        """Start decoding a plan entry: one item, or the items of a step."""
+        if self.items_per_step > 1:
+            return self._submit_step(index, draw, alloc, device_depth)
+        return self._submit_item(index, draw, alloc, device_depth)
+
+    def _submit_item(self, index, draw, alloc, device_depth=True):
         """Start decoding an item: the size from the header of its first frame, one task per frame writing at its offset of
         `alloc(total bytes)`, the scans behind them (device_depth=False: frames only).  -> job dict with the futures."""
         ds = self.dataset
@@ -472,12 +515,15 @@ class SequenceLoader(_StagedLoader):
 
     def decode_item(self, index, draw=(False, None)):
         """Host half of one item -> (frames (n + 2, Hn, Wn, 3) uint8, flip, jitters); the scans are left to the device half."""
-        job = self._submit(index, draw, lambda nbytes: np.empty(nbytes, np.uint8), device_depth=False)
+        job = self._submit_item(index, draw, lambda nbytes: np.empty(nbytes, np.uint8), device_depth=False)
         self._wait(job)
         return job["buf"].reshape(job["shape"]), job["flip"], job["jitters"]
 
     def _upload(self, job, slot):
         """One host-to-device copy + the data step (`_device_half`) -> (batch dict, event that completes it)."""
-        self._device_state(self.dataset.n)
+        self._device_state(self.dataset.n * self.items_per_step)
+        if self.items_per_step > 1:
+            return self._device_half(job, slot, self._wait(job), lambda dev: self._pre.sequence_batch(
+                dev[:job["frame_bytes"]], job["sizes"], self.dataset.n, job["flips"], job["jitters"]))
         return self._device_half(job, slot, self._wait(job), lambda dev: self._pre.sequence(
             dev[:job["frame_bytes"]].view(job["shape"]), job["flip"], job["jitters"]))

@@ -14,6 +14,7 @@ from ._autograd import (PRECISIONS, GradFork, SkipSum, WgradLanes, _c, _decision
                         add_decision_observer, assert_no_dangling_sums, matrix_precision, remove_decision_observer, skip_of)
 from ._lib import PhotoDesc, check, ptr, stream
 from .convnode import _ConvF
+from .data import seq_item_rows, seq_rows  # noqa: F401
 
 
 DepthcoreError = _lib.DepthcoreError
@@ -1706,6 +1707,27 @@ def gru_sequence_residual(features, hidden_states):
     return _GruResidual.apply(features, hidden_states)
 
 
+class _plan_streams:
+    """`with _plan_streams(S)`: the calling thread's Winograd launches plan their reduction as ONE of S stacked streams would
+    (dc_set_wino_plan_streams), so that a sequence's results in a lockstep step are those of its single-sequence call.  S == 1
+    touches nothing."""
+
+    def __init__(self, streams):
+        self.streams, self.before = int(streams), None
+
+    def __enter__(self):
+        if self.streams > 1:
+            self.before = _lib.lib().dc_set_wino_plan_streams(self.streams)
+            if self.before < 1:
+                raise _lib.DepthcoreError("dc_set_wino_plan_streams(%d) failed" % self.streams)
+        return self
+
+    def __exit__(self, *exc):
+        if self.before is not None:
+            _lib.lib().dc_set_wino_plan_streams(self.before)
+        return False
+
+
 class _GruLevel(torch.autograd.Function):
     """One feature level of `run_gru_v5` for a sequence of n frames (batch_size 1, trainer_gru.py:607-639) as ONE autograd node:
     the cell runs over the frames from the learned initial state, every tensor of every step lives in one buffer per kind
@@ -1717,42 +1739,55 @@ class _GruLevel(torch.autograd.Function):
     way, and the shared parameters get their gradients from ONE weight-gradient pass per convolution over the n frames as a
     batch once the walk is done (per-frame passes + a sum over frames otherwise).  Against the per-op
     graph (ConvGRUCell.forward, kept for single calls) that is ~9 elementwise sums, 3 fills / copies and 1.7 concatenations
-    fewer per cell step: 137 + 47 + 25 launches of a C4 step."""
+    fewer per cell step: 137 + 47 + 25 launches of a C4 step.
+    S > 1 (beyond the reference): the rows hold S sequences time-major (`seq_rows`: frame j of stream s is row j * S + s), every
+    launch of a time step takes the S streams as its batch, the weight-gradient pass takes the n * S rows, and the gradient of
+    the initial state the streams share is the sum of their rows (dc_gru_state_bwd).  S == 1 issues exactly the calls above."""
 
     @staticmethod
-    def forward(ctx, feats, h0, wg, bg, wc, bc):
+    def forward(ctx, feats, h0, wg, bg, wc, bc, S=1):
         L = _lib.lib()
         ff = _c(feats.detach())
-        n, C, H, W = ff.shape
+        rows, C, H, W = ff.shape
         P = H * W
+        S = int(S)
+        if S < 1 or rows % S or rows < S:
+            raise _lib.DepthcoreError("ConvGRU level: %d rows are not the frames of %d lockstep streams" % (rows, S))
+        n = rows // S
         if tuple(h0.shape) != (1, C, H, W) or tuple(wg.shape) != (2 * C, 2 * C, 3, 3) or tuple(wc.shape) != (C, 2 * C, 3, 3):
             raise _lib.DepthcoreError("ConvGRU level: state %s / gate weights %s / candidate weights %s do not match features %s" % (
                 tuple(h0.shape), tuple(wg.shape), tuple(wc.shape), tuple(ff.shape)))
         w_g, b_g, w_c, b_c = _c(wg.detach()), _c(bg.detach()), _c(wc.detach()), _c(bc.detach())
         dev = ff.device
-        Hs = torch.empty(n + 1, C, H, W, dtype=torch.float32, device=dev)
-        Hs[0].copy_(h0.detach()[0])
-        gates = torch.empty(n, 2 * C, H, W, dtype=torch.float32, device=dev)
-        rh = torch.empty(n, C, H, W, dtype=torch.float32, device=dev)
-        cnm = torch.empty(n, C, H, W, dtype=torch.float32, device=dev)
+        Hs = torch.empty((n + 1) * S, C, H, W, dtype=torch.float32, device=dev)
+        if S == 1:
+            Hs[0].copy_(h0.detach()[0])
+        else:
+            gru_infer_init([_c(h0.detach())], [Hs[:S]])                                              # the shared h0, one row per stream
+        gates = torch.empty(rows, 2 * C, H, W, dtype=torch.float32, device=dev)
+        rh = torch.empty(rows, C, H, W, dtype=torch.float32, device=dev)
+        cnm = torch.empty(rows, C, H, W, dtype=torch.float32, device=dev)
         ctx.prec = _use_precision(_precision[0])
-        ws = torch.empty(max(L.dc_conv3x3_fwd_workspace(C, C, 1, 2 * C, H, W), L.dc_conv3x3_fwd_workspace(C, C, 1, C, H, W)),
-                         dtype=torch.uint8, device=dev)
-        st = stream(ff)
-        for i in range(n):
-            x, h = ff[i:i + 1], Hs[i:i + 1]
-            # [reset | update] = sigmoid(conv_gates(cat(x, h)))                                       rnn.py:125-130
-            check(L.dc_conv3x3_fwd(ptr(x), C, 0, ptr(h), C, ptr(w_g), ptr(b_g), ptr(gates[i:i + 1]), ws.data_ptr(), 1, 2 * C, H, W,
-                                   ACT_SIGMOID, PAD_ZERO, st), "dc_conv3x3_fwd")
-            check(L.dc_gru_rh_fwd(ptr(gates[i:i + 1]), ptr(h), ptr(rh[i:i + 1]), 1, C, P, st), "dc_gru_rh_fwd")
-            # cnm = tanh(conv_can(cat(x, reset * h)))                                                   rnn.py:132-134
-            check(L.dc_conv3x3_fwd(ptr(x), C, 0, ptr(rh[i:i + 1]), C, ptr(w_c), ptr(b_c), ptr(cnm[i:i + 1]), ws.data_ptr(), 1, C, H, W,
-                                   ACT_TANH, PAD_ZERO, st), "dc_conv3x3_fwd")
-            check(L.dc_gru_blend_fwd(ptr(gates[i:i + 1]), ptr(h), ptr(cnm[i:i + 1]), ptr(Hs[i + 1:i + 2]), 1, C, P, st),
-                  "dc_gru_blend_fwd")                                                                # rnn.py:136
+        with _plan_streams(S):      # a stream's sums are ordered as in its single-sequence call, whatever S is
+            ws = torch.empty(max(L.dc_conv3x3_fwd_workspace(C, C, S, 2 * C, H, W), L.dc_conv3x3_fwd_workspace(C, C, S, C, H, W)),
+                             dtype=torch.uint8, device=dev)
+            st = stream(ff)
+            for i in range(n):
+                t = seq_rows(i, S)                                # time step i of the S streams: one contiguous slab
+                x, h = ff[t], Hs[t]
+                # [reset | update] = sigmoid(conv_gates(cat(x, h)))                                       rnn.py:125-130
+                check(L.dc_conv3x3_fwd(ptr(x), C, 0, ptr(h), C, ptr(w_g), ptr(b_g), ptr(gates[t]), ws.data_ptr(), S, 2 * C, H, W,
+                                       ACT_SIGMOID, PAD_ZERO, st), "dc_conv3x3_fwd")
+                check(L.dc_gru_rh_fwd(ptr(gates[t]), ptr(h), ptr(rh[t]), S, C, P, st), "dc_gru_rh_fwd")
+                # cnm = tanh(conv_can(cat(x, reset * h)))                                                   rnn.py:132-134
+                check(L.dc_conv3x3_fwd(ptr(x), C, 0, ptr(rh[t]), C, ptr(w_c), ptr(b_c), ptr(cnm[t]), ws.data_ptr(), S, C, H, W,
+                                       ACT_TANH, PAD_ZERO, st), "dc_conv3x3_fwd")
+                check(L.dc_gru_blend_fwd(ptr(gates[t]), ptr(h), ptr(cnm[t]), ptr(Hs[seq_rows(i + 1, S)]), S, C, P, st),
+                      "dc_gru_blend_fwd")                                                                # rnn.py:136
         out = torch.empty_like(ff)
-        check(L.dc_gru_residual_fwd(ptr(ff), ptr(Hs), ptr(out), n, C * P, st), "dc_gru_residual_fwd")   # trainer_gru.py:637-639
+        check(L.dc_gru_residual_fwd(ptr(ff), ptr(Hs), ptr(out), n, S * C * P, st), "dc_gru_residual_fwd")   # trainer_gru.py:637-639
         ctx.save_for_backward(ff, Hs, gates, rh, cnm, w_g, w_c)
+        ctx.streams = S
         ctx.slots = tuple(_slot(t) for t in (wg, bg, wc, bc))
         for t, k in ((wg, 2), (wc, 4)):
             if ctx.needs_input_grad[k]:
@@ -1763,7 +1798,9 @@ class _GruLevel(torch.autograd.Function):
     def backward(ctx, g):
         L = _lib.lib()
         ff, Hs, gates, rh, cnm, w_g, w_c = ctx.saved_tensors
-        n, C, H, W = ff.shape
+        rows, C, H, W = ff.shape
+        S = ctx.streams
+        n = rows // S
         P = H * W
         dev = ff.device
         need = ctx.needs_input_grad
@@ -1771,30 +1808,33 @@ class _GruLevel(torch.autograd.Function):
         st = stream(ff)
         f32 = dict(dtype=torch.float32, device=dev)
         dHs = torch.empty_like(Hs)
-        check(L.dc_gru_residual_bwd(ptr(g_c), ptr(dHs), n, C * P, st), "dc_gru_residual_bwd")
+        check(L.dc_gru_residual_bwd(ptr(g_c), ptr(dHs), n, S * C * P, st), "dc_gru_residual_bwd")
         dfe = torch.empty_like(ff)
-        dgates, dcn = torch.empty(n, 2 * C, H, W, **f32), torch.empty(n, C, H, W, **f32)     # g of the two convolutions' outputs, per frame
-        dxc, drh = torch.empty(1, C, H, W, **f32), torch.empty(1, C, H, W, **f32)
+        dgates, dcn = torch.empty(rows, 2 * C, H, W, **f32), torch.empty(rows, C, H, W, **f32)     # g of the two convolutions' outputs, per frame
+        dxc, drh = torch.empty(S, C, H, W, **f32), torch.empty(S, C, H, W, **f32)
         _use_precision(ctx.prec)
-        ws = torch.empty(max(L.dc_conv3x3_bwd_workspace(C, C, b, co, H, W) for b in (1, n) for co in (C, 2 * C)),
-                         dtype=torch.uint8, device=dev)
-        for i in range(n - 1, -1, -1):
-            x, h, gt, dh = ff[i:i + 1], Hs[i:i + 1], gates[i:i + 1], dHs[i:i + 1]
-            dg, dc = dgates[i:i + 1], dcn[i:i + 1]
-            # h_{i+1} = (1-u) h_i + u cnm: dHs[i+1] is complete here (residual + step i+1)
-            check(L.dc_gru_blend_bwd_acc(ptr(gt), ptr(h), ptr(cnm[i:i + 1]), ptr(dHs[i + 1:i + 2]), ptr(dg), ptr(dh), ptr(dc),
-                                         1, C, P, st), "dc_gru_blend_bwd_acc")
-            # candidate convolution over cat(x, r*h), data gradients only: that of x takes the residual's share (g[i]) along
-            check(L.dc_conv3x3_bwd_add(ptr(x), C, 0, ptr(rh[i:i + 1]), C, ptr(w_c), ptr(cnm[i:i + 1]), ptr(dc), ptr(dxc), ptr(drh),
-                                       ptr(g_c[i:i + 1]), None, None, None, ws.data_ptr(), 1, C, H, W, ACT_TANH, PAD_ZERO, st),
-                  "dc_conv3x3_bwd_add")
-            check(L.dc_gru_rh_bwd_acc(ptr(gt), ptr(h), ptr(drh), ptr(dg), ptr(dh), 1, C, P, st), "dc_gru_rh_bwd_acc")
-            # gate convolution over cat(x, h): d x = own + (candidate's + residual's), d h_i = own + what the slot holds
-            check(L.dc_conv3x3_bwd_add(ptr(x), C, 0, ptr(h), C, ptr(w_g), ptr(gt), ptr(dg), ptr(dfe[i:i + 1]), ptr(dh),
-                                       ptr(dxc), ptr(dh), None, None, ws.data_ptr(), 1, 2 * C, H, W, ACT_SIGMOID, PAD_ZERO, st),
-                  "dc_conv3x3_bwd_add")
+        with _plan_streams(S):      # the workspace is sized and the walk's data gradients are planned as one stream's
+            ws = torch.empty(max(L.dc_conv3x3_bwd_workspace(C, C, b, co, H, W) for b in (S, rows) for co in (C, 2 * C)),
+                             dtype=torch.uint8, device=dev)
+            for i in range(n - 1, -1, -1):
+                t = seq_rows(i, S)
+                x, h, gt, dh = ff[t], Hs[t], gates[t], dHs[t]
+                dg, dc = dgates[t], dcn[t]
+                # h_{i+1} = (1-u) h_i + u cnm: dHs[i+1] is complete here (residual + step i+1)
+                check(L.dc_gru_blend_bwd_acc(ptr(gt), ptr(h), ptr(cnm[t]), ptr(dHs[seq_rows(i + 1, S)]), ptr(dg), ptr(dh), ptr(dc),
+                                             S, C, P, st), "dc_gru_blend_bwd_acc")
+                # candidate convolution over cat(x, r*h), data gradients only: that of x takes the residual's share (g[i]) along
+                check(L.dc_conv3x3_bwd_add(ptr(x), C, 0, ptr(rh[t]), C, ptr(w_c), ptr(cnm[t]), ptr(dc), ptr(dxc), ptr(drh),
+                                           ptr(g_c[t]), None, None, None, ws.data_ptr(), S, C, H, W, ACT_TANH, PAD_ZERO, st),
+                      "dc_conv3x3_bwd_add")
+                check(L.dc_gru_rh_bwd_acc(ptr(gt), ptr(h), ptr(drh), ptr(dg), ptr(dh), S, C, P, st), "dc_gru_rh_bwd_acc")
+                # gate convolution over cat(x, h): d x = own + (candidate's + residual's), d h_i = own + what the slot holds
+                check(L.dc_conv3x3_bwd_add(ptr(x), C, 0, ptr(h), C, ptr(w_g), ptr(gt), ptr(dg), ptr(dfe[t]), ptr(dh),
+                                           ptr(dxc), ptr(dh), None, None, ws.data_ptr(), S, 2 * C, H, W, ACT_SIGMOID, PAD_ZERO, st),
+                      "dc_conv3x3_bwd_add")
         # the parameters are shared by the n steps and nothing downstream waits for their gradients: ONE weight-gradient pass
-        # per convolution with the n frames as its batch (sum over frames = sum over the batch), after the walk
+        # per convolution with the n * S frames as its batch (sum over frames and streams = sum over the batch), after the walk.
+        # Hs / rh hold the state each frame READ in their first n * S rows (time-major: row j * S + s), as the frames do.
         outs = [None] * 4
         for k, (like, x1, y, gy, co, act) in enumerate(((w_g, Hs, gates, dgates, 2 * C, ACT_SIGMOID), (w_c, rh, cnm, dcn, C, ACT_TANH))):
             if not (need[2 + 2 * k] or need[3 + 2 * k]):
@@ -1806,15 +1846,25 @@ class _GruLevel(torch.autograd.Function):
                 if db is None:
                     db = torch.empty(co, **f32)
             check(L.dc_conv3x3_bwd_add(ptr(ff), C, 0, ptr(x1), C, ptr(like), ptr(y), ptr(gy), None, None, None, None, ptr(dw), ptr(db),
-                                       ws.data_ptr(), n, co, H, W, act, PAD_ZERO, st), "dc_conv3x3_bwd_add")
+                                       ws.data_ptr(), rows, co, H, W, act, PAD_ZERO, st), "dc_conv3x3_bwd_add")
             outs[2 * k], outs[2 * k + 1] = dw, db
-        return (dfe if need[0] else None, dHs[0:1] if need[1] else None) + tuple(outs)
+        dh0 = None
+        if need[1]:
+            if S == 1:
+                dh0 = dHs[0:1]
+            else:                                             # the streams share h0: its gradient is the sum of their rows
+                dh0 = torch.empty(1, C, H, W, **f32)
+                check(L.dc_gru_state_bwd(ptr(dHs), ptr(dh0), S, C * P, st), "dc_gru_state_bwd")
+        return (dfe if need[0] else None, dh0) + tuple(outs) + (None,)
 
 
-def gru_level_sequence(features, h0, conv_gates, conv_can):
+def gru_level_sequence(features, h0, conv_gates, conv_can, streams=1):
     """features (n,C,H,W) of one sequence, h0 (1,C,H,W) -> features + (H[1:] + H[:-1]) / 2, H the hidden states of the cell
-    (conv_gates / conv_can: its two nn.Conv2d) run over the frames in order (trainer_gru.py:607-639 at one level)."""
-    return _GruLevel.apply(features, h0, conv_gates.weight, conv_gates.bias, conv_can.weight, conv_can.bias)
+    (conv_gates / conv_can: its two nn.Conv2d) run over the frames in order (trainer_gru.py:607-639 at one level).
+    streams = S > 1: features (n * S, C, H, W) hold S sequences time-major (`seq_rows`); they advance in lockstep from the
+    shared h0 -- the same four launches per time step with S as their batch -- and the parameters' and h0's gradients are the
+    sums over the streams."""
+    return _GruLevel.apply(features, h0, conv_gates.weight, conv_gates.bias, conv_can.weight, conv_can.bias, int(streams))
 
 
 # ---- inference form of the cell step: B independent streams, every level in one launch (dc_gru_infer_*) ---------------------

@@ -35,9 +35,16 @@ def synthetic_batch(batch, height, width, device, num_scales=4, frame_ids=(0, -1
     return inputs
 
 
-def synthetic_sequence_batch(len_sequence, height, width, device, num_scales=4, frame_ids=(0, -1, 1), seed=0):
+def synthetic_sequence_batch(len_sequence, height, width, device, num_scales=4, frame_ids=(0, -1, 1), seed=0, items=None):
     """One sequence of `len_sequence` frames in the schema of datasets/kitti_dataset_seq.py:110-140 (batch size 1):
-    ("color", f, s, j), ("K", s, j), ("inv_K", s, j)."""
+    ("color", f, s, j), ("K", s, j), ("inv_K", s, j).
+    items = S: instead the ALREADY STACKED dict of a step of S sequences as the loader delivers it (("color", f, s),
+    ("color_aug", f, s), ("color_packed", f, 0), ("K", s), ("inv_K", s) with len_sequence * S rows), time-major: frame j of
+    item s is row j * S + s (depthcore.data.seq_rows)."""
+    if items is not None:
+        if int(items) < 1:
+            raise ValueError("items must be >= 1, got %r" % (items,))
+        return synthetic_batch(len_sequence * int(items), height, width, device, num_scales, frame_ids, seed, packed=True)
     flat = synthetic_batch(len_sequence, height, width, device, num_scales, frame_ids, seed)
     out = {}
     for k, v in flat.items():

@@ -95,10 +95,21 @@ class ConvGRUBlocks_v5(nn.Module):
     def forward(self, encoder_features, hidden_states):
         return [cell(f, h) for cell, f, h in zip(self.cells(), encoder_features, hidden_states)]
 
-    def run_sequence(self, features):
+    def run_sequence(self, features, streams=1):
         """trainer_gru.py:607-639 for batch_size 1: `features[k]` (n, C_k, h_k, w_k) holds the encoder features of the n
         frames of one sequence; the cells run over the frames in order from the learned initial states; returns
-        features[k] + (H[1:] + H[:-1]) / 2 with H the n+1 hidden states."""
+        features[k] + (H[1:] + H[:-1]) / 2 with H the n+1 hidden states.
+        streams = S > 1 (beyond the reference): `features[k]` (n * S, C_k, h_k, w_k) holds S sequences time-major (frame j of
+        sequence s is row j * S + s, depthcore.ops.seq_rows); they advance in lockstep, each from the shared learned initial
+        state.  The number of streams belongs to the call, not to the module: the same module validates one sequence."""
+        streams = int(streams)
+        if streams < 1 or features[0].shape[0] % streams:
+            raise DepthcoreError("run_sequence: %d rows are not the frames of %d streams" % (features[0].shape[0], streams))
+        if streams > 1 and not (LEVEL_NODES and features[0].is_cuda and not LEVEL_STREAMS):
+            raise DepthcoreError("run_sequence: lockstep streams run on the level nodes (DC_GRU_LEVEL_NODES=1, no level streams)")
+        if streams > 1:
+            return [_ops.gru_level_sequence(f, cell.h0_layer1, cell.cgru_1.conv_gates, cell.cgru_1.conv_can, streams=streams)
+                    for cell, f in zip(self.cells(), features)]
         if LEVEL_NODES and features[0].is_cuda:
             # one autograd node per level: the frame loop, the trace and the reverse walk live inside it (ops._GruLevel)
             if not LEVEL_STREAMS:

@@ -101,6 +101,7 @@ _BUILD = [
     ("nets_dtype", str, "f32", ["f32", "bf16"]),  # matrix-core precision of the networks' convolutions (bf16: BASELINE configs[4] policy; the loss stays fp32)
     ("imagenet_weights", str, None, None),       # weights_init=pretrained: path of the torchvision resnet{N}-*.pth (no download here)
     ("gru", str, None, [None, "v5"]),            # front-end of trainer_gru.py (run_gru_v5; sequences of len_sequence frames)
+    ("seq_batch", int, 1, None),                 # ConvGRU front-end: sequence items per optimiser step, advanced in lockstep (batch_size stays 1)
     ("splits_dir", str, os.path.join(_HERE, "splits"), None),  # evaluate_depth.py: <splits_dir>/<eval_split>/{test_files.txt, gt_depths.npz} (none ship here)
     ("eval_json", str, None, None),              # evaluate_depth.py: also write the results to this JSON file
     ("log_images", int, 0, None),                # items per log step whose image panel is written to <log_path>/<mode>/images/ (Trainer.log_images); 0 = off, the reference writes 4
@@ -127,7 +128,7 @@ class MonodepthOptions:
     def parse(self, argv=None):
         self.options = self.parser.parse_args(argv)
         for name, typ, _, _ in _BUILD:
-            if typ is int and getattr(self.options, name) in (0, 1) and name != "bucket_mb":
+            if typ is int and getattr(self.options, name) in (0, 1) and name not in ("bucket_mb", "seq_batch"):
                 setattr(self.options, name, bool(getattr(self.options, name)))
         return self.options
 

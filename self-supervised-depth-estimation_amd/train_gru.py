@@ -3,7 +3,9 @@
 
 MonodepthOptions -> Trainer -> train_sequences(): a single process on one GPU.  The drive lists are read from
 `<splits_dir>/<split>/{train,val}_sequences.txt` ("date/drive" per line; none ship with the project); `--len_sequence`,
-`--train_n_tuples`, `--test_n_tuples` and `--h_s_epoch` are the reference's.  One sequence item is one step: the batch size is 1."""
+`--train_n_tuples`, `--test_n_tuples` and `--h_s_epoch` are the reference's.  One sequence item is one step: the batch size is 1.
+`--seq_batch S` (beyond the reference, default 1) trains S sequence items per step in lockstep: the loss and the BatchNorm
+statistics run over the S * len_sequence frames, every parameter is shared, the learning rate is not rescaled."""
 import sys
 
 from options import MonodepthOptions
@@ -17,6 +19,7 @@ def main(argv=None):
     if not opts.gru:
         opts.gru = "v5"
     opts.batch_size = 1                     # trainer_gru.py:206-240: DataLoader(batch_size=1), one sequence per step
+    # (opts.seq_batch sequences per step is its own option: batch_size keeps the reference's meaning and value)
     from trainer import Trainer
     trainer = Trainer(opts)
     trainer.train_sequences()

@@ -71,6 +71,8 @@ class _NoWinoCache:
 
 
 class Trainer:
+    seq_batch = 1            # sequence items per step of the ConvGRU front-end (opt.seq_batch, set in __init__)
+
     def __init__(self, options, device="cuda:0", rank=0, world_size=1, process_group=None, seed=0):
         self.opt = options
         self.device = torch.device(device)
@@ -99,7 +101,19 @@ class Trainer:
         if self.opt.gru and self.opt.batch_size != 1:
             raise ValueError("run_gru_v5 works for batch_size = 1 only (trainer_gru.py:596)")
         # images per loss evaluation: the reference's GRU trainer stacks the sequence along the batch (trainer_gru.py:256-263)
-        self.loss_batch = self.opt.batch_size * (self.opt.len_sequence if self.opt.gru else 1)
+        # opt.seq_batch = S (beyond the reference): S sequence items per step, advanced in lockstep and stacked time-major
+        # (frame j of item s is row j * S + s, depthcore.data.seq_rows); batch_size keeps its meaning and stays 1
+        self.seq_batch = int(getattr(self.opt, "seq_batch", 1))
+        if self.seq_batch < 1:
+            raise ValueError("seq_batch must be >= 1, got %r" % (self.opt.seq_batch,))
+        if self.seq_batch > 1 and not self.opt.gru:
+            raise ValueError("seq_batch > 1 belongs to the ConvGRU front-end (opt.gru); the other trainers batch with batch_size")
+        if self.seq_batch > 1 and getattr(self.opt, "hip_graph", False):
+            raise NotImplementedError("hip_graph captures the ConvGRU step for seq_batch = 1 only; run seq_batch > 1 eagerly")
+        if self.seq_batch > 1 and not self.opt.fused_loss:
+            raise NotImplementedError("seq_batch > 1 runs the fused loss: the layer-by-layer modules are built for one batch size, "
+                                      "and a step has seq_batch items where a validation item has one")
+        self.loss_batch = self.opt.batch_size * (self.opt.len_sequence * self.seq_batch if self.opt.gru else 1)
         self.num_scales = len(self.opt.scales)
         self.num_input_frames = len(self.opt.frame_ids)                                   # trainer.py:50-51
         self.num_pose_frames = 2 if self.opt.pose_model_input == "pairs" else self.num_input_frames
@@ -385,7 +399,12 @@ class Trainer:
             outputs = dict(self.models["fusion"](self.models["depth"](features)))
         elif self.opt.gru:                                       # trainer_gru.py:595-644, batch size 1
             features = self.models["encoder"](inputs[("color", 0, 0)])
-            outputs = dict(self.models["depth"](self.models["gru"].run_sequence(features)))
+            # the streams belong to the call: a step holds seq_batch items, a validation item (val_sequence) one
+            streams = features[0].shape[0] // self.opt.len_sequence
+            if streams * self.opt.len_sequence != features[0].shape[0]:
+                raise ValueError("a ConvGRU batch stacks len_sequence = %d frames per item, got %d rows"
+                                 % (self.opt.len_sequence, features[0].shape[0]))
+            outputs = dict(self.models["depth"](self.models["gru"].run_sequence(features, streams=streams)))
         else:
             features = self.models["encoder"](inputs[("color_aug", 0, 0)])
             outputs = dict(self.models["depth"](features))
@@ -730,7 +749,7 @@ class Trainer:
             items = datasets.generate_sequences(self.opt.data_path, drives, n, n_tuples, random.Random("depthcore.sequences/%s" % mode))
             ds = datasets.KITTISequenceDataset(self.opt.data_path, self.opt.height, self.opt.width, n, items, mode == "train", img_ext=ext)
             loaders.append(SequenceLoader(ds, self.opt.num_workers, self.device, seed=int(mode == "val"), shuffle=mode == "train",
-                                          prefetch=prefetch))
+                                          prefetch=prefetch, items_per_step=self.seq_batch if mode == "train" else 1))
         self.train_loader, self.val_loader = loaders
         self._val_iter = None
         return self.train_loader, self.val_loader
@@ -859,7 +878,8 @@ class Trainer:
             t = int(t)
             return "{:02d}h{:02d}m{:02d}s".format(t // 3600, t // 60 % 60, t % 60)
         step = self.step if step is None else step
-        samples_per_sec = self.opt.batch_size / duration
+        # the ConvGRU front-end reports frames: seq_batch items of len_sequence frames per step
+        samples_per_sec = (self.seq_batch * self.opt.len_sequence if self.opt.gru and self.seq_batch > 1 else self.opt.batch_size) / duration
         time_sofar = time.time() - self.start_time
         training_time_left = (self.num_total_steps / step - 1.0) * time_sofar if step > 0 else 0
         print("epoch {:>3} | batch {:>6} | examples/s: {:5.1f} | loss: {:.5f} | time elapsed: {} | time left: {}".format(
