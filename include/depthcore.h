@@ -768,6 +768,36 @@ int dc_gru_infer_rh(const dc_gru_infer_level* lv, int nlev, int B, void* stream)
 int dc_gru_infer_tail(const dc_gru_infer_level* lv, int nlev, int B, void* stream);
 int dc_gru_infer_init(const float* const* h0, float* const* state, const size_t* M, int nlev, int B, void* stream);
 
+/* ------------------------------------------------------------------ f3 ConvLSTM front-end (gru_version v8) */
+/* networks/rnn.py:32-79 `ConvLSTMCell_v1`: the cell's 3x3 convolution over cat(x, h) is a dc_conv3x3_fwd call with the two
+ * sources, zero padding, bias and no activation; its raw output cc (B, 4C, P) holds the gate pre-activations [i | f | o | g],
+ * P = H * W.  The state update, one pass per direction:
+ *   dc_lstm_cell_fwd:  c_next = sigmoid(f) * c_cur + sigmoid(i) * tanh(g),  h_next = sigmoid(o) * tanh(c_next)   (all (B, C, P))
+ *   dc_lstm_cell_bwd:  recomputes the gates from cc (nothing but cc and c_cur is kept per frame); with dc = g_c + g_h o (1 - t^2),
+ *                      t = tanh(c_next):  d_cc = [dc g i(1-i) | dc c_cur f(1-f) | g_h t o(1-o) | dc i (1-g^2)],  d_c_cur = dc f.
+ *                      g_h or g_c may be NULL: a zero gradient (the last frame's cell state has no consumer).
+ * c_cur has B rows: a learned initial state (1, C, P) shared by B > 1 items is expanded by the caller (depthcore.ops.lstm_cell),
+ * whose reduction over B is then autograd's.
+ * networks/rnn.py:767-773 with :783-791, the coarse-to-fine hand-over of `FeatureFusionBlock_v2`, one launch per direction:
+ *   dc_lstm_handover_fwd:  pre = relu(a + (h_prev + h_new) / 2)  (B, C, h, w);  up = PixelShuffle(2)(tanh(pre))  (B, C/4, 2h, 2w),
+ *                          up[b, q, 2y + i, 2x + j] = tanh(pre[b, 4q + 2i + j, y, x]).  up may be NULL (the finest block).
+ *                          The ReLU is the reference's in-place nn.ReLU of resConfUnit2 rewriting pre_output before it is shuffled.
+ *   dc_lstm_handover_bwd:  d = (pre > 0) * (g_pre + unshuffle(g_up) * (1 - tanh(pre)^2));  d_a = d,  d_h_prev = d_h_new = d / 2.
+ *                          g_pre or g_up may be NULL (zero); any of d_a, d_h_prev, d_h_new may be NULL (not wanted), not all three.
+ * float4 loads and stores where the sizes allow (cell: C * P % 4 == 0; hand-over: w % 4 == 0; 16-byte aligned bases), scalar
+ * otherwise.  Every thread owns what it writes: no atomics, two calls give the same bits; no allocation or synchronisation:
+ * capturable.  dc_lstm_block: threads per block of these launches (a cell block's float4 body covers 4 * dc_lstm_block floats of
+ * a batch item).  DC_EINVAL: a NULL pointer among the required ones, a size <= 0, C % 4 != 0 (hand-over), B > 65535 (cell),
+ * a tensor of 2^31 elements or more. */
+int dc_lstm_block(void);
+int dc_lstm_cell_fwd(const float* cc, const float* c_cur, float* h_next, float* c_next, int B, int C, int P, void* stream);
+int dc_lstm_cell_bwd(const float* cc, const float* c_cur, const float* g_h, const float* g_c, float* d_cc, float* d_c_cur,
+                     int B, int C, int P, void* stream);
+int dc_lstm_handover_fwd(const float* a, const float* h_prev, const float* h_new, float* pre, float* up,
+                         int B, int C, int h, int w, void* stream);
+int dc_lstm_handover_bwd(const float* pre, const float* g_pre, const float* g_up, float* d_a, float* d_h_prev, float* d_h_new,
+                         int B, int C, int h, int w, void* stream);
+
 /* ------------------------------------------------------------------ transformed-weight cache of the Winograd kernels */
 /* ------------------------------------------------------------------ reduced-precision networks (BASELINE configs[4]) */
 /* "Networks in reduced precision, loss in fp32" (trainer_fusion_v3.py:311-330 under mixed precision; the reference itself

@@ -261,6 +261,11 @@ def _sig(lib):
         "dc_gru_infer_rh": (i, [POINTER(GruInferLevel), i, i, p]),
         "dc_gru_infer_tail": (i, [POINTER(GruInferLevel), i, i, p]),
         "dc_gru_infer_init": (i, [p, p, p, i, i, p]),
+        "dc_lstm_block": (i, []),
+        "dc_lstm_cell_fwd": (i, [p, p, p, p, i, i, i, p]),
+        "dc_lstm_cell_bwd": (i, [p, p, p, p, p, p, i, i, i, p]),
+        "dc_lstm_handover_fwd": (i, [p, p, p, p, p, i, i, i, i, p]),
+        "dc_lstm_handover_bwd": (i, [p, p, p, p, p, p, i, i, i, i, p]),
         "dc_set_matrix_precision": (i, [i]),
         "dc_get_matrix_precision": (i, []),
         "dc_clear_error": (i, []),

@@ -1940,3 +1940,89 @@ def copy_segments(srcs, dsts):
         k = len(s)
         check(L.dc_gather_copy((ctypes.c_void_p * k)(*[ptr(t.detach()) for t in s]), (ctypes.c_void_p * k)(*[ptr(t) for t in d]),
                                (ctypes.c_size_t * k)(*[t.numel() for t in s]), k, stream(d[0])), "dc_gather_copy")
+
+
+# ----------------------------------------------------------------------------------------------
+# f3 ConvLSTM v8: state update and coarse-to-fine hand-over   (reference networks/rnn.py:70-79, 767-773, 783-791)
+# ----------------------------------------------------------------------------------------------
+def _rows(t, B, what):
+    """A learned initial state (1, C, H, W) shared by B > 1 items, expanded: its gradient's sum over B is autograd's (a plain,
+    ordered torch reduction)."""
+    if t.shape[0] == 1 and B > 1:
+        return t.expand((B,) + tuple(t.shape[1:]))
+    if t.shape[0] != B:
+        raise DepthcoreError("%s has %d rows for a batch of %d" % (what, t.shape[0], B))
+    return t
+
+
+class _LstmCell(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cc, c_cur):
+        L = _lib.lib()
+        g, c = _c(cc.detach()), _c(c_cur.detach())
+        if c.dim() != 4 or tuple(g.shape) != (c.shape[0], 4 * c.shape[1]) + tuple(c.shape[2:]):
+            raise DepthcoreError("gate pre-activations %s do not match the cell state %s" % (tuple(g.shape), tuple(c.shape)))
+        B, C, P = c.shape[0], c.shape[1], c.shape[2] * c.shape[3]
+        h_next, c_next = torch.empty_like(c), torch.empty_like(c)
+        check(L.dc_lstm_cell_fwd(ptr(g), ptr(c), ptr(h_next), ptr(c_next), B, C, P, stream(c)), "dc_lstm_cell_fwd")
+        ctx.save_for_backward(g, c)
+        ctx.set_materialize_grads(False)        # a state nobody reads (the last frame's c) arrives as None -> NULL
+        return h_next, c_next
+
+    @staticmethod
+    def backward(ctx, g_h, g_c):
+        if g_h is None and g_c is None:
+            return None, None
+        L = _lib.lib()
+        g, c = ctx.saved_tensors
+        B, C, P = c.shape[0], c.shape[1], c.shape[2] * c.shape[3]
+        gh = _c(g_h) if g_h is not None else None
+        gc = _c(g_c) if g_c is not None else None
+        d_cc, d_c = torch.empty_like(g), torch.empty_like(c)
+        check(L.dc_lstm_cell_bwd(ptr(g), ptr(c), ptr(gh), ptr(gc), ptr(d_cc), ptr(d_c), B, C, P, stream(c)), "dc_lstm_cell_bwd")
+        return d_cc, d_c
+
+
+def lstm_cell(cc, c_cur):
+    """(h_next, c_next) of a ConvLSTM step from the raw output cc (B, 4C, H, W) = [i | f | o | g] of the cell's convolution and
+    the cell state c_cur (B, C, H, W), or (1, C, H, W): a learned initial state shared over the batch."""
+    return _LstmCell.apply(cc, _rows(c_cur, cc.shape[0], "c_cur"))
+
+
+class _LstmHandover(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, h_prev, h_new, need_up):
+        L = _lib.lib()
+        aa, hp, hn = _c(a.detach()), _c(h_prev.detach()), _c(h_new.detach())
+        if aa.dim() != 4 or hp.shape != aa.shape or hn.shape != aa.shape or aa.shape[1] % 4:
+            raise DepthcoreError("hand-over takes three (B, C, h, w) tensors with C a multiple of 4, got %s %s %s"
+                                 % (tuple(aa.shape), tuple(hp.shape), tuple(hn.shape)))
+        B, C, h, w = aa.shape
+        pre = torch.empty_like(aa)
+        up = torch.empty(B, C // 4, 2 * h, 2 * w, dtype=torch.float32, device=aa.device) if need_up else None
+        check(L.dc_lstm_handover_fwd(ptr(aa), ptr(hp), ptr(hn), ptr(pre), ptr(up), B, C, h, w, stream(aa)), "dc_lstm_handover_fwd")
+        ctx.save_for_backward(pre)
+        ctx.set_materialize_grads(False)
+        return pre, up
+
+    @staticmethod
+    def backward(ctx, g_pre, g_up):
+        need = ctx.needs_input_grad
+        if (g_pre is None and g_up is None) or not any(need[:3]):
+            return None, None, None, None
+        L = _lib.lib()
+        pre, = ctx.saved_tensors
+        B, C, h, w = pre.shape
+        gp = _c(g_pre) if g_pre is not None else None
+        gu = _c(g_up) if g_up is not None else None
+        d = [torch.empty_like(pre) if need[k] else None for k in range(3)]
+        check(L.dc_lstm_handover_bwd(ptr(pre), ptr(gp), ptr(gu), ptr(d[0]), ptr(d[1]), ptr(d[2]), B, C, h, w, stream(pre)),
+              "dc_lstm_handover_bwd")
+        return d[0], d[1], d[2], None
+
+
+def lstm_handover(a, h_prev, h_new, need_up=True):
+    """pre = relu(a + (h_prev + h_new) / 2) and up = pixel_shuffle(tanh(pre), 2) (None without need_up) in one launch:
+    FeatureFusionBlock_v2's join of the residual unit's output with the mean hidden state, and its UpscalePS.  h_prev may be
+    (1, C, h, w): the learned initial hidden state shared over the batch."""
+    return _LstmHandover.apply(a, _rows(h_prev, a.shape[0], "h_prev"), h_new, bool(need_up))

@@ -58,8 +58,8 @@ def check_options(opt):
     if opt.eval_split.startswith("odom"):
         raise ValueError("eval_split %r is pose evaluation: run evaluate_pose.py" % opt.eval_split)
     if getattr(opt, "gru_version", "v5") != "v5":
-        raise NotImplementedError("gru_version %r: the ConvGRU front-end of this project is v5 (ConvGRUBlocks_v5, run_gru_v5)"
-                                  % opt.gru_version)
+        raise NotImplementedError("gru_version %r: this evaluation covers v5 (ConvGRUBlocks_v5, evaluate_v5_seq); v8 trains "
+                                  "(train_gru.py) but is not evaluated here" % opt.gru_version)
     if opt.post_process:
         raise NotImplementedError("--post_process with the ConvGRU front-end: the reference's v5 evaluation has none, and a "
                                   "mirrored stream under a learned, non-symmetric initial state is a different model")

@@ -24,6 +24,8 @@ through the depth encoder + decoder and fused by `networks.Fusion_v3` (BASELINE 
 `opt.len_sequence` frames (dict keys carry the sequence index: ("color", f, s, j), ("K", s, j)), the encoder features of the
 sequence pass through `networks.ConvGRUBlocks_v5`, and the loss runs on the sequence stacked along the batch.  Its data
 come from `build_sequence_loaders` (items already stacked by the data step) and its loop is `train_sequences` (train_gru.py).
+`opt.gru = "v8"` is trainer_gru.py:402-460 (`run_gru_v8`) on the same data and loop: the decoder runs with pre_disp=True and
+`networks.ConvGRUBlocks_v8` (four ConvLSTM cells + fusion blocks, coarse to fine) turns its feature maps into the disparities.
 `opt.model = "rn_encoder_with_attention"` (or `"rn_fusion"` together with `opt.fusion = "v3"`) builds the depth encoder as
 `networks.ResnetEncoderAttention` (trainer_dpt.py:78-92); every other value, the default included, builds `ResnetEncoder`.
 """
@@ -94,8 +96,8 @@ class Trainer:
             raise NotImplementedError("fusion front-ends: None (trainer.py) or 'v3' (trainer_fusion_v3.py)")
         if self.opt.fusion and -2 not in self.opt.frame_ids:
             raise ValueError("the Fusion_v3 front-end stacks frames [-2, -1, 0]: frame_ids must be [0, -2, -1, 1]")
-        if getattr(self.opt, "gru", None) not in (None, "v5"):
-            raise NotImplementedError("ConvGRU front-ends: None or 'v5' (trainer_gru.py run_gru_v5)")
+        if getattr(self.opt, "gru", None) not in (None, "v5", "v8"):
+            raise NotImplementedError("ConvGRU front-ends: None, 'v5' (trainer_gru.py run_gru_v5) or 'v8' (run_gru_v8)")
         if self.opt.gru and self.opt.fusion:
             raise ValueError("fusion and gru front-ends are separate trainers in the reference; pick one")
         if self.opt.gru and self.opt.batch_size != 1:
@@ -113,6 +115,14 @@ class Trainer:
         if self.seq_batch > 1 and not self.opt.fused_loss:
             raise NotImplementedError("seq_batch > 1 runs the fused loss: the layer-by-layer modules are built for one batch size, "
                                       "and a step has seq_batch items where a validation item has one")
+        if self.opt.gru == "v8":
+            # the ConvLSTM front-end chains its four scales inside a frame: one sequence per step, eager, on the fused loss
+            if self.seq_batch > 1:
+                raise NotImplementedError("gru 'v8' trains one sequence item per step: seq_batch > 1 (lockstep) covers 'v5' only")
+            if getattr(self.opt, "hip_graph", False):
+                raise NotImplementedError("gru 'v8' runs eagerly: hip_graph capture of the ConvLSTM step is not covered")
+            if not self.opt.fused_loss:
+                raise NotImplementedError("gru 'v8' runs the fused loss: the layer-by-layer loss (--fused_loss 0) is not covered")
         self.loss_batch = self.opt.batch_size * (self.opt.len_sequence * self.seq_batch if self.opt.gru else 1)
         self.num_scales = len(self.opt.scales)
         self.num_input_frames = len(self.opt.frame_ids)                                   # trainer.py:50-51
@@ -150,7 +160,11 @@ class Trainer:
         self.models["depth"] = networks.DepthDecoder(self.models["encoder"].num_ch_enc, self.opt.scales)
         if self.opt.fusion:                                      # trainer_fusion_v3.py:74
             self.models["fusion"] = networks.Fusion_v3(attention=not self.opt.disable_attention)
-        if self.opt.gru:                                         # trainer_gru.py:128
+        if self.opt.gru == "v8":                                 # trainer_gru.py:141-144
+            self.models["gru"] = networks.ConvGRUBlocks_v8(kernel_size=(3, 3), bias=True, device="cpu", attention=False,
+                                                           height=self.opt.height, width=self.opt.width,
+                                                           num_ch_dec=tuple(int(c) for c in self.models["depth"].num_ch_dec[:4]))
+        elif self.opt.gru:                                       # trainer_gru.py:128
             self.models["gru"] = networks.ConvGRUBlocks_v5(kernel_size=(3, 3), bias=True, device="cpu", height=self.opt.height,
                                                            width=self.opt.width,
                                                            num_ch_enc=tuple(int(c) for c in self.models["encoder"].num_ch_enc))
@@ -174,7 +188,8 @@ class Trainer:
             broadcast_parameters(self.models.values(), 0, process_group)
         # in the order the forward runs the modules (GradBuckets exchanges in the reverse of it): with overlap_streams
         # the pose branch is issued first (process_batch), so its gradients are the last ones backward produces
-        main = ["encoder"] + [k for k in ("gru",) if k in self.models] + ["depth"] + \
+        front = [k for k in ("gru",) if k in self.models]
+        main = ["encoder"] + (["depth"] + front if self.opt.gru == "v8" else front + ["depth"]) + \
             [k for k in ("fusion", "predictive_mask") if k in self.models]
         order = (["pose_encoder", "pose"] + main) if getattr(self.opt, "overlap_streams", False) else (main + ["pose_encoder", "pose"])
         order = [k for k in order if k in self.models] + [k for k in self.models if k not in order]
@@ -249,13 +264,16 @@ class Trainer:
     def freeze_hidden_states(self):
         """trainer_gru.py:295-307: from epoch `opt.h_s_epoch` on the learned initial hidden states of the ConvGRU cells stop
         training (`h0_layer1.requires_grad = False`; they stay in Adam's parameter list and simply receive no gradient any
-        more, as in the reference).  Captured hipGraphs recorded the old autograd graph and are dropped (re-captured after
+        more, as in the reference), and with them the initial cell states `c0_layer1` of the ConvLSTM cells of v8
+        (trainer_gru.py:303-307).  Captured hipGraphs recorded the old autograd graph and are dropped (re-captured after
         the usual warm-up)."""
         if "gru" not in self.models:
             return
         for cell in self.models["gru"].cells():
-            cell.h0_layer1.requires_grad = False
-            cell.h0_layer1.grad = None
+            for state in (cell.h0_layer1, getattr(cell, "c0_layer1", None)):
+                if state is not None:
+                    state.requires_grad = False
+                    state.grad = None
         self.reset_graphs()
 
     def start_epoch(self, epoch):
@@ -397,6 +415,13 @@ class Trainer:
             enc_input = torch.cat([inputs[("color_aug", i, 0)] for i in (-2, -1, 0)], 0)
             features = self.models["encoder"](enc_input)
             outputs = dict(self.models["fusion"](self.models["depth"](features)))
+        elif self.opt.gru == "v8":                               # trainer_gru.py:402-460, batch size 1
+            # encoder -> decoder (pre_disp: its feature maps; the dispconvs are not run and get no gradient) -> ConvLSTM blocks
+            features = self.models["encoder"](inputs[("color", 0, 0)])
+            if features[0].shape[0] != self.opt.len_sequence:
+                raise ValueError("a ConvLSTM batch is ONE sequence of len_sequence = %d frames, got %d rows"
+                                 % (self.opt.len_sequence, features[0].shape[0]))
+            outputs = dict(self.models["gru"].run_sequence(self.models["depth"](features, pre_disp=True)))
         elif self.opt.gru:                                       # trainer_gru.py:595-644, batch size 1
             features = self.models["encoder"](inputs[("color", 0, 0)])
             # the streams belong to the call: a step holds seq_batch items, a validation item (val_sequence) one
