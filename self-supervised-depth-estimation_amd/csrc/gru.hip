@@ -5,7 +5,8 @@
 //   rh      = r * h                      r = gates[:, :C]  (reset gate),  gates = sigmoid(conv_gates(cat(x, h)))
 //   h_next  = (1 - u) * h + u * cnm      u = gates[:, C:]  (update gate), cnm = tanh(conv_can(cat(x, r * h)))
 //   out[i]  = f[i] + (H[i+1] + H[i]) / 2     H = the n+1 hidden states of a sequence of n frames (trainer_gru.py:637-639)
-// Forward and backward, float4 where the plane size allows; memory-bound, one pass each.
+// Forward and backward, one float per thread and trip of a grid-stride loop (at most 4096 blocks of 256); memory-bound, one
+// pass each.  Only the segment copy (gather_copy_kernel) moves float4 where source and destination are 16-byte aligned.
 #include "dc_common.h"
 
 #include <algorithm>
@@ -21,7 +22,11 @@ __global__ __launch_bounds__(256) void gru_rh_fwd_kernel(const float* __restrict
         rh[i] = gates[b * 2 * C * P + r] * h[i];
     }
 }
-// d_gates[:, :C] = g * h (the update half is written by the blend backward), d_h = g * r
+// d_gates = [g * h | 0], d_h = g * r.
+// ACC: the accumulating form of the sequence backward (dc_gru_*_bwd_acc; _GruLevel walks the frames of a sequence backwards and
+// every step's gradient of h_i joins what the later steps and the residual already left in d_H[i]): d_h += g * r, and ONLY the
+// reset half of d_gates is written -- the blend backward of the same step wrote the update half.
+template <bool ACC>
 __global__ __launch_bounds__(256) void gru_rh_bwd_kernel(const float* __restrict__ gates, const float* __restrict__ h, const float* __restrict__ g,
                                                         float* __restrict__ d_gates, float* __restrict__ d_h, int B, int C, int P) {
     const size_t n = (size_t)B * C * P;
@@ -30,39 +35,12 @@ __global__ __launch_bounds__(256) void gru_rh_bwd_kernel(const float* __restrict
         const size_t gi = b * 2 * C * P + r;
         const float gv = g[i];
         d_gates[gi] = gv * h[i];
-        d_gates[gi + (size_t)C * P] = 0.f;
-        d_h[i] = gv * gates[gi];
-    }
-}
-// The accumulating forms of the sequence backward (dc_gru_*_bwd_acc; ops._GruLevel walks the frames of a sequence backwards and
-// every step's gradient of h_i joins what the later steps and the residual already left in d_H[i]):
-//   rh:    d_gates[:, :C] = g * h   (ONLY the reset half is written -- the blend backward of the same step wrote the update half),
-//          d_h += g * r
-__global__ __launch_bounds__(256) void gru_rh_bwd_acc_kernel(const float* __restrict__ gates, const float* __restrict__ h, const float* __restrict__ g,
-                                                            float* __restrict__ d_gates, float* __restrict__ d_h, int B, int C, int P) {
-    const size_t n = (size_t)B * C * P;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const size_t b = i / ((size_t)C * P), r = i - b * (size_t)C * P;
-        const size_t gi = b * 2 * C * P + r;
-        const float gv = g[i];
-        d_gates[gi] = gv * h[i];
-        d_h[i] += gv * gates[gi];
-    }
-}
-//   blend: d_gates = [0 | g * (cnm - h)], d_h += g * (1 - u), d_cnm = g * u
-__global__ __launch_bounds__(256) void gru_blend_bwd_acc_kernel(const float* __restrict__ gates, const float* __restrict__ h,
-                                                               const float* __restrict__ cnm, const float* __restrict__ g,
-                                                               float* __restrict__ d_gates, float* __restrict__ d_h, float* __restrict__ d_cnm,
-                                                               int B, int C, int P) {
-    const size_t n = (size_t)B * C * P;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const size_t b = i / ((size_t)C * P), r = i - b * (size_t)C * P;
-        const size_t gi = b * 2 * C * P + r;
-        const float u = gates[gi + (size_t)C * P], gv = g[i];
-        d_gates[gi] = 0.f;
-        d_gates[gi + (size_t)C * P] = gv * (cnm[i] - h[i]);
-        d_h[i] += gv * (1.f - u);
-        d_cnm[i] = gv * u;
+        if constexpr (ACC) {
+            d_h[i] += gv * gates[gi];
+        } else {
+            d_gates[gi + (size_t)C * P] = 0.f;
+            d_h[i] = gv * gates[gi];
+        }
     }
 }
 // The sequence trainer stacks the frames of one sequence along the batch at every use (trainer_gru.py:819-821, 886-896, 943-944:
@@ -97,7 +75,8 @@ __global__ __launch_bounds__(256) void gru_blend_fwd_kernel(const float* __restr
         out[i] = (1.f - u) * h[i] + u * cnm[i];          // rnn.py:141
     }
 }
-// d_gates[:, C:] = g * (cnm - h) (the reset half is zero here), d_h = g * (1 - u), d_cnm = g * u
+// d_gates = [0 | g * (cnm - h)], d_h = g * (1 - u), d_cnm = g * u.  ACC: d_h += g * (1 - u), the rest alike.
+template <bool ACC>
 __global__ __launch_bounds__(256) void gru_blend_bwd_kernel(const float* __restrict__ gates, const float* __restrict__ h,
                                                            const float* __restrict__ cnm, const float* __restrict__ g,
                                                            float* __restrict__ d_gates, float* __restrict__ d_h, float* __restrict__ d_cnm,
@@ -109,7 +88,11 @@ __global__ __launch_bounds__(256) void gru_blend_bwd_kernel(const float* __restr
         const float u = gates[gi + (size_t)C * P], gv = g[i];
         d_gates[gi] = 0.f;
         d_gates[gi + (size_t)C * P] = gv * (cnm[i] - h[i]);
-        d_h[i] = gv * (1.f - u);
+        if constexpr (ACC) {
+            d_h[i] += gv * (1.f - u);
+        } else {
+            d_h[i] = gv * (1.f - u);
+        }
         d_cnm[i] = gv * u;
     }
 }
@@ -142,7 +125,13 @@ __global__ __launch_bounds__(256) void gru_state_bwd_kernel(const float* __restr
     }
 }
 
-static inline int gru_grid(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 4096); }
+// Every element-wise entry point: `kernel` over n elements, 256 threads a block, at most 4096 blocks (the kernels stride).
+template <typename... P, typename... A>
+static int gru_launch(void (*kernel)(P...), size_t n, void* stream, A... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream, args...);
+    DC_CHECK_LAUNCH();
+    return DC_OK;
+}
 
 }  // namespace dc
 
@@ -152,67 +141,43 @@ static bool gru_ok(int B, int C, int P) { return B > 0 && C > 0 && P > 0 && (siz
 
 extern "C" int dc_gru_rh_fwd(const float* gates, const float* h, float* rh, int B, int C, int P, void* stream) {
     if (!gates || !h || !rh || !gru_ok(B, C, P)) return DC_EINVAL;
-    hipLaunchKernelGGL(gru_rh_fwd_kernel, dim3(gru_grid((size_t)B * C * P)), dim3(256), 0, (hipStream_t)stream, gates, h, rh, B, C, P);
-    DC_CHECK_LAUNCH();
-    return DC_OK;
+    return gru_launch(gru_rh_fwd_kernel, (size_t)B * C * P, stream, gates, h, rh, B, C, P);
 }
 extern "C" int dc_gru_rh_bwd(const float* gates, const float* h, const float* g, float* d_gates, float* d_h, int B, int C, int P,
                              void* stream) {
     if (!gates || !h || !g || !d_gates || !d_h || !gru_ok(B, C, P)) return DC_EINVAL;
-    hipLaunchKernelGGL(gru_rh_bwd_kernel, dim3(gru_grid((size_t)B * C * P)), dim3(256), 0, (hipStream_t)stream, gates, h, g, d_gates, d_h,
-                       B, C, P);
-    DC_CHECK_LAUNCH();
-    return DC_OK;
+    return gru_launch(gru_rh_bwd_kernel<false>, (size_t)B * C * P, stream, gates, h, g, d_gates, d_h, B, C, P);
+}
+extern "C" int dc_gru_rh_bwd_acc(const float* gates, const float* h, const float* g, float* d_gates, float* d_h, int B, int C, int P,
+                                 void* stream) {
+    if (!gates || !h || !g || !d_gates || !d_h || !gru_ok(B, C, P)) return DC_EINVAL;
+    return gru_launch(gru_rh_bwd_kernel<true>, (size_t)B * C * P, stream, gates, h, g, d_gates, d_h, B, C, P);
 }
 extern "C" int dc_gru_blend_fwd(const float* gates, const float* h, const float* cnm, float* h_next, int B, int C, int P, void* stream) {
     if (!gates || !h || !cnm || !h_next || !gru_ok(B, C, P)) return DC_EINVAL;
-    hipLaunchKernelGGL(gru_blend_fwd_kernel, dim3(gru_grid((size_t)B * C * P)), dim3(256), 0, (hipStream_t)stream, gates, h, cnm, h_next,
-                       B, C, P);
-    DC_CHECK_LAUNCH();
-    return DC_OK;
+    return gru_launch(gru_blend_fwd_kernel, (size_t)B * C * P, stream, gates, h, cnm, h_next, B, C, P);
 }
 extern "C" int dc_gru_blend_bwd(const float* gates, const float* h, const float* cnm, const float* g, float* d_gates, float* d_h,
                                 float* d_cnm, int B, int C, int P, void* stream) {
     if (!gates || !h || !cnm || !g || !d_gates || !d_h || !d_cnm || !gru_ok(B, C, P)) return DC_EINVAL;
-    hipLaunchKernelGGL(gru_blend_bwd_kernel, dim3(gru_grid((size_t)B * C * P)), dim3(256), 0, (hipStream_t)stream, gates, h, cnm, g,
-                       d_gates, d_h, d_cnm, B, C, P);
-    DC_CHECK_LAUNCH();
-    return DC_OK;
-}
-extern "C" int dc_gru_residual_fwd(const float* f, const float* H, float* out, int n, size_t M, void* stream) {
-    if (!f || !H || !out || n <= 0 || M == 0) return DC_EINVAL;
-    hipLaunchKernelGGL(gru_residual_fwd_kernel, dim3(gru_grid((size_t)n * M)), dim3(256), 0, (hipStream_t)stream, f, H, out, n, M);
-    DC_CHECK_LAUNCH();
-    return DC_OK;
-}
-extern "C" int dc_gru_residual_bwd(const float* g, float* d_H, int n, size_t M, void* stream) {
-    if (!g || !d_H || n <= 0 || M == 0) return DC_EINVAL;
-    hipLaunchKernelGGL(gru_residual_bwd_kernel, dim3(gru_grid((size_t)(n + 1) * M)), dim3(256), 0, (hipStream_t)stream, g, d_H, n, M);
-    DC_CHECK_LAUNCH();
-    return DC_OK;
-}
-extern "C" int dc_gru_state_bwd(const float* d_H, float* d_h0, int S, size_t M, void* stream) {
-    if (!d_H || !d_h0 || S <= 0 || M == 0 || M > (1ull << 40) / (size_t)S) return DC_EINVAL;
-    hipLaunchKernelGGL(gru_state_bwd_kernel, dim3(gru_grid(M)), dim3(256), 0, (hipStream_t)stream, d_H, d_h0, S, M);
-    DC_CHECK_LAUNCH();
-    return DC_OK;
-}
-
-extern "C" int dc_gru_rh_bwd_acc(const float* gates, const float* h, const float* g, float* d_gates, float* d_h, int B, int C, int P,
-                                 void* stream) {
-    if (!gates || !h || !g || !d_gates || !d_h || !gru_ok(B, C, P)) return DC_EINVAL;
-    hipLaunchKernelGGL(gru_rh_bwd_acc_kernel, dim3(gru_grid((size_t)B * C * P)), dim3(256), 0, (hipStream_t)stream, gates, h, g, d_gates,
-                       d_h, B, C, P);
-    DC_CHECK_LAUNCH();
-    return DC_OK;
+    return gru_launch(gru_blend_bwd_kernel<false>, (size_t)B * C * P, stream, gates, h, cnm, g, d_gates, d_h, d_cnm, B, C, P);
 }
 extern "C" int dc_gru_blend_bwd_acc(const float* gates, const float* h, const float* cnm, const float* g, float* d_gates, float* d_h,
                                     float* d_cnm, int B, int C, int P, void* stream) {
     if (!gates || !h || !cnm || !g || !d_gates || !d_h || !d_cnm || !gru_ok(B, C, P)) return DC_EINVAL;
-    hipLaunchKernelGGL(gru_blend_bwd_acc_kernel, dim3(gru_grid((size_t)B * C * P)), dim3(256), 0, (hipStream_t)stream, gates, h, cnm, g,
-                       d_gates, d_h, d_cnm, B, C, P);
-    DC_CHECK_LAUNCH();
-    return DC_OK;
+    return gru_launch(gru_blend_bwd_kernel<true>, (size_t)B * C * P, stream, gates, h, cnm, g, d_gates, d_h, d_cnm, B, C, P);
+}
+extern "C" int dc_gru_residual_fwd(const float* f, const float* H, float* out, int n, size_t M, void* stream) {
+    if (!f || !H || !out || n <= 0 || M == 0) return DC_EINVAL;
+    return gru_launch(gru_residual_fwd_kernel, (size_t)n * M, stream, f, H, out, n, M);
+}
+extern "C" int dc_gru_residual_bwd(const float* g, float* d_H, int n, size_t M, void* stream) {
+    if (!g || !d_H || n <= 0 || M == 0) return DC_EINVAL;
+    return gru_launch(gru_residual_bwd_kernel, (size_t)(n + 1) * M, stream, g, d_H, n, M);
+}
+extern "C" int dc_gru_state_bwd(const float* d_H, float* d_h0, int S, size_t M, void* stream) {
+    if (!d_H || !d_h0 || S <= 0 || M == 0 || M > (1ull << 40) / (size_t)S) return DC_EINVAL;
+    return gru_launch(gru_state_bwd_kernel, M, stream, d_H, d_h0, S, M);
 }
 
 extern "C" int dc_gather_copy(const float* const* src, float* const* dst, const size_t* n, int nseg, void* stream) {

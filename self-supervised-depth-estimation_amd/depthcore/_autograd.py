@@ -1,8 +1,9 @@
 """Autograd plumbing shared by every binding module: decision observers, the matrix-core precision policy, gradient
 destinations, weight-gradient lanes and the gradient joins of tensors with several consumers (GradFork, SkipSum).
 
-The lowest layer above `_lib`: `convnode`, `ops` and `bnfold` import it, it imports none of them.  `ops` re-exports every
-name, so each piece of mutable state (`_precision`, the observer list, the WgradLanes class attributes) is one object.
+The lowest layer above `_lib`: `convnode`, the binding modules behind `ops` (photo, layer_ops, convs, eval_ops, attention,
+recurrent) and `bnfold` import it, it imports none of them.  `ops` re-exports every name, so each piece of mutable state
+(`_precision`, the observer list, the WgradLanes class attributes) is one object.
 """
 import collections
 import contextlib
@@ -93,6 +94,12 @@ def _grad_dst(slot, like):
     if slot is not None and slot.armed:
         return slot.take()
     return torch.empty_like(like) if like is not None else None
+
+
+def _bias_grad_dst(slot, n, device):
+    """backward(): where the gradient of a bias of `n` values is written -- the armed bucket slice, else a fresh (n,) tensor."""
+    gb = _grad_dst(slot, None)
+    return gb if gb is not None else torch.empty(n, dtype=torch.float32, device=device)
 
 
 # ---- weight gradients off the backward's critical path ----------------------------------------------------------------------

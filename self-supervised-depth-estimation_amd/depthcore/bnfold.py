@@ -13,7 +13,7 @@ layer (statistics, apply, backward statistics, backward apply).  Here:
     (`BNLink`) that convolution's data-gradient epilogue -- which already adds the skip's gradient -- does the masking and the
     backward partials, so the backward is one pass as well.
 
-Same arithmetic as depthcore.ops.bn_relu up to the order of the sums; deterministic.  No fallback: CPU tensors raise.
+Same arithmetic as depthcore.convs.bn_relu (`ops.bn_relu`) up to the order of the sums; deterministic.  No fallback: CPU tensors raise.
 """
 import torch
 

@@ -3,7 +3,7 @@
 
 One backward protocol for a convolution whose input has other consumers -- GradFork arrive / take / park, SkipSum arm / take,
 the addend checks, the weight gradient on a WgradLanes lane -- with or without a BatchNorm folded in (dc_bn_fold, see
-bnfold.py).  `ops` holds the plain wrappers (wino_conv3x3, conv1x1, conv_s2), `bnfold` the folded ones.
+bnfold.py).  `convs` holds the plain wrappers (wino_conv3x3, conv1x1, conv_s2; `ops` re-exports them), `bnfold` the folded ones.
 """
 import ctypes
 
@@ -221,7 +221,7 @@ _KINDS = {"g1": _K1, "wino": _KW, "s2": _KS}
 # consumers and, with a fold, carries the BatchNorm-backward epilogue
 # ----------------------------------------------------------------------------------------------
 class _ConvF(torch.autograd.Function):
-    """`groups` None: no dc_bn_fold reaches the library (the plain wrappers in ops.py); an int: every launch gets one with
+    """`groups` None: no dc_bn_fold reaches the library (the plain wrappers in convs.py); an int: every launch gets one with
     `groups` set (bnfold.py), `cfg` then carries in_stats / bn / prev / want_stats and receives out_stats."""
     @staticmethod
     def forward(ctx, x, weight, kind, stride, fork=None, skip=None, groups=None, cfg=None, gamma=None, beta=None):

@@ -64,6 +64,82 @@ def test_gate_kernels_vs_torch():
         close(a, b, rtol=1e-6, atol=1e-7)
 
 
+# (B, C, P) of the gate-backward entry points called directly: an odd plane with the batch row boundary inside a block; and
+# 1,048,578 elements, two more than the 4096 x 256 threads of the capped grid -- the stride loop's second trip, for two threads
+GATE_SHAPES = [(2, 5, 63), (3, 2, 174763)]
+_gate_cases = {}
+
+
+def _gate_case(shape):
+    """Seeded inputs of the gate backwards on the device and as fp64 on the host, made once per shape and only read."""
+    if shape not in _gate_cases:
+        B, C, P = shape
+        g = torch.Generator().manual_seed(17)
+        host = {"gates": torch.rand(B, 2 * C, P, generator=g)}
+        for k in ("h", "cnm", "g", "prior"):
+            host[k] = torch.randn(B, C, P, generator=g)
+        _gate_cases[shape] = ({k: v.to(DEV) for k, v in host.items()}, {k: v.double() for k, v in host.items()})
+    return _gate_cases[shape]
+
+
+def _gate_call(name, d, *tensors):
+    from depthcore import _lib
+    from depthcore.ops import ptr
+    B, C, P = d["h"].shape
+    rc = getattr(_lib.lib(), name)(*[ptr(t) for t in tensors], B, C, P, _lib.stream(d["h"]))
+    assert rc == 0, (name, rc)
+
+
+@pytest.mark.parametrize("shape", GATE_SHAPES)
+def test_rh_bwd_acc_adds_and_leaves_the_update_half(shape):
+    """dc_gru_rh_bwd_acc: d_h = prior + g * r, d_gates[:, :C] = g * h, and the update half keeps every bit it held."""
+    d, ref = _gate_case(shape)
+    C = shape[1]
+    d_h = d["prior"].clone()
+    d_gates = torch.full_like(d["gates"], -7.25)
+    _gate_call("dc_gru_rh_bwd_acc", d, d["gates"], d["h"], d["g"], d_gates, d_h)
+    close(d_h, ref["prior"] + ref["g"] * ref["gates"][:, :C], rtol=1e-5, atol=1e-6)
+    close(d_gates[:, :C], ref["g"] * ref["h"], rtol=1e-5, atol=1e-6)
+    assert torch.equal(d_gates[:, C:], torch.full_like(d_gates[:, C:], -7.25))
+
+
+@pytest.mark.parametrize("shape", GATE_SHAPES)
+def test_blend_bwd_acc_adds_and_zeroes_the_reset_half(shape):
+    """dc_gru_blend_bwd_acc: d_gates = [0 | g * (cnm - h)], d_h = prior + g * (1 - u), d_cnm = g * u."""
+    d, ref = _gate_case(shape)
+    C = shape[1]
+    u = ref["gates"][:, C:]
+    d_h = d["prior"].clone()
+    d_gates = torch.full_like(d["gates"], float("nan"))
+    d_cnm = torch.full_like(d["h"], float("nan"))
+    _gate_call("dc_gru_blend_bwd_acc", d, d["gates"], d["h"], d["cnm"], d["g"], d_gates, d_h, d_cnm)
+    assert torch.equal(d_gates[:, :C], torch.zeros_like(d_gates[:, :C]))
+    close(d_gates[:, C:], ref["g"] * (ref["cnm"] - ref["h"]), rtol=1e-5, atol=1e-6)
+    close(d_h, ref["prior"] + ref["g"] * (1 - u), rtol=1e-5, atol=1e-6)
+    close(d_cnm, ref["g"] * u, rtol=1e-5, atol=1e-6)
+
+
+@pytest.mark.parametrize("shape", GATE_SHAPES)
+def test_plain_gate_backwards_overwrite_every_element(shape):
+    """dc_gru_rh_bwd / dc_gru_blend_bwd into NaN-filled outputs: every element is written, the half of d_gates that the op has
+    no gradient for is exactly 0, and nothing of what d_h held before remains."""
+    d, ref = _gate_case(shape)
+    C = shape[1]
+    u = ref["gates"][:, C:]
+    nan = float("nan")
+    d_gates, d_h = torch.full_like(d["gates"], nan), torch.full_like(d["h"], nan)
+    _gate_call("dc_gru_rh_bwd", d, d["gates"], d["h"], d["g"], d_gates, d_h)
+    assert torch.equal(d_gates[:, C:], torch.zeros_like(d_gates[:, C:]))
+    close(d_gates[:, :C], ref["g"] * ref["h"], rtol=1e-5, atol=1e-6)
+    close(d_h, ref["g"] * ref["gates"][:, :C], rtol=1e-5, atol=1e-6)
+    d_gates, d_h, d_cnm = torch.full_like(d["gates"], nan), torch.full_like(d["h"], nan), torch.full_like(d["h"], nan)
+    _gate_call("dc_gru_blend_bwd", d, d["gates"], d["h"], d["cnm"], d["g"], d_gates, d_h, d_cnm)
+    assert torch.equal(d_gates[:, :C], torch.zeros_like(d_gates[:, :C]))
+    close(d_gates[:, C:], ref["g"] * (ref["cnm"] - ref["h"]), rtol=1e-5, atol=1e-6)
+    close(d_h, ref["g"] * (1 - u), rtol=1e-5, atol=1e-6)
+    close(d_cnm, ref["g"] * u, rtol=1e-5, atol=1e-6)
+
+
 def test_blocks_v5_sequence_vs_reference_fixture(golden):
     """ConvGRUBlocks_v5 over a 2-frame sequence at the reference's hard-coded 192x640 feature sizes, with the hidden-state
     aggregation of trainer_gru.py:607-639: outputs and every gradient (features, weights, learned initial states)."""
