@@ -333,7 +333,9 @@ int dc_bn_relu_bwd(const float* x, const float* y, const float* gy, const float*
  *             -> dc_bn_bwd_apply: dx = a*g' + b*(x - mean) + c0;   conv B's weight gradient re-forms relu(scale*x + shift)
  *             in its loader.
  * Partials: float2 part[channel][p], p < nparts; partial p covers pixels of one BatchNorm group, group(p) = min(p / ppg,
- * groups - 1) (the *_parts queries return nparts and ppg, 0 = this shape has no epilogue: use dc_bn_stats / dc_bn_relu_bwd).
+ * groups - 1) (the *_parts queries return nparts and ppg, 0 = this shape has no epilogue: use dc_bn_stats / dc_bn_relu_bwd;
+ * a positive nparts always comes with ppg >= 1 and (groups - 1) * ppg < nparts -- what dc_bn_finalize / dc_bn_bwd_finalize require --
+ * also where one group's whole batch is smaller than the pixels one partial covers).
  * Everything is summed in a fixed order: deterministic.  Arithmetic = dc_bn_relu_fwd / _bwd up to the order of the sums. */
 typedef struct dc_bn_fold {
     int groups;                 /* BatchNorm groups of the batch (dc_bn_relu_fwd); image b belongs to group b / (B / groups) */

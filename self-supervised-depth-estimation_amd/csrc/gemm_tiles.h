@@ -87,13 +87,15 @@ __device__ __forceinline__ void mma_chunk32(RA&& ra, RB&& rb, gf4 (&acc)[MT][NT]
 
 // Partials per channel of the forward's statistics epilogue / the data gradient's BatchNorm epilogue on a grid of (32 tile_nt)-column
 // tiles over B images of P pixels (0: not with this group layout): one per wave column of 16 tile_nt pixels; a group boundary must
-// not fall inside one.  Each kernel family passes its own tile pick.  ppg (nullable): partials per group.
+// not fall inside one.  Each kernel family passes its own tile pick.  ppg (nullable): partials per group, >= 1 whenever the count
+// is positive -- one group owns every partial (group(p) = min(p / ppg, groups - 1) = 0), also where the whole batch is smaller
+// than one wave column (B P < cover: a layer4 map of 2 x 4 at B <= 3); several groups hold whole wave columns each.
 inline int gemm_parts(int tile_nt, int B, int P, int groups, int* ppg) {
     if (groups < 1 || B % groups) return 0;
     const int N = B * P;
     const int cover = 16 * tile_nt;
     if (groups > 1 && (N / groups) % cover) return 0;
-    if (ppg) *ppg = (N / groups) / cover;
+    if (ppg) *ppg = (N / groups) / cover > 0 ? (N / groups) / cover : 1;
     return ceil_div(N, 32 * tile_nt) * 2;
 }
 

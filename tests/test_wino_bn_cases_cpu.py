@@ -101,35 +101,7 @@ def test_region_transcription_on_the_trunk_maps():
 
 @pytest.mark.parametrize("case", WC.params(WC.CASES))
 def test_case_is_well_conditioned(case):
-    inp, r64, r32 = WC.reference(case)
-    name = WC.TENSORS[case.kind]
-    for k, v in r64.items():
-        assert bool(torch.isfinite(v.double()).all()) and bool(torch.isfinite(r32[k].double()).all()), k
-    e32 = WC.rel_err(r32[name], r64[name])
-    assert e32 < WC.E32_MAX, e32
-    assert float(r64[name].abs().max()) > 0.1
-    pre = WC.decision_preact(case, inp)
-    if pre is None:
-        return
-    # the decision margin: nothing within MARGIN of zero but the planted ties, which are exactly zero
-    ties = WC.tie_mask(case, pre.shape[1])
-    assert int(ties.sum()) >= (2 if case.H * case.W > 1 else 1)
-    assert bool((pre[ties] == 0).all())
-    assert bool((pre[~ties].abs() >= WC.MARGIN).all()), float(pre[~ties].abs().min())
-    # a tie is "off": torch's ReLU and the kernels' `> 0` agree, in both precisions
-    pre32 = WC.preact(case, *[inp[k] for k in (("bn_x", "s", "t", "res") if case.kind == "dgrad" else ("x", "s", "t"))]).float()
-    assert bool((pre32[ties] == 0).all()) and not bool((pre32[ties] > 0).any()) and bool((torch.relu(pre32[ties]) == 0).all())
-    if case.kind == "dgrad":
-        for r in (r64, r32):
-            assert not bool(r["keep"][ties].any()) and bool((r["gx"][ties] == 0).all())
-        assert bool((r64["keep"] == r32["keep"]).all())
-        assert 0.2 < float(r64["keep"].double().mean()) < 0.8
-        # the tie matters: the unmasked gradient there is not zero, so `>=` for `>` would show
-        assert float(r64["r"][ties].abs().min()) > 1e-3 * float(r64["gx"].abs().max())
-    if case.kind == "dgrad" and case.mode == 3:
-        assert bool((inp["res"][ties] == 0).all())
-        # the residual takes part in the decision: it differs from the decision without it somewhere
-        assert bool(((WC.preact(case, inp["bn_x"], inp["s"], inp["t"]) > 0) != r64["keep"]).any())
+    WC.assert_well_conditioned(case, *WC.reference(case))
 
 
 # ---- refusals: host-side, DC_EINVAL before anything is launched -------------------------------------------------------------------

@@ -284,12 +284,13 @@ def tie_mask(c, C):
     return m
 
 
-def build(c):
-    """fp32 inputs of one case (a dict of CPU tensors; absent operands are None)."""
+def build(c, ksize=3, tag="wino_bn"):
+    """fp32 inputs of one case (a dict of CPU tensors; absent operands are None).  ksize, tag: the kernel size and the seed's name
+    (tests/pointwise_bn_cases.py builds the 1x1 cases with the same builder)."""
     B, Ci, Co, H, W = c.B, c.Ci, c.Co, c.H, c.W
-    g = torch.Generator().manual_seed(zlib.crc32(repr(("wino_bn", tuple(c))).encode()))
+    g = torch.Generator().manual_seed(zlib.crc32(repr((tag, tuple(c))).encode()))
     rn = lambda *shape: torch.randn(*shape, generator=g)
-    inp = {"w": rn(Co, Ci, 3, 3) * (2.0 / (9 * Ci)) ** 0.5, "x": None, "gy": None, "s": None, "t": None, "bn_x": None,
+    inp = {"w": rn(Co, Ci, ksize, ksize) * (2.0 / (ksize * ksize * Ci)) ** 0.5, "x": None, "gy": None, "s": None, "t": None, "bn_x": None,
            "mean": None, "res": None, "addend": None}
     if c.kind in ("fwd", "wgrad"):
         inp["x"] = rn(B, Ci, H, W)
@@ -322,8 +323,8 @@ def _per_group(c, per_img):
     return per_img.view(c.groups, c.B // c.groups, -1).sum(1)
 
 
-def evaluate(c, inp, dt):
-    """{name: tensor} of the statement in `dt`."""
+def evaluate(c, inp, dt, padding=1):
+    """{name: tensor} of the statement in `dt` (padding = 1: the 3x3 convolution; 0 with 1x1 weights: tests/pointwise_bn_cases.py)."""
     to = lambda k: None if inp[k] is None else inp[k].to(dt)
     gi = _group_of(c)
     w = to("w")
@@ -333,11 +334,11 @@ def evaluate(c, inp, dt):
         if c.loader:
             a = F.relu(bc(to("s")) * a + bc(to("t")))
         if c.kind == "wgrad":
-            return {"dW": torch.nn.grad.conv2d_weight(a, w.shape, to("gy"), padding=1)}
-        y = F.conv2d(a, w, padding=1)
+            return {"dW": torch.nn.grad.conv2d_weight(a, w.shape, to("gy"), padding=padding)}
+        y = F.conv2d(a, w, padding=padding)
         s_img, q_img = y.sum((2, 3)), (y * y).sum((2, 3))
         return {"y": y, "S_img": s_img, "Q_img": q_img, "S": _per_group(c, s_img), "Q": _per_group(c, q_img)}
-    r = torch.nn.grad.conv2d_input((c.B, c.Ci, c.H, c.W), w, to("gy"), padding=1)
+    r = torch.nn.grad.conv2d_input((c.B, c.Ci, c.H, c.W), w, to("gy"), padding=padding)
     if c.addend:
         r = r + to("addend")
     bx = to("bn_x")
@@ -359,6 +360,40 @@ def reference(c):
 
 rel_err = LC.rel_err
 TENSORS = {"fwd": "y", "dgrad": "gx", "wgrad": "dW"}
+
+
+def assert_well_conditioned(case, inp, r64, r32):
+    """The case is fit to judge a kernel with: finite, torch's fp32 evaluation of the statement within E32_MAX of fp64, no ReLU
+    decision a rounding question (MARGIN), the planted ties exactly zero and "off" in both precisions.  (Shared with
+    tests/test_pointwise_bn_cases_cpu.py.)"""
+    name = TENSORS[case.kind]
+    for k, v in r64.items():
+        assert bool(torch.isfinite(v.double()).all()) and bool(torch.isfinite(r32[k].double()).all()), k
+    e32 = rel_err(r32[name], r64[name])
+    assert e32 < E32_MAX, e32
+    assert float(r64[name].abs().max()) > 0.1
+    pre = decision_preact(case, inp)
+    if pre is None:
+        return
+    # the decision margin: nothing within MARGIN of zero but the planted ties, which are exactly zero
+    ties = tie_mask(case, pre.shape[1])
+    assert int(ties.sum()) >= (2 if case.H * case.W > 1 else 1)
+    assert bool((pre[ties] == 0).all())
+    assert bool((pre[~ties].abs() >= MARGIN).all()), float(pre[~ties].abs().min())
+    # a tie is "off": torch's ReLU and the kernels' `> 0` agree, in both precisions
+    pre32 = preact(case, *[inp[k] for k in (("bn_x", "s", "t", "res") if case.kind == "dgrad" else ("x", "s", "t"))]).float()
+    assert bool((pre32[ties] == 0).all()) and not bool((pre32[ties] > 0).any()) and bool((torch.relu(pre32[ties]) == 0).all())
+    if case.kind == "dgrad":
+        for r in (r64, r32):
+            assert not bool(r["keep"][ties].any()) and bool((r["gx"][ties] == 0).all())
+        assert bool((r64["keep"] == r32["keep"]).all())
+        assert 0.2 < float(r64["keep"].double().mean()) < 0.8
+        # the tie matters: the unmasked gradient there is not zero, so `>=` for `>` would show
+        assert float(r64["r"][ties].abs().min()) > 1e-3 * float(r64["gx"].abs().max())
+    if case.kind == "dgrad" and case.mode == 3:
+        assert bool((inp["res"][ties] == 0).all())
+        # the residual takes part in the decision: it differs from the decision without it somewhere
+        assert bool(((preact(case, inp["bn_x"], inp["s"], inp["t"]) > 0) != r64["keep"]).any())
 
 
 # ---- the gates --------------------------------------------------------------------------------------------------------------------
