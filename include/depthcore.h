@@ -799,6 +799,24 @@ int dc_lstm_handover_fwd(const float* a, const float* h_prev, const float* h_new
                          int B, int C, int h, int w, void* stream);
 int dc_lstm_handover_bwd(const float* pre, const float* g_pre, const float* g_up, float* d_a, float* d_h_prev, float* d_h_new,
                          int B, int C, int h, int w, void* stream);
+/* Inference form of a v8 frame at one scale for B independent streams (evaluate_depth_gru_fusion.py:557-618 `evaluate_v8_seq`
+ * over networks/rnn.py:70-79, 767-773, 783-791; run for several windows in lockstep: depthcore.evaluate.WindowPredictor), ONE
+ * launch for dc_lstm_cell_fwd + the `+ r` of ResidualConvUnit (networks/fusion_v2.py:11-43) + dc_lstm_handover_fwd:
+ *   c' = sigmoid(f) * c + sigmoid(i) * tanh(g),  h' = sigmoid(o) * tanh(c')
+ *   pre = relu((y + r) + (h + h') / 2),  up = PixelShuffle(2)(tanh(pre)),  h <- h',  c <- c'
+ * cc (B, 4C, hh, w) = [i | f | o | g], the raw output of the cell's convolution.  h, c: the first B rows of state buffers of at
+ * least B rows of C * hh * w floats, REWRITTEN IN PLACE (each element by the thread that read it); rows behind B are not
+ * touched.  y, r (B, C, hh, w), both given or both NULL: resConfUnit1.conv2's output and the unit's ReLU-ed input; with them
+ * NULL the call is the state update alone (scale 0 on every frame but a window's last).  pre (B, C, hh, w) or NULL.  up NULL,
+ * or element (b, q, 2y + i, 2x + j) lives at up + b * up_bstride + (q * 2hh + 2y + i) * 2w + 2x + j: up_bstride >= C * hh * w
+ * lets the launch write straight into the upper channel half of the next finer scale's cat(dec, up) buffer.  Apart from h and
+ * c being their own outputs nothing may alias.  float4 form (dc_lstm_handover_fwd's item) where C % 4 == 0, w % 4 == 0, every
+ * base is 16-byte aligned and up_bstride % 4 == 0; scalar otherwise.  The accurate expf / tanhf of the training forms; no
+ * atomics, two calls give the same bits; capturable.  DC_EINVAL before any launch: B, C, hh or w <= 0; cc, h or c NULL; exactly
+ * one of y / r NULL; pre or up without y; up with C % 4 != 0 or up_bstride < C * hh * w; a tensor of 2^31 elements or more
+ * (cc counts 4 * B * C * hh * w). */
+int dc_lstm_infer_step(const float* cc, const float* y, const float* r, float* h, float* c, float* pre, float* up,
+                       size_t up_bstride, int B, int C, int hh, int w, void* stream);
 
 /* ------------------------------------------------------------------ transformed-weight cache of the Winograd kernels */
 /* ------------------------------------------------------------------ reduced-precision networks (BASELINE configs[4]) */

@@ -7,24 +7,10 @@
 // the forward read or wrote: nothing but cc and c_cur (cell) and pre (hand-over) is kept per frame.  Every thread owns the
 // elements it writes: no atomics, two runs give the same bits.  sigmoid and tanh are the accurate expf / tanhf (not __expf):
 // the states are carried over the frames of a sequence.
-#include "dc_common.h"
-
-#include <algorithm>
-#include <initializer_list>
+#include "lstm_dev.h"            // lstm_sigmoid, lstm_fwd1, handover_pre, LSTM_BLOCK, lstm_grid, all16: shared with lstm_infer.hip
 
 namespace dc {
 
-constexpr int LSTM_BLOCK = 256;     // threads per block; a float4 body block covers 1024 floats of a batch item
-
-__device__ __forceinline__ float lstm_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
-
-struct LstmFwd { float h, c; };
-__device__ __forceinline__ LstmFwd lstm_fwd1(float ci, float cf, float co, float cg, float c) {
-    LstmFwd r;
-    r.c = lstm_sigmoid(cf) * c + lstm_sigmoid(ci) * tanhf(cg);          // rnn.py:71-76
-    r.h = lstm_sigmoid(co) * tanhf(r.c);                                // rnn.py:77
-    return r;
-}
 struct LstmBwd { float di, df, dO, dg, dc; };
 __device__ __forceinline__ LstmBwd lstm_bwd1(float ci, float cf, float co, float cg, float c, float gh, float gc) {
     const float i = lstm_sigmoid(ci), f = lstm_sigmoid(cf), o = lstm_sigmoid(co), g = tanhf(cg);
@@ -116,8 +102,7 @@ __global__ __launch_bounds__(LSTM_BLOCK) void lstm_cell_bwd_kernel(const float* 
 }
 
 // ---- coarse-to-fine hand-over ---------------------------------------------------------------------------------------------
-// PixelShuffle(2): up[b, q, 2y + i, 2x + j] = tanh(pre[b, 4q + 2i + j, y, x]).
-__device__ __forceinline__ float handover_pre(float a, float hp, float hn) { return fmaxf(a + (hp + hn) * 0.5f, 0.f); }
+// PixelShuffle(2): up[b, q, 2y + i, 2x + j] = tanh(pre[b, 4q + 2i + j, y, x])   (handover_pre: lstm_dev.h)
 // d(pre pre-ReLU) from the two consumers of pre: the ReLU's mask, the tanh recomputed from pre
 __device__ __forceinline__ float handover_d(float pre, float gp, float gu) {
     const float t = tanhf(pre);
@@ -224,8 +209,6 @@ __global__ __launch_bounds__(LSTM_BLOCK) void lstm_handover_bwd_kernel(const flo
     }
 }
 
-static inline unsigned lstm_grid(size_t work) { return (unsigned)std::min<size_t>((work + LSTM_BLOCK - 1) / LSTM_BLOCK, 4096); }
-
 }  // namespace dc
 
 using namespace dc;
@@ -258,11 +241,6 @@ extern "C" int dc_lstm_cell_bwd(const float* cc, const float* c_cur, const float
 
 static bool handover_ok(int B, int C, int h, int w) {
     return B > 0 && C > 0 && (C & 3) == 0 && h > 0 && w > 0 && (size_t)B * C * h * w < (1ull << 31);
-}
-static bool all16(std::initializer_list<const void*> ps) {
-    for (const void* p : ps)
-        if ((size_t)p & 15) return false;
-    return true;
 }
 
 extern "C" int dc_lstm_handover_fwd(const float* a, const float* h_prev, const float* h_new, float* pre, float* up, int B, int C, int h,

@@ -266,6 +266,7 @@ def _sig(lib):
         "dc_lstm_cell_bwd": (i, [p, p, p, p, p, p, i, i, i, p]),
         "dc_lstm_handover_fwd": (i, [p, p, p, p, p, i, i, i, i, p]),
         "dc_lstm_handover_bwd": (i, [p, p, p, p, p, p, i, i, i, i, p]),
+        "dc_lstm_infer_step": (i, [p, p, p, p, p, p, p, z, i, i, i, i, p]),
         "dc_set_matrix_precision": (i, [i]),
         "dc_get_matrix_precision": (i, []),
         "dc_clear_error": (i, []),

@@ -465,6 +465,211 @@ def predict_disparities_sequences(encoder, gru, decoder, scenes, min_depth=0.1, 
     return predict_disparities_lockstep(encoder, gru, decoder, lengths, batch, min_depth, max_depth, streams)
 
 
+# ---- ConvLSTM v8 (evaluate_depth_gru_fusion.py:557-618 `evaluate_v8_seq`): every test file is a window of its own -------------
+def window_groups(lengths, streams):
+    """The right-aligned counterpart of lockstep_groups, for windows that END at the frame that is scored: -> [(ids, widths)].
+    `ids` as there (sorted by length, descending and stable, over ALL windows, then cut into consecutive groups of up to
+    `streams`).  A group whose longest window has L frames takes L steps; the windows alive at step j are those with
+    length >= L - j -- a GROWING prefix of ids, widths[j] of them -- and window c shows its frame j - (L - lengths[c]).  All
+    windows of a group reach their last frame together at step L - 1, so the head runs once per group, at full width."""
+    if streams <= 0:
+        raise ValueError("streams must be positive")
+    if any(n <= 0 for n in lengths):
+        raise ValueError("every window needs at least one frame")
+    order = sorted(range(len(lengths)), key=lambda i: -lengths[i])
+    groups = []
+    for g0 in range(0, len(order), streams):
+        ids = order[g0:g0 + streams]
+        L = lengths[ids[0]]
+        groups.append((ids, [sum(1 for i in ids if lengths[i] >= L - j) for j in range(L)]))
+    return groups
+
+
+class WindowPredictor:
+    """Streaming inference of the ConvLSTM v8 front-end for up to `streams` independent windows that advance together
+    (evaluate_depth_gru_fusion.py:595-607 is one stream).  The recurrence reads, per frame and scale, only the LSTM convolution,
+    resConfUnit1 and the hand-over; resConfUnit2, the conv3x3 head and the sigmoid feed nothing but the disparity, which is
+    wanted at scale 0 of a window's last frame.  So `advance(frames)` runs no head at all (and at scale 0 just the state
+    update), and `step(frames)` adds scale 0's resConfUnit1, resConfUnit2 and head and returns the scaled disparities.
+
+    Per scale 3, 2, 1 of a frame at batch B: the decoder map copied into the lower channel half of the scale's cat(dec, up)
+    buffer and the buffer's ReLU (stock tensor ops); the LSTM convolution over (x_s, h[:B]) and resConfUnit1's two convolutions
+    (dc_conv3x3_fwd); ONE dc_lstm_infer_step, which rewrites (h, c)[:B] in place and writes up_s into the upper channel half of
+    scale s - 1's buffer.  Scale 0 of `advance`: the copy, the convolution and the state-only dc_lstm_infer_step.
+    Allocated once, here: the (h, c) buffers of `streams` rows per scale -- copies (dc_gru_infer_init) of the learned
+    h0_layer1 / c0_layer1, which are never written --, the cat(dec, up) and ReLU-ed input buffers per scale, one cc / conv1 /
+    conv2 / pre buffer sized for the largest scale, and the convolutions' workspace."""
+
+    def __init__(self, encoder, decoder, lstm, streams=16, min_depth=0.1, max_depth=100.0):
+        if streams <= 0:
+            raise ValueError("streams must be positive")
+        self.encoder, self.decoder, self.lstm = encoder, decoder, lstm
+        self.streams, self.min_depth, self.max_depth = int(streams), float(min_depth), float(max_depth)
+        cells = lstm.cells()
+        dev = cells[0].h0_layer1.device
+        if dev.type != "cuda":
+            raise _lib.DepthcoreError("WindowPredictor runs on depthcore kernels only (the ConvLSTM is on %s); there is no CPU path" % dev)
+        S = self.streams
+        self.hid = [int(c.h0_layer1.shape[1]) for c in cells]                       # 2 * num_ch_dec[s]
+        self.size = [tuple(c.h0_layer1.shape[2:]) for c in cells]
+        if any(self.hid[s] % 4 or cells[s].clstm_1.input_dim != (self.hid[s] if s < 3 else self.hid[s] // 2) or
+               (s and (self.hid[s] != 2 * self.hid[s - 1] or self.size[s - 1] != (2 * self.size[s][0], 2 * self.size[s][1])))
+               for s in range(4)):
+            raise _lib.DepthcoreError("WindowPredictor: not ConvGRUBlocks_v8's cells (hidden %s at %s)" % (self.hid, self.size))
+
+        def buf(s):
+            return torch.empty((S, self.hid[s]) + self.size[s], dtype=torch.float32, device=dev)
+        self.h, self.c = [buf(s) for s in range(4)], [buf(s) for s in range(4)]
+        self.x = [buf(s) for s in range(3)]                  # cat(dec_s, up_{s+1}); scale 3's input is dec_3 itself
+        self.r = [buf(s) for s in range(4)]                  # relu(input_1): input_1 = x_s, or cat(dec_3, dec_3)
+        n = max(S * self.hid[s] * self.size[s][0] * self.size[s][1] for s in range(4))
+        self._cc, self._t, self._y, self._pre = (torch.empty(k * n, dtype=torch.float32, device=dev) for k in (4, 1, 1, 1))
+        self._ws = None
+        self.reset()
+
+    def reset(self):
+        """Every stream back to the learned initial states (as they are now: a later optimiser step is seen by the next reset)."""
+        cells = self.lstm.cells()
+        ops.gru_infer_init([c.h0_layer1 for c in cells] + [c.c0_layer1 for c in cells], self.h + self.c)
+
+    def _view(self, flat, s, mult=1):
+        shape = (self.streams, mult * self.hid[s]) + self.size[s]
+        return flat[:shape[0] * shape[1] * shape[2] * shape[3]].view(shape)
+
+    def _workspace(self, B):
+        L = _lib.lib()
+        need = 1
+        for s in range(4):
+            C, (H, W) = self.hid[s], self.size[s]
+            need = max(need, L.dc_conv3x3_fwd_workspace(C if s < 3 else C // 2, C, B, 4 * C, H, W), L.dc_conv3x3_fwd_workspace(C, 0, B, C, H, W))
+        need = max(need, L.dc_conv3x3_fwd_workspace(self.hid[0], 0, B, 1, self.size[0][0], self.size[0][1]))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.h[0].device)
+        return self._ws.data_ptr()
+
+    def _recur(self, dec, head):
+        """The recurrent part of a frame on the decoder's pre_disp maps [dec_0..dec_3] of streams 0..B-1; head: also scale 0's
+        unit, hand-over and disparity head -> the (B,1,h,w) sigmoid output (None without)."""
+        L = _lib.lib()
+        dec = [d if d.is_contiguous() else d.contiguous() for d in dec]
+        B = dec[0].shape[0]
+        if len(dec) != 4 or any(d.dtype != torch.float32 or tuple(d.shape) != (B, self.hid[s] // 2) + self.size[s] for s, d in enumerate(dec)):
+            raise _lib.DepthcoreError("decoder maps %s do not match the ConvLSTM's states %s at %s" % (
+                [tuple(d.shape) for d in dec], [c // 2 for c in self.hid], self.size))
+        if not 1 <= B <= self.streams:
+            raise _lib.DepthcoreError("a step of %d frames on a predictor of %d streams" % (B, self.streams))
+        ops._use_precision(ops._precision[0])                    # the caller's ops.matrix_precision, as ops.conv3x3_block
+        ws = self._workspace(B)
+        st = stream(dec[0])
+
+        def conv(x0, C0, x1, C1, m, y, s, act, pad=ops.PAD_ZERO):
+            w, b = m.weight.detach(), m.bias.detach()
+            check(L.dc_conv3x3_fwd(ptr(x0), C0, 0, ptr(x1), C1, ptr(w), ptr(b), ptr(y), ws, B, w.shape[0], self.size[s][0], self.size[s][1],
+                                   act, pad, st), "dc_conv3x3_fwd")
+
+        def unit(u, r, s):                                       # conv2(relu(conv1(r))) -> y; the caller adds r
+            t, y = self._view(self._t, s), self._view(self._y, s)
+            conv(r, self.hid[s], None, 0, u.conv1, t, s, ops.ACT_RELU)
+            conv(t, self.hid[s], None, 0, u.conv2, y, s, ops.ACT_NONE)
+            return y
+        for s in (3, 2, 1, 0):
+            C, d = self.hid[s], dec[s]
+            fusion, cc = getattr(self.lstm, "fusion_%d" % s), self._view(self._cc, s, 4)
+            if s == 3:
+                x = d
+            else:
+                x = self.x[s]
+                x[:B, :C // 2].copy_(d)                          # the upper half is scale s + 1's up, written by its launch
+            # [i | f | o | g] = conv(cat(x_s, h))                                                              rnn.py:67-70
+            conv(x, x.shape[1], self.h[s], C, self.lstm.cells()[s].clstm_1.conv, cc, s, ops.ACT_NONE)
+            if s == 0 and not head:
+                ops.lstm_infer_step(cc, self.h[s], self.c[s], B=B)
+                return None
+            r = self.r[s]
+            if s == 3:
+                r[:B].view(B, 2, C // 2, *self.size[s]).copy_(torch.relu(d).unsqueeze(1))       # relu(cat(dec_3, dec_3))
+            else:
+                torch.clamp_min(x[:B], 0.0, out=r[:B])           # relu(x_s) (torch.relu takes no `out`)
+            y = unit(fusion.resConfUnit1, r, s)
+            pre = self._view(self._pre, 0) if s == 0 else None
+            ops.lstm_infer_step(cc, self.h[s], self.c[s], y, r, pre, None if s == 0 else self.x[s - 1][:, C // 4:], B)
+        # scale 0's head: sigmoid(conv3x3(reflect_pad(unit2(pre))))                                       rnn.py:774-777
+        y = unit(fusion.resConfUnit2, pre, 0)                    # (unit2's leading ReLU finds pre non-negative already)
+        t = self._view(self._t, 0)
+        torch.add(y[:B], pre[:B], out=t[:B])
+        disp = torch.empty((B, 1) + self.size[0], dtype=torch.float32, device=t.device)
+        conv(t, C, None, 0, fusion.conv3x3.conv, disp, 0, ops.ACT_SIGMOID, ops.PAD_REFLECT)
+        return disp
+
+    def _maps(self, frames, what):
+        _frames_ok(frames, what)
+        x = frames if frames.is_contiguous() else frames.contiguous()
+        out = self.decoder(self.encoder(x), True)
+        return [out[("disp", s)] for s in range(4)]
+
+    def _advance(self, frames):
+        self._recur(self._maps(frames, "WindowPredictor.advance"), False)
+
+    def _step(self, frames):
+        disp = self._recur(self._maps(frames, "WindowPredictor.step"), True)
+        dst = torch.empty_like(disp)
+        _scaled_disparity(disp, dst, False, self.min_depth, self.max_depth)
+        return dst
+
+    def _nets(self):
+        return [net for net in (self.encoder, self.decoder, self.lstm) if net is not None]
+
+    def advance(self, frames):
+        """frames (B,3,h,w), B <= streams: the next frame of streams 0..B-1; their states advance, the states of the streams
+        behind B stay.  Returns nothing: no head is run at any scale.  predict_disparities' contract holds for every call."""
+        with _EvalMode(*self._nets()):
+            self._advance(frames)
+
+    def step(self, frames):
+        """As advance, for a frame whose disparity is wanted: -> (B,1,h,w) scaled disparities of scale 0."""
+        with _EvalMode(*self._nets()):
+            return self._step(frames)
+
+    def advance_maps(self, dec):
+        """The recurrent part of `advance` on its own: dec = [dec_0..dec_3], the decoder's pre_disp maps of streams 0..B-1."""
+        with _EvalMode(*self._nets()):
+            self._recur(dec, False)
+
+    def step_maps(self, dec):
+        """The recurrent part of `step` on its own -> the UNSCALED (B,1,h,w) scale-0 disparity."""
+        with _EvalMode(*self._nets()):
+            return self._recur(dec, True)
+
+
+def predict_disparities_windows(encoder, decoder, lstm, lengths, batch_fn, min_depth=0.1, max_depth=100.0, streams=16):
+    """The ConvLSTM v8 evaluation of N independent windows that advance in lockstep (window_groups' schedule): window c has
+    lengths[c] frames, starts from the learned (h0, c0) and is scored at its last frame.  batch_fn(j, ids, frame_of) -> the
+    (len(ids),3,h,w) float32 device tensor of step j of a group: frame frame_of[b] (counted inside the window) of window
+    ids[b]; called once per step.  -> (N,1,h,w) scaled disparities in the order of `lengths`.  One reset and one head per group;
+    contract: predict_disparities'."""
+    lengths = list(lengths)
+    if not lengths:
+        raise ValueError("predict_disparities_windows: no windows")
+    groups = window_groups(lengths, streams)
+    out = None
+    with _EvalMode(encoder, decoder, lstm):
+        wp = WindowPredictor(encoder, decoder, lstm, min(streams, len(lengths)), min_depth, max_depth)
+        for g, (ids, widths) in enumerate(groups):
+            if g:
+                wp.reset()
+            L = len(widths)
+            for j, B in enumerate(widths):
+                frames = batch_fn(j, ids[:B], [j - (L - lengths[c]) for c in ids[:B]])
+                if j < L - 1:
+                    wp._advance(frames)
+                else:
+                    disp = wp._step(frames)
+            if out is None:
+                out = torch.empty((len(lengths),) + tuple(disp.shape[1:]), dtype=torch.float32, device=disp.device)
+            ops.copy_segments([disp[b] for b in range(len(ids))], [out[c] for c in ids])
+    return out
+
+
 def predict_disparities_fusion(encoder, decoder, fusion, triplets, min_depth=0.1, max_depth=100.0, post_process=False, batch_size=16):
     """evaluate_depth_fusion_v3.py:131-165 -> (N,1,h,w) scaled disparities on the device.
 

@@ -29,4 +29,4 @@ from .photo import (PhotoConfig, _fill_desc, _PhotoLoss, pack_rgbx, photo_algori
                     profile_enable)
 from .recurrent import (_GruBlend, _GruLevel, _GruResidual, _GruRH, _infer_levels, _infer_rows, _LstmCell, _LstmHandover,  # noqa: F401
                         _plan_streams, _rows, copy_segments, gru_blend, gru_infer_init, gru_infer_rh, gru_infer_tail,
-                        gru_level_sequence, gru_reset_times_state, gru_sequence_residual, lstm_cell, lstm_handover, stack_frames)
+                        gru_level_sequence, gru_reset_times_state, gru_sequence_residual, lstm_cell, lstm_handover, lstm_infer_step, stack_frames)

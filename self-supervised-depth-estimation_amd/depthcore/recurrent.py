@@ -1,5 +1,5 @@
 """Recurrent front-ends: the ConvGRU gate ops, the frame stacking, the level node of a training sequence, the inference step
-of lockstep streams, and the ConvLSTM state update and hand-over.
+of lockstep streams, and the ConvLSTM state update and hand-over with their one-launch inference form.
 
 Imports `_lib`, `_autograd`, `convs` (the fused block's activation and padding codes) and `data` (`seq_rows`); `ops`
 re-exports every name.
@@ -457,3 +457,36 @@ def lstm_handover(a, h_prev, h_new, need_up=True):
     FeatureFusionBlock_v2's join of the residual unit's output with the mean hidden state, and its UpscalePS.  h_prev may be
     (1, C, h, w): the learned initial hidden state shared over the batch."""
     return _LstmHandover.apply(a, _rows(h_prev, a.shape[0], "h_prev"), h_new, bool(need_up))
+
+
+def lstm_infer_step(cc, h, c, y=None, r=None, pre=None, up=None, B=None):
+    """A v8 frame at one scale for B lockstep streams in ONE launch (dc_lstm_infer_step), no autograd:
+        c' = sigmoid(f) * c + sigmoid(i) * tanh(g),  h' = sigmoid(o) * tanh(c'),  pre = relu((y + r) + (h + h') / 2),
+        up = pixel_shuffle(tanh(pre), 2),  h[:B] <- h',  c[:B] <- c'.
+    cc (B, 4C, hh, w) = [i | f | o | g]; h, c (S >= B, C, hh, w) state buffers REWRITTEN IN PLACE in their first B rows; y, r
+    (resConfUnit1.conv2's output, the unit's ReLU-ed input) both or neither -- neither is the state update alone; pre
+    (>= B, C, hh, w) and up are written where given.  up holds (C/4, 2hh, 2w) per row and may be a channel slice of a wider
+    contiguous buffer (the upper half of the next scale's cat(dec, up)): its row stride is passed down.  B: default cc's rows."""
+    ts = dict(cc=cc, h=h, c=c, y=y, r=r, pre=pre, up=up)
+    ts = {k: (None if t is None else t.detach()) for k, t in ts.items()}
+    cc_, h_, c_ = ts["cc"], ts["h"], ts["c"]
+    B = cc_.shape[0] if B is None else int(B)
+    _, C, P = _gate_dims(cc_, h_, 4, lambda: "gate pre-activations %s do not match the state %s" % (tuple(cc_.shape), tuple(h_.shape)),
+                         rows=False)
+    hh, w = h_.shape[2], h_.shape[3]
+    if c_.shape != h_.shape or not 1 <= B <= min(cc_.shape[0], h_.shape[0]):
+        raise DepthcoreError("lstm_infer_step: B = %d streams of cc %s, h %s, c %s" % (B, tuple(cc_.shape), tuple(h_.shape), tuple(c_.shape)))
+    for k in ("y", "r", "pre"):
+        if ts[k] is not None and (ts[k].dim() != 4 or ts[k].shape[0] < B or ts[k].shape[1:] != h_.shape[1:]):
+            raise DepthcoreError("lstm_infer_step: %s %s does not match %d rows of the state %s" % (k, tuple(ts[k].shape), B, tuple(h_.shape)))
+    up_, stride = ts["up"], 0
+    if up_ is not None:
+        if C % 4 or up_.dim() != 4 or up_.shape[0] < B or tuple(up_.shape[1:]) != (C // 4, 2 * hh, 2 * w) or \
+                up_.stride()[1:] != (4 * P, 2 * w, 1) or (up_.shape[0] > 1 and up_.stride(0) < C * P):
+            raise DepthcoreError("lstm_infer_step: up %s (strides %s) is not (>= %d, %d, %d, %d) with contiguous rows" % (
+                tuple(up_.shape), up_.stride(), B, C // 4, 2 * hh, 2 * w))
+        if up_.dtype != torch.float32 or not up_.is_cuda:
+            raise DepthcoreError("lstm_infer_step: up must be a float32 device tensor")
+        stride = up_.stride(0) if up_.shape[0] > 1 else C * P
+    check(_lib.lib().dc_lstm_infer_step(ptr(cc_), ptr(ts["y"]), ptr(ts["r"]), ptr(h_), ptr(c_), ptr(ts["pre"]),
+                                        None if up_ is None else up_.data_ptr(), stride, B, C, hh, w, stream(h_)), "dc_lstm_infer_step")

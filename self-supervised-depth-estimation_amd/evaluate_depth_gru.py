@@ -1,11 +1,12 @@
-"""Drop-in for the reference's evaluate_depth_gru_fusion.py with `--gru_version v5` (its `evaluate_v5_seq`, lines 504-554, and
-`evaluate`, lines 622-853): scores a ConvGRU v5 model (train_gru.py's encoder.pth / gru.pth / depth.pth) on a KITTI test split
-with evaluate_depth.py's options and prints the same table.
+"""Drop-in for the reference's evaluate_depth_gru_fusion.py with `--gru_version v5` or `v8` (its `evaluate_v5_seq`, lines 504-554,
+`evaluate_v8_seq`, lines 557-618, and `evaluate`, lines 622-853): scores a ConvGRU v5 or ConvLSTM v8 model (train_gru.py's
+encoder.pth / gru.pth / depth.pth) on a KITTI test split with evaluate_depth.py's options and prints the same table.
 
     python evaluate_depth_gru.py --load_weights_folder <weights_N> --eval_mono [--eval_split eigen] [--batch_size 16]
+                                 [--gru_version v8 [--n_prev_images 6]]
                                  [--data_path kitti_data] [--splits_dir splits] [--eval_json results.json]
 
-The model is recurrent.  The lines of test_files.txt are grouped by their drive (first field); the drives are taken in sorted
+v5.  The model is recurrent.  The lines of test_files.txt are grouped by their drive (first field); the drives are taken in sorted
 order and a drive's lines sorted as strings (`sorted(test_files[scene])`, so frame "100" comes before frame "20" -- kept);
 the hidden state starts at the learned `h0_layer1` and is carried from one TEST FILE of a drive to the next (the frames between
 them are skipped, as in the reference); every frame's decoder input is features + (h_cur + h_prev) / 2.  The drives are
@@ -19,8 +20,16 @@ Where it differs from the reference, beyond evaluate_depth.py's own 
     the permutation; when only the reference's gt_depths_seq.npz (export_gt_depth_seq.py) exists it is read and un-permuted;
   - the split and data paths are the options', not "splits/eigen/test_files.txt" and a fixed kitti_data;
   - the networks' size is the one stored in encoder.pth (the reference resizes to 192 x 640 whatever the checkpoint says);
-  - --post_process is refused: the reference's v5 path has none, and a mirrored stream under a learned, non-symmetric h0 is a
-    different model; gru versions other than v5 are refused.
+  - --post_process is refused: the reference's v5 and v8 paths have none, and a mirrored stream under a learned, non-symmetric
+    h0 is a different model; gru versions other than v5 and v8 are refused.
+
+v8.  Every test file is a window of its own: the file's frame and up to `--n_prev_images` (6, the reference's
+constant) frames before it in the same drive and side, `max(0, f - n_prev) .. f`; the window starts from the learned (h0, c0) of
+the four cells, every frame goes through encoder -> decoder(pre_disp) -> the ConvLSTM, and the scale-0 disparity of the LAST
+frame is the prediction.  The windows are independent of each other, so `--batch_size` of them advance in lockstep, right
+aligned (depthcore.evaluate.predict_disparities_windows): the disparity heads, which the recurrence never reads, run once per
+group instead of four times per frame.  Frames shared by the windows of neighbouring test files are computed once per window, as
+in the reference.
 """
 import collections
 import os
@@ -54,24 +63,40 @@ def sequence_order(lines):
     return np.array([i for _, ids in scenes_of(lines) for i in ids], np.int64)
 
 
-def check_options(opt):
+N_PREV_IMAGES = 6            # evaluate_depth_gru_fusion.py:558
+
+
+VERSIONS = {"v5": "ConvGRUBlocks_v5, evaluate_v5_seq", "v8": "ConvGRUBlocks_v8, evaluate_v8_seq"}     # what evaluate() scores
+
+
+def check_options(opt, versions=("v5",)):
+    """Refuses what the evaluation of the gru versions `versions` does not cover.  The one-argument form is the check of the
+    v5 evaluation and stays what it was (callers and a test rely on it refusing every other version); `evaluate` passes
+    VERSIONS, so the script takes v8 as well."""
     if opt.eval_split.startswith("odom"):
         raise ValueError("eval_split %r is pose evaluation: run evaluate_pose.py" % opt.eval_split)
-    if getattr(opt, "gru_version", "v5") != "v5":
-        raise NotImplementedError("gru_version %r: this evaluation covers v5 (ConvGRUBlocks_v5, evaluate_v5_seq); v8 trains "
-                                  "(train_gru.py) but is not evaluated here" % opt.gru_version)
+    if getattr(opt, "gru_version", "v5") not in versions:
+        raise NotImplementedError("gru_version %r: this evaluation covers %s" % (
+            opt.gru_version, " and ".join("%s (%s)" % (v, VERSIONS[v]) for v in versions)))
     if opt.post_process:
-        raise NotImplementedError("--post_process with the ConvGRU front-end: the reference's v5 evaluation has none, and a "
-                                  "mirrored stream under a learned, non-symmetric initial state is a different model")
+        raise NotImplementedError("--post_process with the recurrent front-ends: the reference's v5 and v8 evaluations have none, "
+                                  "and a mirrored stream under a learned, non-symmetric initial state is a different model")
+    if getattr(opt, "n_prev_images", N_PREV_IMAGES) < 0:
+        raise ValueError("--n_prev_images must not be negative")
     assert sum((opt.eval_mono, opt.eval_stereo)) == 1, \
         "Please choose mono or stereo evaluation by setting either --eval_mono or --eval_stereo"
 
 
 def load_networks(opt, device):
-    """evaluate_depth.load_networks' encoder and decoder + gru.pth into ConvGRUBlocks_v5 at the size stored in encoder.pth."""
+    """evaluate_depth.load_networks' encoder and decoder + gru.pth into ConvGRUBlocks_v5, or with --gru_version v8 into
+    ConvGRUBlocks_v8 (num_ch_dec from the decoder), at the size stored in encoder.pth."""
     encoder, decoder, height, width = ED.load_networks(opt, device)
-    gru = networks.ConvGRUBlocks_v5(kernel_size=(3, 3), bias=True, device="cpu", height=height, width=width,
-                                    num_ch_enc=tuple(int(c) for c in encoder.num_ch_enc))
+    if getattr(opt, "gru_version", "v5") == "v8":
+        gru = networks.ConvGRUBlocks_v8(kernel_size=(3, 3), bias=True, device="cpu", attention=False, height=height, width=width,
+                                        num_ch_dec=tuple(int(c) for c in decoder.num_ch_dec[:4]))
+    else:
+        gru = networks.ConvGRUBlocks_v5(kernel_size=(3, 3), bias=True, device="cpu", height=height, width=width,
+                                        num_ch_enc=tuple(int(c) for c in encoder.num_ch_enc))
     gru.load_state_dict(torch.load(os.path.join(os.path.expanduser(opt.load_weights_folder), "gru.pth"), map_location="cpu"))
     return encoder, gru.to(device), decoder, height, width
 
@@ -82,8 +107,34 @@ def frame_batch(prep, paths, device):
     return prep.ragged(torch.from_numpy(packed).to(device), sizes)[("color", 0, 0)]
 
 
+def window_paths(data_path, line, img_ext=".jpg", n_prev=N_PREV_IMAGES):
+    """evaluate_depth_gru_fusion.py:580-586: the image paths of a test line's window, frames max(0, f - n_prev) .. f of its
+    drive and side, in order (the line's own frame last)."""
+    folder, frame, side = line.split()
+    frame = int(frame)
+    return [ED.image_path(data_path, "%s %d %s" % (folder, k, side), img_ext) for k in range(max(0, frame - n_prev), frame + 1)]
+
+
+def predict_v8(opt, device):
+    """-> (N,1,h,w) scaled disparities in test_files.txt order: one window per test file, --batch_size windows in lockstep."""
+    encoder, lstm, decoder, height, width = load_networks(opt, device)
+    lines = ED.readlines(os.path.join(opt.splits_dir, opt.eval_split, "test_files.txt"))
+    img_ext = ".png" if getattr(opt, "png", False) else ".jpg"
+    windows = [window_paths(opt.data_path, line, img_ext, getattr(opt, "n_prev_images", N_PREV_IMAGES)) for line in lines]
+    prep = GpuPreprocessor(height, width, num_scales=1, frame_idxs=(0,), device=device)
+    print("-> Computing predictions with size {}x{}: {} windows of up to {} frames, {} in lockstep".format(
+        width, height, len(windows), max(len(w) for w in windows), opt.batch_size))
+
+    def batch(j, ids, frame_of):
+        return frame_batch(prep, [windows[c][t] for c, t in zip(ids, frame_of)], device)
+    return E.predict_disparities_windows(encoder, decoder, lstm, [len(w) for w in windows], batch, opt.min_depth, opt.max_depth,
+                                         opt.batch_size)
+
+
 def predict(opt, device):
     """-> (N,1,h,w) scaled disparities in test_files.txt order."""
+    if getattr(opt, "gru_version", "v5") == "v8":
+        return predict_v8(opt, device)
     encoder, gru, decoder, height, width = load_networks(opt, device)
     lines = ED.readlines(os.path.join(opt.splits_dir, opt.eval_split, "test_files.txt"))
     img_ext = ".png" if getattr(opt, "png", False) else ".jpg"
@@ -112,9 +163,9 @@ def load_gt_depths(opt):
 
 
 def evaluate(opt):
-    """evaluate_depth_gru_fusion.py:622-853 for gru_version v5.  Returns depthcore.evaluate.evaluate_depth's result, or None when
+    """evaluate_depth_gru_fusion.py:622-853 for gru_version v5 / v8.  Returns depthcore.evaluate.evaluate_depth's result, or None when
     nothing is scored."""
-    check_options(opt)
+    check_options(opt, tuple(VERSIONS))
     device = torch.device("cuda", torch.cuda.current_device())
     pred_disps = predict(opt, device) if opt.ext_disp_to_eval is None else ED.load_external_disparities(opt, device)
     return ED.finish(opt, pred_disps, load_gt_depths)

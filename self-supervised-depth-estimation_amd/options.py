@@ -105,6 +105,7 @@ _BUILD = [
     ("splits_dir", str, os.path.join(_HERE, "splits"), None),  # evaluate_depth.py: <splits_dir>/<eval_split>/{test_files.txt, gt_depths.npz} (none ship here)
     ("eval_json", str, None, None),              # evaluate_depth.py: also write the results to this JSON file
     ("log_images", int, 0, None),                # items per log step whose image panel is written to <log_path>/<mode>/images/ (Trainer.log_images); 0 = off, the reference writes 4
+    ("n_prev_images", int, 6, None),             # evaluate_depth_gru.py --gru_version v8: frames before a test file's own in its window (the reference's constant, evaluate_depth_gru_fusion.py:558)
     ("frame_cache_gb", float, 0.0, None),        # train.py: GiB of HBM for the training loader's cache of resized frames (depthcore/frame_cache.py); 0 = off
 ]
 
@@ -128,7 +129,7 @@ class MonodepthOptions:
     def parse(self, argv=None):
         self.options = self.parser.parse_args(argv)
         for name, typ, _, _ in _BUILD:
-            if typ is int and getattr(self.options, name) in (0, 1) and name not in ("bucket_mb", "seq_batch"):
+            if typ is int and getattr(self.options, name) in (0, 1) and name not in ("bucket_mb", "seq_batch", "n_prev_images"):
                 setattr(self.options, name, bool(getattr(self.options, name)))
         return self.options
 
