@@ -33,6 +33,7 @@ import torch.nn.functional as F
 
 import layer_ops_cases as LC
 import wino_bn_cases as WC
+from wino_split_cases import al256, uhat_bytes, slab_bytes as _wino_slab_bytes      # the Winograd workspace layout is transcribed there
 
 Case = collections.namedtuple("Case", "B C0 up0 C1 Co H W act pad bias grads add0 add1 dsplit")
 
@@ -174,10 +175,6 @@ def params(cases):
 
 
 # ---- the dispatch, transcribed ------------------------------------------------------------------------------------------------------
-def al256(v):
-    return (v + 255) & ~255
-
-
 def pick_mr(M):
     return 4 if M > 32 else (2 if M > 16 else 1)
 
@@ -209,13 +206,8 @@ def c3b_wgrad_split(B, H, W, Co, Cin):
     return min(max(1, min(ntiles, 512 // max(outer, 1))), 256)
 
 
-def _wino_slab_bytes(nout):
-    return (8 if nout * 4 <= (2 << 20) else 2) * nout * 4
-
-
 def wino_conv_ws_bytes(B, Ci, Co, H, W):
-    uhat = al256(ceil_div(Ci, 32) * 32 * ceil_div(Co, 32) * 32 * 16 * 4)
-    return uhat + al256(max(_wino_slab_bytes(B * Co * H * W), _wino_slab_bytes(B * Ci * (H + 2) * (W + 2))))
+    return uhat_bytes(Ci, Co) + al256(max(_wino_slab_bytes(B * Co * H * W), _wino_slab_bytes(B * Ci * (H + 2) * (W + 2))))
 
 
 def wino_eligible(C0, C1, H, W):

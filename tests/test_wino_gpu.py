@@ -19,10 +19,12 @@ CASES = [
     (2, 20, 40, 9, 34),        # K not a multiple of the chunk, M straddles blocks
     (1, 8, 16, 2, 2),          # single tile
     (2, 64, 256, 80, 256),     # bottleneck-style, C3 geometry
-    (1, 512, 512, 6, 20),      # layer4 at batch 1: one sub-region per image, the reduction split 8 ways (small outputs)
-    (1, 256, 256, 12, 40),     # layer3 at batch 1 (split 4 or 8)
-    (3, 512, 512, 6, 20),      # the ConvGRU sequence batch
-    (1, 72, 40, 6, 20),        # 9 chunks: splits whose last slab gets fewer chunks than the others
+    # the split each of these reaches, from tests/wino_split_cases.py's mech() (forward and data gradient alike; the 16-channel tile):
+    (1, 512, 512, 6, 20),      # layer4 at batch 1: one sub-region per image, 64 chunks over 8 slabs of 8
+    (1, 256, 256, 12, 40),     # layer3 at batch 1: 32 chunks over 8 slabs of 4
+    (3, 512, 512, 6, 20),      # the ConvGRU sequence batch: 8 slabs of 8, the plan of the batch-1 launch
+    (1, 72, 40, 6, 20),        # 9 chunks (5 in the data gradient): NO split under wino_ps_cost -- a split cannot pay below 12 chunks; the
+                               # ragged and empty last slabs are pinned in tests/test_wino_split_shapes_gpu.py (9 over 4 under a forced plan)
 ]
 
 
