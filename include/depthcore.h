@@ -818,6 +818,49 @@ int dc_lstm_handover_bwd(const float* pre, const float* g_pre, const float* g_up
 int dc_lstm_infer_step(const float* cc, const float* y, const float* r, float* h, float* c, float* pre, float* up,
                        size_t up_bstride, int B, int C, int hh, int w, void* stream);
 
+/* ------------------------------------------------------------------ f3 coarse-to-fine ConvGRU front-end (gru_version v10) */
+/* networks/rnn.py:472-569 `ConvGRUBlocks_v9` built with attention=False (trainer_gru.py:716-764 `run_gru_v9_v10`): v8's
+ * arrangement with `ConvGRUCell`s (rnn.py:101-143).  The cell's two convolutions are dc_conv3x3_fwd calls (sigmoid / tanh in the
+ * epilogue) and r * h is dc_gru_rh_*; the rest of a frame at one scale is ONE launch per direction:
+ *   dc_gru_handover_fwd  replaces rnn.py:136 (h_next of the cell: dc_gru_blend_fwd), rnn.py:533/542/551/560 (fusion_input_2 =
+ *                        (h + h') / 2) and rnn.py:767-773 with :783-791 (the block's sum, the in-place ReLU, UpscalePS:
+ *                        dc_lstm_handover_fwd):
+ *                          u = gates[:, C:2C]     gates (B, 2C, h, w) = [reset | update], post-sigmoid (dc_gru_blend's layout)
+ *                          h_new = (1 - u) * h_prev + u * cnm
+ *                          pre   = relu(a + (h_prev + h_new) / 2)
+ *                          up[b, q, 2y + i, 2x + j] = tanh(pre[b, 4q + 2i + j, y, x])       (B, C/4, 2h, 2w); up may be NULL (scale 0)
+ *   dc_gru_handover_bwd  their backward (dc_lstm_handover_bwd, then dc_gru_blend_bwd on g_h_new + d / 2), from gates, h_prev, cnm
+ *                        and pre -- all that is kept per frame:
+ *                          t = tanh(pre);  d = (pre > 0) * (g_pre + unshuffle(g_up) * (1 - t^2));  G = g_h_new + d / 2
+ *                          d_a = d;  d_cnm = G * u;  d_gates = [0 | G * (cnm - h_prev)];  d_h_prev = d / 2 + G * (1 - u)
+ *                        g_h_new, g_pre, g_up may each be NULL (zero), not all three.  d_gates is written in full, reset half
+ *                        zero, as dc_gru_blend_bwd writes it: dc_gru_rh_bwd_acc composes behind it as in v5.
+ * h_prev has B rows: a learned initial state (1, C, h, w) shared by B > 1 items is expanded by the caller
+ * (depthcore.ops.gru_handover), whose reduction over B is then autograd's.
+ *   dc_gru_c2f_infer_step  the inference form for B lockstep windows (evaluate_depth_gru_fusion_my_v.py:641-701
+ *                        `evaluate_v9_v10_seq`; depthcore.evaluate.GruWindowPredictor), the counterpart of dc_lstm_infer_step:
+ *                          h' = (1 - u) * h + u * cnm;  pre = relu((y + r) + (h + h') / 2);  up = PixelShuffle(2)(tanh(pre));  h <- h'
+ *                        h: the first B rows of a state buffer, REWRITTEN IN PLACE (each element by the thread that read it); rows
+ *                        behind B are not touched.  y, r both given or both NULL (the state update alone); pre, up only with y;
+ *                        up's element (b, q, 2y + i, 2x + j) lives at up + b * up_bstride + (q * 2hh + 2y + i) * 2w + 2x + j, so
+ *                        that the launch writes into the upper channel half of scale s - 1's cat(dec, up) buffer.  Apart from h
+ *                        being its own output nothing may alias.  The r * h between the two convolutions is dc_gru_infer_rh with
+ *                        one level.
+ * float4 form (four channels 4q..4q+3 at four neighbouring pixels per thread: dc_lstm_handover's item) where C % 4 == 0,
+ * w % 4 == 0, every base is 16-byte aligned and up_bstride % 4 == 0; one element per thread otherwise.  Every thread owns what
+ * it writes: no atomics, two calls give the same bits; no allocation or synchronisation: capturable.  Threads per block:
+ * dc_lstm_block.  DC_EINVAL before any HIP call: a NULL pointer among the required ones (fwd: all but up; bwd: all but the three
+ * g_*; step: gates, cnm, h), a size <= 0, C % 4 != 0 where a shuffle is written or read (up / g_up given), a tensor of 2^31
+ * elements or more (gates counts 2 * B * C * h * w), all three g_* NULL, exactly one of y / r NULL, pre or up without y,
+ * up_bstride < C * hh * w. */
+int dc_gru_handover_fwd(const float* gates, const float* h_prev, const float* cnm, const float* a, float* h_new, float* pre, float* up,
+                        int B, int C, int h, int w, void* stream);
+int dc_gru_handover_bwd(const float* gates, const float* h_prev, const float* cnm, const float* pre, const float* g_h_new,
+                        const float* g_pre, const float* g_up, float* d_gates, float* d_h_prev, float* d_cnm, float* d_a,
+                        int B, int C, int h, int w, void* stream);
+int dc_gru_c2f_infer_step(const float* gates, const float* cnm, const float* y, const float* r, float* h, float* pre, float* up,
+                          size_t up_bstride, int B, int C, int hh, int w, void* stream);
+
 /* ------------------------------------------------------------------ transformed-weight cache of the Winograd kernels */
 /* ------------------------------------------------------------------ reduced-precision networks (BASELINE configs[4]) */
 /* "Networks in reduced precision, loss in fp32" (trainer_fusion_v3.py:311-330 under mixed precision; the reference itself

@@ -7,7 +7,7 @@
 // the forward read or wrote: nothing but cc and c_cur (cell) and pre (hand-over) is kept per frame.  Every thread owns the
 // elements it writes: no atomics, two runs give the same bits.  sigmoid and tanh are the accurate expf / tanhf (not __expf):
 // the states are carried over the frames of a sequence.
-#include "lstm_dev.h"            // lstm_sigmoid, lstm_fwd1, handover_pre, LSTM_BLOCK, lstm_grid, all16: shared with lstm_infer.hip
+#include "lstm_dev.h"            // lstm_sigmoid, lstm_fwd1, handover_pre, handover_d, LSTM_BLOCK, lstm_grid, all16: shared with lstm_infer.hip, gru_c2f.hip
 
 namespace dc {
 
@@ -103,11 +103,7 @@ __global__ __launch_bounds__(LSTM_BLOCK) void lstm_cell_bwd_kernel(const float* 
 
 // ---- coarse-to-fine hand-over ---------------------------------------------------------------------------------------------
 // PixelShuffle(2): up[b, q, 2y + i, 2x + j] = tanh(pre[b, 4q + 2i + j, y, x])   (handover_pre: lstm_dev.h)
-// d(pre pre-ReLU) from the two consumers of pre: the ReLU's mask, the tanh recomputed from pre
-__device__ __forceinline__ float handover_d(float pre, float gp, float gu) {
-    const float t = tanhf(pre);
-    return pre > 0.f ? gp + gu * (1.f - t * t) : 0.f;
-}
+// d(pre pre-ReLU) from the two consumers of pre: handover_d (lstm_dev.h)
 
 // Vector form (w % 4 == 0, 16-byte aligned bases): a thread takes the four channels 4q..4q+3 at four neighbouring pixels of a
 // row: 12 float4 loads, 4 float4 stores of pre and 4 float4 stores of up (two output rows of eight pixels).

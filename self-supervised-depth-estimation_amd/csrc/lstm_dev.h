@@ -1,5 +1,5 @@
-// The per-element expressions of the ConvLSTM v8 passes and their launch shape, stated once for the training forms (lstm.hip)
-// and the inference step (lstm_infer.hip).  sigmoid and tanh are the accurate expf / tanhf (not __expf): the states are
+// The per-element expressions of the ConvLSTM v8 passes and their launch shape, stated once for the training forms (lstm.hip),
+// the inference step (lstm_infer.hip) and the ConvGRU v10 hand-over, which shares the hand-over's item walk (gru_c2f.hip).  sigmoid and tanh are the accurate expf / tanhf (not __expf): the states are
 // carried over the frames of a sequence.
 #pragma once
 #include "dc_common.h"
@@ -23,6 +23,11 @@ __device__ __forceinline__ LstmFwd lstm_fwd1(float ci, float cf, float co, float
 
 // PixelShuffle(2): up[b, q, 2y + i, 2x + j] = tanh(pre[b, 4q + 2i + j, y, x]).
 __device__ __forceinline__ float handover_pre(float a, float hp, float hn) { return fmaxf(a + (hp + hn) * 0.5f, 0.f); }
+// d(pre pre-ReLU) from the two consumers of pre: the ReLU's mask, the tanh recomputed from pre
+__device__ __forceinline__ float handover_d(float pre, float gp, float gu) {
+    const float t = tanhf(pre);
+    return pre > 0.f ? gp + gu * (1.f - t * t) : 0.f;
+}
 
 static inline unsigned lstm_grid(size_t work) { return (unsigned)std::min<size_t>((work + LSTM_BLOCK - 1) / LSTM_BLOCK, 4096); }
 

@@ -267,6 +267,9 @@ def _sig(lib):
         "dc_lstm_handover_fwd": (i, [p, p, p, p, p, i, i, i, i, p]),
         "dc_lstm_handover_bwd": (i, [p, p, p, p, p, p, i, i, i, i, p]),
         "dc_lstm_infer_step": (i, [p, p, p, p, p, p, p, z, i, i, i, i, p]),
+        "dc_gru_handover_fwd": (i, [p, p, p, p, p, p, p, i, i, i, i, p]),
+        "dc_gru_handover_bwd": (i, [p, p, p, p, p, p, p, p, p, p, p, i, i, i, i, p]),
+        "dc_gru_c2f_infer_step": (i, [p, p, p, p, p, p, p, z, i, i, i, i, p]),
         "dc_set_matrix_precision": (i, [i]),
         "dc_get_matrix_precision": (i, []),
         "dc_clear_error": (i, []),

@@ -498,7 +498,11 @@ class WindowPredictor:
     scale s - 1's buffer.  Scale 0 of `advance`: the copy, the convolution and the state-only dc_lstm_infer_step.
     Allocated once, here: the (h, c) buffers of `streams` rows per scale -- copies (dc_gru_infer_init) of the learned
     h0_layer1 / c0_layer1, which are never written --, the cat(dec, up) and ReLU-ed input buffers per scale, one cc / conv1 /
-    conv2 / pre buffer sized for the largest scale, and the convolutions' workspace."""
+    conv2 / pre buffer sized for the largest scale, and the convolutions' workspace.
+
+    What belongs to the cell type is five methods -- `_input_dim`, `_alloc_cell`, `reset`, `_cell_workspace`, `_cell` -- which
+    GruWindowPredictor restates for the ConvGRU cells of v10; the rest (the buffers of the fusion blocks, the walk over the
+    scales, the units, the head, the public methods) is stated here once."""
 
     def __init__(self, encoder, decoder, lstm, streams=16, min_depth=0.1, max_depth=100.0):
         if streams <= 0:
@@ -509,28 +513,53 @@ class WindowPredictor:
         dev = cells[0].h0_layer1.device
         if dev.type != "cuda":
             raise _lib.DepthcoreError("WindowPredictor runs on depthcore kernels only (the ConvLSTM is on %s); there is no CPU path" % dev)
-        S = self.streams
+        S, self._dev = self.streams, dev
         self.hid = [int(c.h0_layer1.shape[1]) for c in cells]                       # 2 * num_ch_dec[s]
         self.size = [tuple(c.h0_layer1.shape[2:]) for c in cells]
-        if any(self.hid[s] % 4 or cells[s].clstm_1.input_dim != (self.hid[s] if s < 3 else self.hid[s] // 2) or
+        if any(self.hid[s] % 4 or self._input_dim(cells[s]) != (self.hid[s] if s < 3 else self.hid[s] // 2) or
                (s and (self.hid[s] != 2 * self.hid[s - 1] or self.size[s - 1] != (2 * self.size[s][0], 2 * self.size[s][1])))
                for s in range(4)):
-            raise _lib.DepthcoreError("WindowPredictor: not ConvGRUBlocks_v8's cells (hidden %s at %s)" % (self.hid, self.size))
-
-        def buf(s):
-            return torch.empty((S, self.hid[s]) + self.size[s], dtype=torch.float32, device=dev)
-        self.h, self.c = [buf(s) for s in range(4)], [buf(s) for s in range(4)]
-        self.x = [buf(s) for s in range(3)]                  # cat(dec_s, up_{s+1}); scale 3's input is dec_3 itself
-        self.r = [buf(s) for s in range(4)]                  # relu(input_1): input_1 = x_s, or cat(dec_3, dec_3)
+            raise _lib.DepthcoreError("%s: not %s's cells (hidden %s at %s)" % (type(self).__name__, self.BLOCKS, self.hid, self.size))
+        self.h = [self._buf(s) for s in range(4)]
+        self.x = [self._buf(s) for s in range(3)]            # cat(dec_s, up_{s+1}); scale 3's input is dec_3 itself
+        self.r = [self._buf(s) for s in range(4)]            # relu(input_1): input_1 = x_s, or cat(dec_3, dec_3)
         n = max(S * self.hid[s] * self.size[s][0] * self.size[s][1] for s in range(4))
-        self._cc, self._t, self._y, self._pre = (torch.empty(k * n, dtype=torch.float32, device=dev) for k in (4, 1, 1, 1))
+        self._t, self._y, self._pre = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3))
+        self._alloc_cell(n, dev)
         self._ws = None
         self.reset()
+
+    def _buf(self, s):
+        return torch.empty((self.streams, self.hid[s]) + self.size[s], dtype=torch.float32, device=self._dev)
+
+    # ---- the cell type: ConvLSTMCell_v1 here -------------------------------------------------------------------------------
+    BLOCKS = "ConvGRUBlocks_v8"
+
+    @staticmethod
+    def _input_dim(cell):
+        lstm = getattr(cell, "clstm_1", None)                    # None: another cell type, refused by the caller
+        return None if lstm is None else lstm.input_dim
+
+    def _alloc_cell(self, n, dev):
+        """The cell's own buffers: the cell state per scale and one buffer of gate pre-activations for the largest scale."""
+        self.c = [self._buf(s) for s in range(4)]
+        self._cc = torch.empty(4 * n, dtype=torch.float32, device=dev)
 
     def reset(self):
         """Every stream back to the learned initial states (as they are now: a later optimiser step is seen by the next reset)."""
         cells = self.lstm.cells()
         ops.gru_infer_init([c.h0_layer1 for c in cells] + [c.c0_layer1 for c in cells], self.h + self.c)
+
+    def _cell_workspace(self, L, s, B):
+        C, (H, W) = self.hid[s], self.size[s]
+        return L.dc_conv3x3_fwd_workspace(C if s < 3 else C // 2, C, B, 4 * C, H, W)
+
+    def _cell(self, conv, s, x, B, y=None, r=None, pre=None, up=None):
+        """The cell's convolution over (x_s, h[:B]) and the one launch that steps the state and, with y, hands over."""
+        cc = self._view(self._cc, s, 4)
+        # [i | f | o | g] = conv(cat(x_s, h))                                                              rnn.py:67-70
+        conv(x, x.shape[1], self.h[s], self.hid[s], self.lstm.cells()[s].clstm_1.conv, cc, s, ops.ACT_NONE)
+        ops.lstm_infer_step(cc, self.h[s], self.c[s], y, r, pre, up, B)
 
     def _view(self, flat, s, mult=1):
         shape = (self.streams, mult * self.hid[s]) + self.size[s]
@@ -541,7 +570,7 @@ class WindowPredictor:
         need = 1
         for s in range(4):
             C, (H, W) = self.hid[s], self.size[s]
-            need = max(need, L.dc_conv3x3_fwd_workspace(C if s < 3 else C // 2, C, B, 4 * C, H, W), L.dc_conv3x3_fwd_workspace(C, 0, B, C, H, W))
+            need = max(need, self._cell_workspace(L, s, B), L.dc_conv3x3_fwd_workspace(C, 0, B, C, H, W))
         need = max(need, L.dc_conv3x3_fwd_workspace(self.hid[0], 0, B, 1, self.size[0][0], self.size[0][1]))
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.h[0].device)
@@ -574,16 +603,14 @@ class WindowPredictor:
             return y
         for s in (3, 2, 1, 0):
             C, d = self.hid[s], dec[s]
-            fusion, cc = getattr(self.lstm, "fusion_%d" % s), self._view(self._cc, s, 4)
+            fusion = getattr(self.lstm, "fusion_%d" % s)
             if s == 3:
                 x = d
             else:
                 x = self.x[s]
                 x[:B, :C // 2].copy_(d)                          # the upper half is scale s + 1's up, written by its launch
-            # [i | f | o | g] = conv(cat(x_s, h))                                                              rnn.py:67-70
-            conv(x, x.shape[1], self.h[s], C, self.lstm.cells()[s].clstm_1.conv, cc, s, ops.ACT_NONE)
             if s == 0 and not head:
-                ops.lstm_infer_step(cc, self.h[s], self.c[s], B=B)
+                self._cell(conv, s, x, B)
                 return None
             r = self.r[s]
             if s == 3:
@@ -592,7 +619,7 @@ class WindowPredictor:
                 torch.clamp_min(x[:B], 0.0, out=r[:B])           # relu(x_s) (torch.relu takes no `out`)
             y = unit(fusion.resConfUnit1, r, s)
             pre = self._view(self._pre, 0) if s == 0 else None
-            ops.lstm_infer_step(cc, self.h[s], self.c[s], y, r, pre, None if s == 0 else self.x[s - 1][:, C // 4:], B)
+            self._cell(conv, s, x, B, y, r, pre, None if s == 0 else self.x[s - 1][:, C // 4:])
         # scale 0's head: sigmoid(conv3x3(reflect_pad(unit2(pre))))                                       rnn.py:774-777
         y = unit(fusion.resConfUnit2, pre, 0)                    # (unit2's leading ReLU finds pre non-negative already)
         t = self._view(self._t, 0)
@@ -641,9 +668,46 @@ class WindowPredictor:
             return self._recur(dec, True)
 
 
+class GruWindowPredictor(WindowPredictor):
+    """WindowPredictor for the coarse-to-fine ConvGRU front-end, v10 (evaluate_depth_gru_fusion_my_v.py:673-690 is one stream):
+    `lstm` is a ConvGRUBlocks_v9(attention=False).  Per frame and scale the cell is the gate convolution over (x_s, h[:B]),
+    dc_gru_infer_rh with one level, the candidate convolution over (x_s, r * h), and ONE dc_gru_c2f_infer_step, which rewrites
+    h[:B] in place and hands over; there is no cell state.  Its own buffers: gates, r * h and the candidate for the largest
+    scale."""
+    BLOCKS = "ConvGRUBlocks_v9"
+
+    @staticmethod
+    def _input_dim(cell):
+        gru = getattr(cell, "cgru_1", None)
+        return None if gru is None else gru.conv_gates.in_channels - gru.hidden_dim
+
+    def _alloc_cell(self, n, dev):
+        self._gates, self._rh, self._cnm = (torch.empty(k * n, dtype=torch.float32, device=dev) for k in (2, 1, 1))
+
+    def reset(self):
+        ops.gru_infer_init([c.h0_layer1 for c in self.lstm.cells()], self.h)
+
+    def _cell_workspace(self, L, s, B):
+        C, (H, W) = self.hid[s], self.size[s]
+        return max(L.dc_conv3x3_fwd_workspace(C if s < 3 else C // 2, C, B, co, H, W) for co in (2 * C, C))
+
+    def _cell(self, conv, s, x, B, y=None, r=None, pre=None, up=None):
+        cell, C = self.lstm.cells()[s].cgru_1, self.hid[s]
+        gates, rh, cnm = self._view(self._gates, s, 2), self._view(self._rh, s), self._view(self._cnm, s)
+        conv(x, x.shape[1], self.h[s], C, cell.conv_gates, gates, s, ops.ACT_SIGMOID)                    # rnn.py:125-130
+        ops.gru_infer_rh([gates], [self.h[s]], [rh], B)
+        conv(x, x.shape[1], rh, C, cell.conv_can, cnm, s, ops.ACT_TANH)                                  # rnn.py:132-134
+        ops.gru_c2f_infer_step(gates, cnm, self.h[s], y, r, pre, up, B)
+
+
+def window_predictor_class(blocks):
+    """WindowPredictor for ConvGRUBlocks_v8 (ConvLSTM cells), GruWindowPredictor for ConvGRUBlocks_v9 (ConvGRU cells)."""
+    return WindowPredictor if hasattr(blocks.cells()[0], "clstm_1") else GruWindowPredictor
+
+
 def predict_disparities_windows(encoder, decoder, lstm, lengths, batch_fn, min_depth=0.1, max_depth=100.0, streams=16):
-    """The ConvLSTM v8 evaluation of N independent windows that advance in lockstep (window_groups' schedule): window c has
-    lengths[c] frames, starts from the learned (h0, c0) and is scored at its last frame.  batch_fn(j, ids, frame_of) -> the
+    """The ConvLSTM v8 / ConvGRU v10 evaluation of N independent windows that advance in lockstep (window_groups' schedule):
+    window c has lengths[c] frames, starts from the learned initial states and is scored at its last frame.  batch_fn(j, ids, frame_of) -> the
     (len(ids),3,h,w) float32 device tensor of step j of a group: frame frame_of[b] (counted inside the window) of window
     ids[b]; called once per step.  -> (N,1,h,w) scaled disparities in the order of `lengths`.  One reset and one head per group;
     contract: predict_disparities'."""
@@ -653,7 +717,7 @@ def predict_disparities_windows(encoder, decoder, lstm, lengths, batch_fn, min_d
     groups = window_groups(lengths, streams)
     out = None
     with _EvalMode(encoder, decoder, lstm):
-        wp = WindowPredictor(encoder, decoder, lstm, min(streams, len(lengths)), min_depth, max_depth)
+        wp = window_predictor_class(lstm)(encoder, decoder, lstm, min(streams, len(lengths)), min_depth, max_depth)
         for g, (ids, widths) in enumerate(groups):
             if g:
                 wp.reset()

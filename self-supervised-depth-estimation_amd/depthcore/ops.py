@@ -27,6 +27,7 @@ from .layer_ops import (_aligned8, _Backproject, _DispToDepth, _GridSample, _Pos
                         pose_head, pose_matrix, project3d, smooth_loss, ssim, upsample_bilinear, upsample_nearest2x)
 from .photo import (PhotoConfig, _fill_desc, _PhotoLoss, pack_rgbx, photo_algorithmic_bytes, photometric_loss, profile_collect,  # noqa: F401
                     profile_enable)
-from .recurrent import (_GruBlend, _GruLevel, _GruResidual, _GruRH, _infer_levels, _infer_rows, _LstmCell, _LstmHandover,  # noqa: F401
-                        _plan_streams, _rows, copy_segments, gru_blend, gru_infer_init, gru_infer_rh, gru_infer_tail,
-                        gru_level_sequence, gru_reset_times_state, gru_sequence_residual, lstm_cell, lstm_handover, lstm_infer_step, stack_frames)
+from .recurrent import (_GruBlend, _GruHandover, _GruLevel, _GruResidual, _GruRH, _infer_levels, _infer_rows, _LstmCell,  # noqa: F401
+                        _LstmHandover, _plan_streams, _rows, copy_segments, gru_blend, gru_infer_init, gru_infer_rh, gru_infer_tail,
+                        gru_level_sequence, gru_reset_times_state, gru_sequence_residual, lstm_cell, lstm_handover, lstm_infer_step,
+                        gru_handover, gru_c2f_infer_step, stack_frames)

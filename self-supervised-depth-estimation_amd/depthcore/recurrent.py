@@ -1,5 +1,6 @@
 """Recurrent front-ends: the ConvGRU gate ops, the frame stacking, the level node of a training sequence, the inference step
-of lockstep streams, and the ConvLSTM state update and hand-over with their one-launch inference form.
+of lockstep streams, the ConvLSTM state update and hand-over with their one-launch inference form, and the coarse-to-fine
+ConvGRU's one-launch hand-over (the GRU's tail joined with the fusion block's hand-over) with its inference form.
 
 Imports `_lib`, `_autograd`, `convs` (the fused block's activation and padding codes) and `data` (`seq_rows`); `ops`
 re-exports every name.
@@ -459,6 +460,27 @@ def lstm_handover(a, h_prev, h_new, need_up=True):
     return _LstmHandover.apply(a, _rows(h_prev, a.shape[0], "h_prev"), h_new, bool(need_up))
 
 
+def _step_outputs(name, h_, B, ts):
+    """The hand-over tensors of an inference step (ts: y, r, pre, up, each a tensor or None) against B rows of the state h_
+    (S >= B, C, hh, w) -> (address of up or None, its row stride).  up holds (C/4, 2hh, 2w) per row and may be a channel slice
+    of a wider contiguous buffer, whose row stride is passed down."""
+    C, hh, w = h_.shape[1:]
+    P = hh * w
+    for k in ("y", "r", "pre"):
+        if ts[k] is not None and (ts[k].dim() != 4 or ts[k].shape[0] < B or ts[k].shape[1:] != h_.shape[1:]):
+            raise DepthcoreError("%s: %s %s does not match %d rows of the state %s" % (name, k, tuple(ts[k].shape), B, tuple(h_.shape)))
+    up_, stride = ts["up"], 0
+    if up_ is not None:
+        if C % 4 or up_.dim() != 4 or up_.shape[0] < B or tuple(up_.shape[1:]) != (C // 4, 2 * hh, 2 * w) or \
+                up_.stride()[1:] != (4 * P, 2 * w, 1) or (up_.shape[0] > 1 and up_.stride(0) < C * P):
+            raise DepthcoreError("%s: up %s (strides %s) is not (>= %d, %d, %d, %d) with contiguous rows" % (
+                name, tuple(up_.shape), up_.stride(), B, C // 4, 2 * hh, 2 * w))
+        if up_.dtype != torch.float32 or not up_.is_cuda:
+            raise DepthcoreError("%s: up must be a float32 device tensor" % name)
+        stride = up_.stride(0) if up_.shape[0] > 1 else C * P
+    return (None if up_ is None else up_.data_ptr()), stride
+
+
 def lstm_infer_step(cc, h, c, y=None, r=None, pre=None, up=None, B=None):
     """A v8 frame at one scale for B lockstep streams in ONE launch (dc_lstm_infer_step), no autograd:
         c' = sigmoid(f) * c + sigmoid(i) * tanh(g),  h' = sigmoid(o) * tanh(c'),  pre = relu((y + r) + (h + h') / 2),
@@ -476,17 +498,70 @@ def lstm_infer_step(cc, h, c, y=None, r=None, pre=None, up=None, B=None):
     hh, w = h_.shape[2], h_.shape[3]
     if c_.shape != h_.shape or not 1 <= B <= min(cc_.shape[0], h_.shape[0]):
         raise DepthcoreError("lstm_infer_step: B = %d streams of cc %s, h %s, c %s" % (B, tuple(cc_.shape), tuple(h_.shape), tuple(c_.shape)))
-    for k in ("y", "r", "pre"):
-        if ts[k] is not None and (ts[k].dim() != 4 or ts[k].shape[0] < B or ts[k].shape[1:] != h_.shape[1:]):
-            raise DepthcoreError("lstm_infer_step: %s %s does not match %d rows of the state %s" % (k, tuple(ts[k].shape), B, tuple(h_.shape)))
-    up_, stride = ts["up"], 0
-    if up_ is not None:
-        if C % 4 or up_.dim() != 4 or up_.shape[0] < B or tuple(up_.shape[1:]) != (C // 4, 2 * hh, 2 * w) or \
-                up_.stride()[1:] != (4 * P, 2 * w, 1) or (up_.shape[0] > 1 and up_.stride(0) < C * P):
-            raise DepthcoreError("lstm_infer_step: up %s (strides %s) is not (>= %d, %d, %d, %d) with contiguous rows" % (
-                tuple(up_.shape), up_.stride(), B, C // 4, 2 * hh, 2 * w))
-        if up_.dtype != torch.float32 or not up_.is_cuda:
-            raise DepthcoreError("lstm_infer_step: up must be a float32 device tensor")
-        stride = up_.stride(0) if up_.shape[0] > 1 else C * P
-    check(_lib.lib().dc_lstm_infer_step(ptr(cc_), ptr(ts["y"]), ptr(ts["r"]), ptr(h_), ptr(c_), ptr(ts["pre"]),
-                                        None if up_ is None else up_.data_ptr(), stride, B, C, hh, w, stream(h_)), "dc_lstm_infer_step")
+    up_ptr, stride = _step_outputs("lstm_infer_step", h_, B, ts)
+    check(_lib.lib().dc_lstm_infer_step(ptr(cc_), ptr(ts["y"]), ptr(ts["r"]), ptr(h_), ptr(c_), ptr(ts["pre"]), up_ptr, stride, B, C, hh, w,
+                                        stream(h_)), "dc_lstm_infer_step")
+
+
+# ----------------------------------------------------------------------------------------------
+# f3 coarse-to-fine ConvGRU v10: the GRU's tail and the hand-over in one launch   (reference networks/rnn.py:136, 533, 767-791)
+# ----------------------------------------------------------------------------------------------
+class _GruHandover(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gates, h_prev, cnm, a, need_up):
+        L = _lib.lib()
+        gt, hp, cn, aa = _c(gates.detach()), _c(h_prev.detach()), _c(cnm.detach()), _c(a.detach())
+        def err():
+            return "gates %s / candidate %s / unit output %s do not match the state %s" % (
+                tuple(gt.shape), tuple(cn.shape), tuple(aa.shape), tuple(hp.shape))
+        B, C, _ = _gate_dims(gt, hp, 2, err)
+        if cn.shape != hp.shape or aa.shape != hp.shape or (need_up and C % 4):
+            raise DepthcoreError(err() + (" (the shuffle needs C % 4 == 0)" if need_up and C % 4 else ""))
+        h, w = hp.shape[2:]
+        h_new, pre = torch.empty_like(hp), torch.empty_like(hp)
+        up = torch.empty(B, C // 4, 2 * h, 2 * w, dtype=torch.float32, device=hp.device) if need_up else None
+        check(L.dc_gru_handover_fwd(ptr(gt), ptr(hp), ptr(cn), ptr(aa), ptr(h_new), ptr(pre), ptr(up), B, C, h, w, stream(hp)),
+              "dc_gru_handover_fwd")
+        ctx.save_for_backward(gt, hp, cn, pre)                 # all the backward reads
+        ctx.set_materialize_grads(False)                       # an output nobody reads (the last frame's state) arrives as None -> NULL
+        return h_new, pre, up
+
+    @staticmethod
+    def backward(ctx, g_h, g_pre, g_up):
+        if (g_h is None and g_pre is None and g_up is None) or not any(ctx.needs_input_grad[:4]):
+            return None, None, None, None, None
+        L = _lib.lib()
+        gt, hp, cn, pre = ctx.saved_tensors
+        B, C, h, w = hp.shape
+        gh, gp, gu = [None if g is None else _c(g) for g in (g_h, g_pre, g_up)]
+        d_gates, d_h, d_cnm, d_a = torch.empty_like(gt), torch.empty_like(hp), torch.empty_like(cn), torch.empty_like(pre)
+        check(L.dc_gru_handover_bwd(ptr(gt), ptr(hp), ptr(cn), ptr(pre), ptr(gh), ptr(gp), ptr(gu), ptr(d_gates), ptr(d_h), ptr(d_cnm),
+                                    ptr(d_a), B, C, h, w, stream(hp)), "dc_gru_handover_bwd")
+        return d_gates, d_h, d_cnm, d_a, None
+
+
+def gru_handover(gates, h_prev, cnm, a, need_up=True):
+    """(h_new, pre, up) of a v10 frame at one scale in one launch (dc_gru_handover_fwd): with u = gates[:, C:],
+    h_new = (1 - u) * h_prev + u * cnm, pre = relu(a + (h_prev + h_new) / 2), up = pixel_shuffle(tanh(pre), 2) (None without
+    need_up).  gates (B, 2C, h, w) = [reset | update] after the sigmoid, cnm the candidate, a resConfUnit1's output.  h_prev may
+    be (1, C, h, w): the learned initial state shared over the batch."""
+    return _GruHandover.apply(gates, _rows(h_prev, a.shape[0], "h_prev"), cnm, a, bool(need_up))
+
+
+def gru_c2f_infer_step(gates, cnm, h, y=None, r=None, pre=None, up=None, B=None):
+    """A v10 frame at one scale for B lockstep streams in ONE launch (dc_gru_c2f_infer_step), no autograd: with u = gates[:, C:],
+        h' = (1 - u) * h + u * cnm,  pre = relu((y + r) + (h + h') / 2),  up = pixel_shuffle(tanh(pre), 2),  h[:B] <- h'.
+    gates (B, 2C, hh, w), cnm (>= B, C, hh, w); h (S >= B, C, hh, w) the state buffer, REWRITTEN IN PLACE in its first B rows;
+    y, r, pre, up as lstm_infer_step's.  B: default gates' rows."""
+    ts = dict(gates=gates, cnm=cnm, h=h, y=y, r=r, pre=pre, up=up)
+    ts = {k: (None if t is None else t.detach()) for k, t in ts.items()}
+    gt, cn, h_ = ts["gates"], ts["cnm"], ts["h"]
+    B = gt.shape[0] if B is None else int(B)
+    _, C, P = _gate_dims(gt, h_, 2, lambda: "gates %s do not match the state %s" % (tuple(gt.shape), tuple(h_.shape)), rows=False)
+    hh, w = h_.shape[2], h_.shape[3]
+    if cn.dim() != 4 or cn.shape[1:] != h_.shape[1:] or not 1 <= B <= min(gt.shape[0], cn.shape[0], h_.shape[0]):
+        raise DepthcoreError("gru_c2f_infer_step: B = %d streams of gates %s, cnm %s, h %s" % (
+            B, tuple(gt.shape), tuple(cn.shape), tuple(h_.shape)))
+    up_ptr, stride = _step_outputs("gru_c2f_infer_step", h_, B, ts)
+    check(_lib.lib().dc_gru_c2f_infer_step(ptr(gt), ptr(cn), ptr(ts["y"]), ptr(ts["r"]), ptr(h_), ptr(ts["pre"]), up_ptr, stride, B, C, hh, w,
+                                           stream(h_)), "dc_gru_c2f_infer_step")

@@ -3,7 +3,7 @@
 encoder.pth / gru.pth / depth.pth) on a KITTI test split with evaluate_depth.py's options and prints the same table.
 
     python evaluate_depth_gru.py --load_weights_folder <weights_N> --eval_mono [--eval_split eigen] [--batch_size 16]
-                                 [--gru_version v8 [--n_prev_images 6]]
+                                 [--gru_version v8 [--n_prev_images 6]] [--gru_version v10 [--n_prev_images 10]]
                                  [--data_path kitti_data] [--splits_dir splits] [--eval_json results.json]
 
 v5.  The model is recurrent.  The lines of test_files.txt are grouped by their drive (first field); the drives are taken in sorted
@@ -21,7 +21,7 @@ Where it differs from the reference, beyond evaluate_depth.py's own 
   - the split and data paths are the options', not "splits/eigen/test_files.txt" and a fixed kitti_data;
   - the networks' size is the one stored in encoder.pth (the reference resizes to 192 x 640 whatever the checkpoint says);
   - --post_process is refused: the reference's v5 and v8 paths have none, and a mirrored stream under a learned, non-symmetric
-    h0 is a different model; gru versions other than v5 and v8 are refused.
+    h0 is a different model; gru versions other than v5, v8 and v10 are refused.
 
 v8.  Every test file is a window of its own: the file's frame and up to `--n_prev_images` (6, the reference's
 constant) frames before it in the same drive and side, `max(0, f - n_prev) .. f`; the window starts from the learned (h0, c0) of
@@ -30,6 +30,11 @@ frame is the prediction.  The windows are independent of each other, so `--batch
 aligned (depthcore.evaluate.predict_disparities_windows): the disparity heads, which the recurrence never reads, run once per
 group instead of four times per frame.  Frames shared by the windows of neighbouring test files are computed once per window, as
 in the reference.
+
+v10 is the reference's evaluate_depth_gru_fusion_my_v.py (`evaluate_v9_v10_seq`, lines 641-701) for the coarse-to-fine
+ConvGRU model: v8's protocol with `ConvGRUBlocks_v9(attention=False)`, windows that start from the learned h0 of the four cells,
+and 10 previous frames where v8 has 6.  `--n_prev_images` keeps its default of 6 for every version: `--n_prev_images 10`
+reproduces the reference's v10 protocol.  v9 (the attention variant) is not built.
 """
 import collections
 import os
@@ -66,20 +71,25 @@ def sequence_order(lines):
 N_PREV_IMAGES = 6            # evaluate_depth_gru_fusion.py:558
 
 
-VERSIONS = {"v5": "ConvGRUBlocks_v5, evaluate_v5_seq", "v8": "ConvGRUBlocks_v8, evaluate_v8_seq"}     # what evaluate() scores
+N_PREV_IMAGES_MY_V = 10      # evaluate_depth_gru_fusion_my_v.py:642 (v9 / v10): asked for with --n_prev_images 10
+
+
+VERSIONS = {"v5": "ConvGRUBlocks_v5, evaluate_v5_seq", "v8": "ConvGRUBlocks_v8, evaluate_v8_seq"}     # evaluate_depth_gru_fusion.py's
+MY_V_VERSIONS = {"v10": "ConvGRUBlocks_v9(attention=False), evaluate_v9_v10_seq"}                     # evaluate_depth_gru_fusion_my_v.py's
+WINDOWED = ("v8", "v10")     # one window per test file (predict_windows); v5 carries its state along a drive
 
 
 def check_options(opt, versions=("v5",)):
     """Refuses what the evaluation of the gru versions `versions` does not cover.  The one-argument form is the check of the
     v5 evaluation and stays what it was (callers and a test rely on it refusing every other version); `evaluate` passes
-    VERSIONS, so the script takes v8 as well."""
+    both tables' versions, so the script takes v8 and v10 as well."""
     if opt.eval_split.startswith("odom"):
         raise ValueError("eval_split %r is pose evaluation: run evaluate_pose.py" % opt.eval_split)
     if getattr(opt, "gru_version", "v5") not in versions:
         raise NotImplementedError("gru_version %r: this evaluation covers %s" % (
-            opt.gru_version, " and ".join("%s (%s)" % (v, VERSIONS[v]) for v in versions)))
+            opt.gru_version, " and ".join("%s (%s)" % (v, {**VERSIONS, **MY_V_VERSIONS}[v]) for v in versions)))
     if opt.post_process:
-        raise NotImplementedError("--post_process with the recurrent front-ends: the reference's v5 and v8 evaluations have none, "
+        raise NotImplementedError("--post_process with the recurrent front-ends: the reference's v5, v8 and v10 evaluations have none, "
                                   "and a mirrored stream under a learned, non-symmetric initial state is a different model")
     if getattr(opt, "n_prev_images", N_PREV_IMAGES) < 0:
         raise ValueError("--n_prev_images must not be negative")
@@ -88,12 +98,14 @@ def check_options(opt, versions=("v5",)):
 
 
 def load_networks(opt, device):
-    """evaluate_depth.load_networks' encoder and decoder + gru.pth into ConvGRUBlocks_v5, or with --gru_version v8 into
-    ConvGRUBlocks_v8 (num_ch_dec from the decoder), at the size stored in encoder.pth."""
+    """evaluate_depth.load_networks' encoder and decoder + gru.pth into ConvGRUBlocks_v5, or with --gru_version v8 / v10 into
+    ConvGRUBlocks_v8 / ConvGRUBlocks_v9 (num_ch_dec from the decoder), at the size stored in encoder.pth."""
     encoder, decoder, height, width = ED.load_networks(opt, device)
-    if getattr(opt, "gru_version", "v5") == "v8":
-        gru = networks.ConvGRUBlocks_v8(kernel_size=(3, 3), bias=True, device="cpu", attention=False, height=height, width=width,
-                                        num_ch_dec=tuple(int(c) for c in decoder.num_ch_dec[:4]))
+    version = getattr(opt, "gru_version", "v5")
+    if version in WINDOWED:
+        blocks = networks.ConvGRUBlocks_v8 if version == "v8" else networks.ConvGRUBlocks_v9
+        gru = blocks(kernel_size=(3, 3), bias=True, device="cpu", attention=False, height=height, width=width,
+                     num_ch_dec=tuple(int(c) for c in decoder.num_ch_dec[:4]))
     else:
         gru = networks.ConvGRUBlocks_v5(kernel_size=(3, 3), bias=True, device="cpu", height=height, width=width,
                                         num_ch_enc=tuple(int(c) for c in encoder.num_ch_enc))
@@ -115,8 +127,9 @@ def window_paths(data_path, line, img_ext=".jpg", n_prev=N_PREV_IMAGES):
     return [ED.image_path(data_path, "%s %d %s" % (folder, k, side), img_ext) for k in range(max(0, frame - n_prev), frame + 1)]
 
 
-def predict_v8(opt, device):
-    """-> (N,1,h,w) scaled disparities in test_files.txt order: one window per test file, --batch_size windows in lockstep."""
+def predict_windows(opt, device):
+    """v8 / v10 -> (N,1,h,w) scaled disparities in test_files.txt order: one window per test file, --batch_size windows in
+    lockstep."""
     encoder, lstm, decoder, height, width = load_networks(opt, device)
     lines = ED.readlines(os.path.join(opt.splits_dir, opt.eval_split, "test_files.txt"))
     img_ext = ".png" if getattr(opt, "png", False) else ".jpg"
@@ -133,8 +146,8 @@ def predict_v8(opt, device):
 
 def predict(opt, device):
     """-> (N,1,h,w) scaled disparities in test_files.txt order."""
-    if getattr(opt, "gru_version", "v5") == "v8":
-        return predict_v8(opt, device)
+    if getattr(opt, "gru_version", "v5") in WINDOWED:
+        return predict_windows(opt, device)
     encoder, gru, decoder, height, width = load_networks(opt, device)
     lines = ED.readlines(os.path.join(opt.splits_dir, opt.eval_split, "test_files.txt"))
     img_ext = ".png" if getattr(opt, "png", False) else ".jpg"
@@ -163,9 +176,9 @@ def load_gt_depths(opt):
 
 
 def evaluate(opt):
-    """evaluate_depth_gru_fusion.py:622-853 for gru_version v5 / v8.  Returns depthcore.evaluate.evaluate_depth's result, or None when
+    """evaluate_depth_gru_fusion.py:622-853 for gru_version v5 / v8 and evaluate_depth_gru_fusion_my_v.py for v10.  Returns depthcore.evaluate.evaluate_depth's result, or None when
     nothing is scored."""
-    check_options(opt, tuple(VERSIONS))
+    check_options(opt, tuple(VERSIONS) + tuple(MY_V_VERSIONS))
     device = torch.device("cuda", torch.cuda.current_device())
     pred_disps = predict(opt, device) if opt.ext_disp_to_eval is None else ED.load_external_disparities(opt, device)
     return ED.finish(opt, pred_disps, load_gt_depths)

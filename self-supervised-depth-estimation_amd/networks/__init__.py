@@ -16,3 +16,4 @@ from .pose_cnn import PoseCNN
 from .fusion import Fusion_v3, FeatureFusionBlock_v3, ResidualAttentionUnit, AttentionConv, UpscalePS
 from .convgru import ConvGRUBlocks_v5, ConvGRUModel_v1, ConvGRUCell
 from .convlstm import ConvGRUBlocks_v8, ConvLSTMModel_v1, ConvLSTMCell_v1, FeatureFusionBlock_v2
+from .convgru_c2f import ConvGRUBlocks_v9

@@ -100,12 +100,12 @@ _BUILD = [
     ("torch_adam", int, 0, [0, 1]),              # 1: torch.optim.Adam(fused=True) instead of the depthcore Adam kernel (A/B)
     ("nets_dtype", str, "f32", ["f32", "bf16"]),  # matrix-core precision of the networks' convolutions (bf16: BASELINE configs[4] policy; the loss stays fp32)
     ("imagenet_weights", str, None, None),       # weights_init=pretrained: path of the torchvision resnet{N}-*.pth (no download here)
-    ("gru", str, None, [None, "v5", "v8"]),      # front-end of trainer_gru.py (run_gru_v5 / run_gru_v8; sequences of len_sequence frames)
+    ("gru", str, None, [None, "v5", "v8", "v10"]),  # front-end of trainer_gru.py (run_gru_v5 / run_gru_v8 / run_gru_v9_v10; sequences of len_sequence frames)
     ("seq_batch", int, 1, None),                 # ConvGRU front-end: sequence items per optimiser step, advanced in lockstep (batch_size stays 1)
     ("splits_dir", str, os.path.join(_HERE, "splits"), None),  # evaluate_depth.py: <splits_dir>/<eval_split>/{test_files.txt, gt_depths.npz} (none ship here)
     ("eval_json", str, None, None),              # evaluate_depth.py: also write the results to this JSON file
     ("log_images", int, 0, None),                # items per log step whose image panel is written to <log_path>/<mode>/images/ (Trainer.log_images); 0 = off, the reference writes 4
-    ("n_prev_images", int, 6, None),             # evaluate_depth_gru.py --gru_version v8: frames before a test file's own in its window (the reference's constant, evaluate_depth_gru_fusion.py:558)
+    ("n_prev_images", int, 6, None),             # evaluate_depth_gru.py --gru_version v8 / v10: frames before a test file's own in its window (6: the reference's constant for v8, evaluate_depth_gru_fusion.py:558; its constant for v10 is 10)
     ("frame_cache_gb", float, 0.0, None),        # train.py: GiB of HBM for the training loader's cache of resized frames (depthcore/frame_cache.py); 0 = off
 ]
 

@@ -4,7 +4,8 @@
 MonodepthOptions -> Trainer -> train_sequences(): a single process on one GPU.  The drive lists are read from
 `<splits_dir>/<split>/{train,val}_sequences.txt` ("date/drive" per line; none ship with the project); `--len_sequence`,
 `--train_n_tuples`, `--test_n_tuples` and `--h_s_epoch` are the reference's.  One sequence item is one step: the batch size is 1.
-`--gru_version` picks the front-end: `v5` (ConvGRU inside the skip connections, the default) or `v8` (ConvLSTM behind the decoder).
+`--gru_version` picks the front-end: `v5` (ConvGRU inside the skip connections, the default) `v8` (ConvLSTM behind the decoder)
+or `v10` (ConvGRU cells in v8's coarse-to-fine arrangement).
 `--seq_batch S` (beyond the reference, default 1) trains S sequence items per step in lockstep: the loss and the BatchNorm
 statistics run over the S * len_sequence frames, every parameter is shared, the learning rate is not rescaled."""
 import sys
@@ -18,7 +19,7 @@ def main(argv=None):
         sys.exit("train_gru.py: --use_stereo is not supported: the trainer has no stereo loss (frame_ids with 's' are never "
                  "supervised); train on the monocular frames [0, -1, 1]")
     if not opts.gru:
-        opts.gru = opts.gru_version         # trainer_gru.py:128-144: "v5" (the default) or "v8"; the Trainer refuses the others
+        opts.gru = opts.gru_version         # trainer_gru.py:128-144: "v5" (the default), "v8" or "v10"; the Trainer refuses the others
     opts.batch_size = 1                     # trainer_gru.py:206-240: DataLoader(batch_size=1), one sequence per step
     # (opts.seq_batch sequences per step is its own option: batch_size keeps the reference's meaning and value)
     from trainer import Trainer

@@ -26,6 +26,8 @@ sequence pass through `networks.ConvGRUBlocks_v5`, and the loss runs on the sequ
 come from `build_sequence_loaders` (items already stacked by the data step) and its loop is `train_sequences` (train_gru.py).
 `opt.gru = "v8"` is trainer_gru.py:402-460 (`run_gru_v8`) on the same data and loop: the decoder runs with pre_disp=True and
 `networks.ConvGRUBlocks_v8` (four ConvLSTM cells + fusion blocks, coarse to fine) turns its feature maps into the disparities.
+`opt.gru = "v10"` is trainer_gru.py:716-764 (`run_gru_v9_v10`): v8's wiring with `networks.ConvGRUBlocks_v9(attention=False)`,
+four ConvGRU cells in the ConvLSTM cells' place ("v9", the same block with attention units, is not built).
 `opt.model = "rn_encoder_with_attention"` (or `"rn_fusion"` together with `opt.fusion = "v3"`) builds the depth encoder as
 `networks.ResnetEncoderAttention` (trainer_dpt.py:78-92); every other value, the default included, builds `ResnetEncoder`.
 """
@@ -96,8 +98,11 @@ class Trainer:
             raise NotImplementedError("fusion front-ends: None (trainer.py) or 'v3' (trainer_fusion_v3.py)")
         if self.opt.fusion and -2 not in self.opt.frame_ids:
             raise ValueError("the Fusion_v3 front-end stacks frames [-2, -1, 0]: frame_ids must be [0, -2, -1, 1]")
-        if getattr(self.opt, "gru", None) not in (None, "v5", "v8"):
-            raise NotImplementedError("ConvGRU front-ends: None, 'v5' (trainer_gru.py run_gru_v5) or 'v8' (run_gru_v8)")
+        if getattr(self.opt, "gru", None) not in (None, "v5", "v8", "v10"):
+            raise NotImplementedError("ConvGRU front-ends: None, 'v5' (trainer_gru.py run_gru_v5), 'v8' (run_gru_v8) or 'v10' "
+                                      "(run_gru_v9_v10 without attention; 'v9', its attention variant, is not built)")
+        # the front-ends BEHIND the decoder (pre_disp=True), coarse to fine: the ConvLSTM blocks and their ConvGRU counterpart
+        self.c2f = self.opt.gru in ("v8", "v10")
         if self.opt.gru and self.opt.fusion:
             raise ValueError("fusion and gru front-ends are separate trainers in the reference; pick one")
         if self.opt.gru and self.opt.batch_size != 1:
@@ -123,6 +128,14 @@ class Trainer:
                 raise NotImplementedError("gru 'v8' runs eagerly: hip_graph capture of the ConvLSTM step is not covered")
             if not self.opt.fused_loss:
                 raise NotImplementedError("gru 'v8' runs the fused loss: the layer-by-layer loss (--fused_loss 0) is not covered")
+        if self.opt.gru == "v10":
+            # the coarse-to-fine ConvGRU front-end, likewise: one sequence per step, eager, on the fused loss
+            if self.seq_batch > 1:
+                raise NotImplementedError("gru 'v10' trains one sequence item per step: seq_batch > 1 (lockstep) covers 'v5' only")
+            if getattr(self.opt, "hip_graph", False):
+                raise NotImplementedError("gru 'v10' runs eagerly: hip_graph capture of the coarse-to-fine ConvGRU step is not covered")
+            if not self.opt.fused_loss:
+                raise NotImplementedError("gru 'v10' runs the fused loss: the layer-by-layer loss (--fused_loss 0) is not covered")
         self.loss_batch = self.opt.batch_size * (self.opt.len_sequence * self.seq_batch if self.opt.gru else 1)
         self.num_scales = len(self.opt.scales)
         self.num_input_frames = len(self.opt.frame_ids)                                   # trainer.py:50-51
@@ -164,6 +177,10 @@ class Trainer:
             self.models["gru"] = networks.ConvGRUBlocks_v8(kernel_size=(3, 3), bias=True, device="cpu", attention=False,
                                                            height=self.opt.height, width=self.opt.width,
                                                            num_ch_dec=tuple(int(c) for c in self.models["depth"].num_ch_dec[:4]))
+        elif self.opt.gru == "v10":                              # trainer_gru.py:149-152
+            self.models["gru"] = networks.ConvGRUBlocks_v9(kernel_size=(3, 3), bias=True, device="cpu", attention=False,
+                                                           height=self.opt.height, width=self.opt.width,
+                                                           num_ch_dec=tuple(int(c) for c in self.models["depth"].num_ch_dec[:4]))
         elif self.opt.gru:                                       # trainer_gru.py:128
             self.models["gru"] = networks.ConvGRUBlocks_v5(kernel_size=(3, 3), bias=True, device="cpu", height=self.opt.height,
                                                            width=self.opt.width,
@@ -189,7 +206,7 @@ class Trainer:
         # in the order the forward runs the modules (GradBuckets exchanges in the reverse of it): with overlap_streams
         # the pose branch is issued first (process_batch), so its gradients are the last ones backward produces
         front = [k for k in ("gru",) if k in self.models]
-        main = ["encoder"] + (["depth"] + front if self.opt.gru == "v8" else front + ["depth"]) + \
+        main = ["encoder"] + (["depth"] + front if self.c2f else front + ["depth"]) + \
             [k for k in ("fusion", "predictive_mask") if k in self.models]
         order = (["pose_encoder", "pose"] + main) if getattr(self.opt, "overlap_streams", False) else (main + ["pose_encoder", "pose"])
         order = [k for k in order if k in self.models] + [k for k in self.models if k not in order]
@@ -415,12 +432,13 @@ class Trainer:
             enc_input = torch.cat([inputs[("color_aug", i, 0)] for i in (-2, -1, 0)], 0)
             features = self.models["encoder"](enc_input)
             outputs = dict(self.models["fusion"](self.models["depth"](features)))
-        elif self.opt.gru == "v8":                               # trainer_gru.py:402-460, batch size 1
-            # encoder -> decoder (pre_disp: its feature maps; the dispconvs are not run and get no gradient) -> ConvLSTM blocks
+        elif self.c2f:                                           # trainer_gru.py:402-460 (v8), :716-764 (v10), batch size 1
+            # encoder -> decoder (pre_disp: its feature maps; the dispconvs are not run and get no gradient) -> the blocks
             features = self.models["encoder"](inputs[("color", 0, 0)])
             if features[0].shape[0] != self.opt.len_sequence:
-                raise ValueError("a ConvLSTM batch is ONE sequence of len_sequence = %d frames, got %d rows"
-                                 % (self.opt.len_sequence, features[0].shape[0]))
+                raise ValueError("a %s batch is ONE sequence of len_sequence = %d frames, got %d rows"
+                                 % ("ConvLSTM" if self.opt.gru == "v8" else "coarse-to-fine ConvGRU", self.opt.len_sequence,
+                                    features[0].shape[0]))
             outputs = dict(self.models["gru"].run_sequence(self.models["depth"](features, pre_disp=True)))
         elif self.opt.gru:                                       # trainer_gru.py:595-644, batch size 1
             features = self.models["encoder"](inputs[("color", 0, 0)])
