@@ -1158,6 +1158,25 @@ size_t dc_disp_render_ws_bytes(int N, int h, int w, int Ho, int Wo);
 int dc_disp_render(const float* disp, const uint8_t* lut, uint8_t* rgb, float* range, int N, int h, int w, int Ho, int Wo, double q,
                    void* ws, size_t ws_bytes, void* stream);
 
+/* One colour range for a whole drive (test_sequence.py; csrc/render.hip): per-image ranges make a depth video flicker.
+ * dc_disp_range_pooled: range (2) fp32 = (vmin, vmax) of the POOLED values of all N upsampled maps -- the arithmetic of
+ *   dc_disp_render's range above with n = N*Ho*Wo and s the N*Ho*Wo values sorted ascending: vmin = s[0], vmax numpy's _lerp at
+ *   the fp64 virtual index (n-1) * (q/100) between exact order statistics.  The same key map, the same upsample (recomputed in
+ *   every pass, never stored) and the same three radix passes, over ONE histogram and ONE selection state (not indexed by
+ *   image); a block keeps its bins in LDS over all the tiles it walks before they reach memory.  Integer histograms and integer
+ *   atomics only: two calls give the same bits; at N = 1 the result is dc_disp_render's range of that image, bit for bit.
+ *   Seven launches, no host synchronisation.  ws: dc_disp_range_pooled_ws_bytes(...) bytes (0 for a bad shape), independent
+ *   of N; DC_EWORKSPACE when ws_bytes is smaller.  DC_EINVAL before any launch: N*Ho*Wo >= 2^32 (ranks and counts are 32-bit),
+ *   N > 65535, q outside [0, 100], a size < 1, a null pointer.
+ * dc_disp_render_fixed: the colouring of dc_disp_render (its last two lines) with (vmin, vmax) = range[0], range[1] read from
+ *   device memory and shared by all N images; no selection pass, ONE launch, no workspace.  rgb 4-byte aligned.  DC_EINVAL: a
+ *   size < 1, N > 65535, a null pointer, a misaligned rgb. */
+size_t dc_disp_range_pooled_ws_bytes(int N, int h, int w, int Ho, int Wo);
+int dc_disp_range_pooled(const float* disp, float* range, int N, int h, int w, int Ho, int Wo, double q, void* ws, size_t ws_bytes,
+                         void* stream);
+int dc_disp_render_fixed(const float* disp, const uint8_t* lut, const float* range, uint8_t* rgb, int N, int h, int w, int Ho, int Wo,
+                         void* stream);
+
 /* ------------------------------------------------------------------ velodyne depth maps (raw drives)
  * generate_depth_map of kitti_utils.py:46-98, the resize and flip of datasets/kitti_dataset.py:71-86 (get_depth) and the maps of
  * export_gt_depth.py, for a batch of n_img scans in one call (csrc/lidar.hip).

@@ -14,6 +14,9 @@
 //                       last histogram, else the smallest key above the prefix.  numpy's _lerp of the two in fp64 -> range
 //   colour              a run of four pixels per thread over the flat (image, pixel) index: three whole dwords per store,
 //                       whatever the image size; the table sits in LDS as 256 packed words
+// One range for a whole drive (dc_disp_range_pooled, dc_disp_render_fixed): the same passes over the values of all N images as
+// ONE population -- one histogram, one selection state, rank floor((N n - 1) q/100), one select block -- which write a single
+// (vmin, vmax) pair; the colour pass alone then renders any number of images against a pair read from device memory.
 // Histograms and minima are integer atomics (order-independent), there is no floating-point atomic: two calls give the same
 // bytes.  No fast-math; the percentile interpolation and the normalisation are compiled with `fp contract(off)` at function
 // scope (as eval.hip's numpy expressions), so their fp64 products, sums and the division and the fp32 roundings are the stated
@@ -76,38 +79,45 @@ __device__ __forceinline__ unsigned rd_wave_min(unsigned m) {
 
 // pass 0: bin = key >> 20, and the image's smallest key;  pass 1: (key >> 8) & 0xfff of keys whose top 12 bits are the selected
 // prefix;  pass 2: key & 0xff of keys whose top 24 bits are, and the smallest key above that prefix.
-template <int PASS>
+// POOLED (dc_disp_range_pooled): the N images are ONE population -- one histogram and one selection state for all of them
+// (slot 0, not indexed by image), and a block walks the tiles blockIdx.x, blockIdx.x + gridDim.x, .. of its image, so that a
+// long drive reaches the shared histogram with a bounded number of blocks; its bins stay private in LDS until the walk ends.
+template <int PASS, bool POOLED = false>
 __global__ __launch_bounds__(RD_THREADS) void rd_hist_kernel(RdArgs a, unsigned* __restrict__ hist, RdState* __restrict__ st) {
     __shared__ unsigned sh[RD_BINS];
     constexpr int NB = PASS == 2 ? 256 : RD_BINS;
-    const int b = blockIdx.y;
+    const int b = blockIdx.y, slot = POOLED ? 0 : b;
     for (int i = threadIdx.x; i < NB; i += RD_THREADS) sh[i] = 0u;
-    const unsigned pre = PASS > 0 ? st[b].prefix : 0u;
+    const unsigned pre = PASS > 0 ? st[slot].prefix : 0u;
     __syncthreads();
     unsigned m = 0xffffffffu;
-    const int j0 = blockIdx.x * RD_TILE;
-    for (int k = 0; k < RD_PPT; ++k) {
-        const int j = j0 + k * RD_THREADS + threadIdx.x;
-        if (j >= a.n) continue;
-        const unsigned key = rd_key(rd_pixel(a, b, j));
-        if (PASS == 0) {
-            atomicAdd(&sh[key >> 20], 1u);
-            m = min(m, key);
-        } else if (PASS == 1) {
-            if ((key >> 20) == pre) atomicAdd(&sh[(key >> 8) & 0xfffu], 1u);
-        } else {
-            if ((key >> 8) == pre) atomicAdd(&sh[key & 0xffu], 1u);
-            else if ((key >> 8) > pre) m = min(m, key);
+    int tile = blockIdx.x;                                         // < a.nbx: the grid's x extent is at most nbx
+    do {
+        const int j0 = tile * RD_TILE;
+        for (int k = 0; k < RD_PPT; ++k) {
+            const int j = j0 + k * RD_THREADS + threadIdx.x;
+            if (j >= a.n) continue;
+            const unsigned key = rd_key(rd_pixel(a, b, j));
+            if (PASS == 0) {
+                atomicAdd(&sh[key >> 20], 1u);
+                m = min(m, key);
+            } else if (PASS == 1) {
+                if ((key >> 20) == pre) atomicAdd(&sh[(key >> 8) & 0xfffu], 1u);
+            } else {
+                if ((key >> 8) == pre) atomicAdd(&sh[key & 0xffu], 1u);
+                else if ((key >> 8) > pre) m = min(m, key);
+            }
         }
-    }
+        tile += gridDim.x;
+    } while (POOLED && tile < a.nbx);
     if (PASS != 1) {
         m = rd_wave_min(m);
-        if ((threadIdx.x & 63) == 0 && m != 0xffffffffu) atomicMin(PASS == 0 ? &st[b].key_min : &st[b].min_above, m);
+        if ((threadIdx.x & 63) == 0 && m != 0xffffffffu) atomicMin(PASS == 0 ? &st[slot].key_min : &st[slot].min_above, m);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < NB; i += RD_THREADS) {
         const unsigned c = sh[i];
-        if (c) atomicAdd(&hist[(size_t)b * RD_BINS + i], c);
+        if (c) atomicAdd(&hist[(size_t)slot * RD_BINS + i], c);
     }
 }
 
@@ -178,7 +188,9 @@ __device__ __forceinline__ int rd_index(float d, float vmin, float vmax, double 
 }
 
 // run r covers pixels 4r .. 4r+3 of the flat (image, pixel) index, bytes 12r .. 12r+11 of rgb: dword aligned for any Ho x Wo.
-// A run may cross into the next image, whose range is then loaded.
+// A run may cross into the next image, whose range is then loaded.  FIXED (dc_disp_render_fixed): range holds ONE pair, shared
+// by all images.
+template <bool FIXED = false>
 __global__ __launch_bounds__(RD_THREADS) void rd_colour_kernel(RdArgs a, const uint8_t* __restrict__ lut, const float* __restrict__ range,
                                                                uint8_t* __restrict__ rgb) {
     __shared__ unsigned pal[256];
@@ -191,7 +203,7 @@ __global__ __launch_bounds__(RD_THREADS) void rd_colour_kernel(RdArgs a, const u
         const size_t p0 = r * RD_RUN;
         int img = (int)(p0 / (size_t)a.n);
         int pos = (int)(p0 - (size_t)img * a.n);
-        float vmin = range[2 * img], vmax = range[2 * img + 1];
+        float vmin = range[FIXED ? 0 : 2 * img], vmax = range[FIXED ? 1 : 2 * img + 1];
         double den = (double)vmax - (double)vmin;
         const int cnt = (int)min((size_t)RD_RUN, total - p0);
         unsigned c[RD_RUN] = {0u, 0u, 0u, 0u};
@@ -201,9 +213,11 @@ __global__ __launch_bounds__(RD_THREADS) void rd_colour_kernel(RdArgs a, const u
             if (pos == a.n) {
                 ++img;
                 pos = 0;
-                vmin = range[2 * img];
-                vmax = range[2 * img + 1];
-                den = (double)vmax - (double)vmin;
+                if (!FIXED) {
+                    vmin = range[2 * img];
+                    vmax = range[2 * img + 1];
+                    den = (double)vmax - (double)vmin;
+                }
             }
             c[k] = pal[rd_index(rd_pixel(a, img, pos), vmin, vmax, den)];
             ++pos;
@@ -243,6 +257,28 @@ static bool rd_layout(int N, int h, int w, int Ho, int Wo, RdArgs& a, RdLayout& 
     return true;
 }
 
+// numpy's virtual index (n - 1) * (q / 100) in fp64, its floor and the fraction, for a population of n values
+static void rd_rank(RdArgs& a, unsigned long long n, double q) {
+    const double vi = (double)(n - 1) * (q / 100.0);
+    double lo = floor(vi);
+    if (lo > (double)(n - 1)) lo = (double)(n - 1);
+    a.lo = (unsigned)lo;
+    a.hi_same = (unsigned long long)a.lo + 1u > n - 1;
+    a.g = vi - lo;
+}
+
+constexpr int RD_POOL_BLOCKS = 2048;                   // blocks that reach the one pooled histogram, about (ceil: at most N more)
+
+// the pooled population: the same per-image limits, and N * Ho * Wo < 2^32 -- ranks and bin counts are 32-bit
+static bool rd_pool_layout(int N, int h, int w, int Ho, int Wo, RdArgs& a, RdLayout& L) {
+    if (!rd_layout(N, h, w, Ho, Wo, a, L)) return false;
+    if ((unsigned long long)N * (unsigned long long)a.n >= (1ull << 32)) return false;
+    L.hist_words = (size_t)3 * RD_BINS;
+    L.state_off = L.hist_words * sizeof(unsigned);
+    L.bytes = L.state_off + sizeof(RdState);
+    return true;
+}
+
 }  // namespace dc
 
 using namespace dc;
@@ -262,13 +298,7 @@ extern "C" int dc_disp_render(const float* disp, const uint8_t* lut, uint8_t* rg
         return DC_EINVAL;
     if (ws_bytes < L.bytes) return DC_EWORKSPACE;
     a.disp = disp;
-    // numpy's virtual index (n - 1) * (q / 100) in fp64, its floor and the fraction: the same for every image of the call
-    const double vi = (double)(a.n - 1) * (q / 100.0);
-    double lo = floor(vi);
-    if (lo > (double)(a.n - 1)) lo = (double)(a.n - 1);
-    a.lo = (unsigned)lo;
-    a.hi_same = a.lo + 1u > (unsigned)(a.n - 1);
-    a.g = vi - lo;
+    rd_rank(a, (unsigned long long)a.n, q);                    // the same for every image of the call
     hipStream_t st = (hipStream_t)stream;
     unsigned* hist = (unsigned*)ws;
     RdState* state = (RdState*)((char*)ws + L.state_off);
@@ -283,7 +313,49 @@ extern "C" int dc_disp_render(const float* disp, const uint8_t* lut, uint8_t* rg
     hipLaunchKernelGGL(rd_select_kernel<2>, dim3(N), dim3(RD_THREADS), 0, st, a, hist + 2 * hw, state, range);
     const size_t runs = ((size_t)N * a.n + RD_RUN - 1) / RD_RUN;
     const int blocks = (int)std::min<size_t>((runs + RD_THREADS - 1) / RD_THREADS, RD_MAX_BLOCKS);
-    hipLaunchKernelGGL(rd_colour_kernel, dim3(blocks), dim3(RD_THREADS), 0, st, a, lut, range, rgb);
+    hipLaunchKernelGGL(rd_colour_kernel<false>, dim3(blocks), dim3(RD_THREADS), 0, st, a, lut, range, rgb);
+    DC_CHECK_LAUNCH();
+    return DC_OK;
+}
+
+extern "C" size_t dc_disp_range_pooled_ws_bytes(int N, int h, int w, int Ho, int Wo) {
+    RdArgs a;
+    RdLayout L;
+    return rd_pool_layout(N, h, w, Ho, Wo, a, L) ? L.bytes : 0;
+}
+
+extern "C" int dc_disp_range_pooled(const float* disp, float* range, int N, int h, int w, int Ho, int Wo, double q, void* ws,
+                                    size_t ws_bytes, void* stream) {
+    RdArgs a;
+    RdLayout L;
+    if (!rd_pool_layout(N, h, w, Ho, Wo, a, L) || !disp || !range || !ws || !(q >= 0.0 && q <= 100.0)) return DC_EINVAL;
+    if (ws_bytes < L.bytes) return DC_EWORKSPACE;
+    a.disp = disp;
+    rd_rank(a, (unsigned long long)N * (unsigned long long)a.n, q);
+    hipStream_t st = (hipStream_t)stream;
+    unsigned* hist = (unsigned*)ws;
+    RdState* state = (RdState*)((char*)ws + L.state_off);
+    const dim3 grid(std::min(a.nbx, (RD_POOL_BLOCKS + N - 1) / N), N);
+    hipLaunchKernelGGL(rd_zero_kernel, dim3((int)((L.hist_words + 255) / 256)), dim3(256), 0, st, hist, L.hist_words, state, 1);
+    hipLaunchKernelGGL((rd_hist_kernel<0, true>), grid, dim3(RD_THREADS), 0, st, a, hist, state);
+    hipLaunchKernelGGL(rd_select_kernel<0>, dim3(1), dim3(RD_THREADS), 0, st, a, hist, state, range);
+    hipLaunchKernelGGL((rd_hist_kernel<1, true>), grid, dim3(RD_THREADS), 0, st, a, hist + RD_BINS, state);
+    hipLaunchKernelGGL(rd_select_kernel<1>, dim3(1), dim3(RD_THREADS), 0, st, a, hist + RD_BINS, state, range);
+    hipLaunchKernelGGL((rd_hist_kernel<2, true>), grid, dim3(RD_THREADS), 0, st, a, hist + 2 * RD_BINS, state);
+    hipLaunchKernelGGL(rd_select_kernel<2>, dim3(1), dim3(RD_THREADS), 0, st, a, hist + 2 * RD_BINS, state, range);
+    DC_CHECK_LAUNCH();
+    return DC_OK;
+}
+
+extern "C" int dc_disp_render_fixed(const float* disp, const uint8_t* lut, const float* range, uint8_t* rgb, int N, int h, int w, int Ho,
+                                    int Wo, void* stream) {
+    RdArgs a;
+    RdLayout L;
+    if (!rd_layout(N, h, w, Ho, Wo, a, L) || !disp || !lut || !range || !rgb || ((uintptr_t)rgb & 3u)) return DC_EINVAL;
+    a.disp = disp;
+    const size_t runs = ((size_t)N * a.n + RD_RUN - 1) / RD_RUN;
+    const int blocks = (int)std::min<size_t>((runs + RD_THREADS - 1) / RD_THREADS, RD_MAX_BLOCKS);
+    hipLaunchKernelGGL(rd_colour_kernel<true>, dim3(blocks), dim3(RD_THREADS), 0, (hipStream_t)stream, a, lut, range, rgb);
     DC_CHECK_LAUNCH();
     return DC_OK;
 }

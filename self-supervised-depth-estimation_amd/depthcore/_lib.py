@@ -193,6 +193,9 @@ def _sig(lib):
         "dc_pose_ate": (i, [p, p, p, i, i, i, p]),
         "dc_disp_render_ws_bytes": (z, [i, i, i, i, i]),
         "dc_disp_render": (i, [p, p, p, p, i, i, i, i, i, c_double, p, z, p]),
+        "dc_disp_range_pooled_ws_bytes": (z, [i, i, i, i, i]),
+        "dc_disp_range_pooled": (i, [p, p, i, i, i, i, i, c_double, p, z, p]),
+        "dc_disp_render_fixed": (i, [p, p, p, p, i, i, i, i, i, p]),
         "dc_lidar_workspace_bytes": (z, [i, i, i]),
         "dc_lidar_depth_maps": (i, [p, z, p, p, i, p, p, p, p, i, i, p, p, z, p]),
         "dc_log_panel_ws_bytes": (z, [i]),

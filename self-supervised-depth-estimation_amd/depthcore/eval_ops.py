@@ -270,6 +270,62 @@ def render_disparity(disp, size, percentile=95.0, lut=None):
     return rgb, rng
 
 
+def _drive_maps(disp, size, what):
+    d = _c(disp.detach())
+    if d.dim() != 4 or d.shape[1] != 1:
+        raise DepthcoreError("%s: (N,1,h,w), got %s" % (what, tuple(d.shape)))
+    N, _, h, w = d.shape
+    Ho, Wo = int(size[0]), int(size[1])
+    if N < 1 or h < 1 or w < 1 or Ho < 1 or Wo < 1:
+        raise DepthcoreError("%s: empty input %s or target size %s" % (what, tuple(d.shape), (Ho, Wo)))
+    return d, N, h, w, Ho, Wo
+
+
+def disparity_range_pooled(disp, size, percentile=95.0):
+    """ONE (vmin, vmax) for all N maps of a drive (dc_disp_range_pooled): disp (N,1,h,w) -> a (2,) float32 device tensor on the
+    current stream.  render_disparity's range -- the minimum and numpy's `percentile` between exact order statistics -- of the
+    pooled N * Ho * Wo values of the maps upsampled to size = (Ho, Wo); the upsampled maps are never stored.  N * Ho * Wo must
+    stay below 2^32.  Bitwise reproducible; no host synchronisation.  No gradient."""
+    L = _lib.lib()
+    d, N, h, w, Ho, Wo = _drive_maps(disp, size, "disparity_range_pooled")
+    q = float(percentile)
+    if not 0.0 <= q <= 100.0:
+        raise DepthcoreError("disparity_range_pooled: percentile must be in [0, 100], got %r" % (percentile,))
+    nws = L.dc_disp_range_pooled_ws_bytes(N, h, w, Ho, Wo)
+    if nws == 0:
+        raise DepthcoreError("disparity_range_pooled: unsupported shape %s -> %s (N * Ho * Wo must be below 2^32, N at most 65535)"
+                             % (tuple(d.shape), (Ho, Wo)))
+    ws = torch.empty(nws, dtype=torch.uint8, device=d.device)
+    rng = torch.empty(2, dtype=torch.float32, device=d.device)
+    check(L.dc_disp_range_pooled(ptr(d), ptr(rng), N, h, w, Ho, Wo, q, ws.data_ptr(), nws, stream(d)), "dc_disp_range_pooled")
+    return rng
+
+
+def render_disparity_fixed(disp, size, rng, lut=None, out=None):
+    """render_disparity's colouring against ONE range for all images (dc_disp_render_fixed, one launch): disp (N,1,h,w), rng a
+    (2,) float32 device tensor (vmin, vmax) -- disparity_range_pooled's, or any other -- -> rgb (N,Ho,Wo,3) uint8 on the device
+    (`out`: a contiguous uint8 device tensor of at least N*Ho*Wo*3 elements to render into).  Values above vmax take the last
+    colour, values below vmin the first; vmin == vmax gives the first colour everywhere.  No gradient."""
+    L = _lib.lib()
+    d, N, h, w, Ho, Wo = _drive_maps(disp, size, "render_disparity_fixed")
+    if not torch.is_tensor(rng) or rng.numel() != 2 or rng.dtype != torch.float32 or rng.device != d.device:
+        raise DepthcoreError("render_disparity_fixed: rng must be a (2,) float32 tensor on %s" % (d.device,))
+    if lut is None:
+        lut = magma_lut(d.device)
+    if tuple(lut.shape) != (256, 3) or lut.dtype != torch.uint8 or lut.device != d.device:
+        raise DepthcoreError("render_disparity_fixed: lut must be a (256,3) uint8 tensor on %s, got %s %s on %s"
+                             % (d.device, tuple(lut.shape), lut.dtype, lut.device))
+    nrgb = N * Ho * Wo * 3
+    if out is None:
+        out = torch.empty(nrgb, dtype=torch.uint8, device=d.device)
+    if out.dtype != torch.uint8 or out.device != d.device or not out.is_contiguous() or out.numel() < nrgb:
+        raise DepthcoreError("render_disparity_fixed: out must be a contiguous uint8 tensor of %d elements on %s" % (nrgb, d.device))
+    rgb = out.view(-1)[:nrgb].view(N, Ho, Wo, 3)
+    check(L.dc_disp_render_fixed(ptr(d), ptr(_c(lut), torch.uint8), ptr(_c(rng).view(2)), ptr(rgb, torch.uint8), N, h, w, Ho, Wo,
+                                 stream(d)), "dc_disp_render_fixed")
+    return rgb
+
+
 # ----------------------------------------------------------------------------------------------
 # training-log image panels: the pictures of trainer.py:666-698, composed on the device
 # ----------------------------------------------------------------------------------------------

@@ -769,3 +769,186 @@ def predict_disparities_fusion(encoder, decoder, fusion, triplets, min_depth=0.1
     if not outs:
         raise ValueError("predict_disparities_fusion: no triplets")
     return outs[0] if len(outs) == 1 else ops.stack_frames([outs])[0]
+
+
+# ---- whole drives: every frame of a video scored, the work shared between overlapping windows (test_sequence.py) ---------------
+def drive_window_plan(n_frames, n_prev, streams):
+    """The lockstep schedule of a drive's windows, as pure arithmetic: frame t of a drive of `n_frames` is predicted from the
+    window of frames max(0, t - n_prev) .. t (evaluate_depth_gru.window_paths' protocol).  -> [(t0, t1, ids, steps)], one entry
+    per group of up to `streams` windows, in frame order:
+      t0, t1    the group's targets are frames t0 .. t1 - 1;
+      ids       the target of every stream, in window_groups' order (by window length, descending and stable), so the streams
+                alive at a step are a prefix;
+      steps     steps[j][b]: the frame that stream b reads at step j, for the streams alive then.  The windows are right
+                aligned: all of them read their own target at the last step, where the head runs once at full width.
+    The ragged windows (t < n_prev) are grouped apart from the full ones.  In a group of full windows ids is t0 .. t1 - 1 and
+    step j reads frames t0 - n_prev + j .. t1 - 1 - n_prev + j: consecutive, ascending -- a slice of a frame-ordered cache."""
+    if n_frames < 1 or n_prev < 0 or streams < 1:
+        raise ValueError("drive_window_plan: n_frames >= 1, n_prev >= 0 and streams >= 1, got %r, %r, %r" % (n_frames, n_prev, streams))
+    head = min(n_prev, n_frames)
+    cuts = [(t0, min(t0 + streams, head)) for t0 in range(0, head, streams)]
+    cuts += [(t0, min(t0 + streams, n_frames)) for t0 in range(head, n_frames, streams)]
+    plan = []
+    for t0, t1 in cuts:
+        lengths = [min(t, n_prev) + 1 for t in range(t0, t1)]
+        (local, widths), = window_groups(lengths, len(lengths))
+        ids = [t0 + i for i in local]
+        L = len(widths)
+        plan.append((t0, t1, ids, [[t - (L - 1) + j for t in ids[:B]] for j, B in enumerate(widths)]))
+    return plan
+
+
+class _MapRing:
+    """The decoder maps of the last `size` frames of a drive on the device, frame f in slot f % size, and a mirror of the first
+    `mirror` slots behind the last one: any run of up to mirror + 1 consecutive frames is ONE slice of the arrays, also where
+    it runs over the ring's end.  A frame is copied in once (twice when its slot is mirrored); reading copies nothing."""
+
+    def __init__(self, like, size, mirror):
+        self.size, self.mirror = int(size), int(mirror)
+        self.maps = [torch.empty((self.size + self.mirror,) + tuple(m.shape[1:]), dtype=torch.float32, device=m.device) for m in like]
+
+    def store(self, first, maps):
+        """maps[s][i] is frame first + i."""
+        maps = [m if m.is_contiguous() else m.contiguous() for m in maps]
+        n, done, src, dst = maps[0].shape[0], 0, [], []
+        while done < n:
+            p = (first + done) % self.size
+            k = min(n - done, self.size - p)
+            spans = [(p, k)] + ([(self.size + p, min(p + k, self.mirror) - p)] if p < self.mirror else [])
+            for at, m in spans:
+                src += [x[done:done + m] for x in maps]
+                dst += [r[at:at + m] for r in self.maps]
+            done += k
+        ops.copy_segments(src, dst)
+
+    def run(self, first, B):
+        """Frames first .. first + B - 1 (B <= mirror + 1) as views."""
+        p = first % self.size
+        return [r[p:p + B] for r in self.maps]
+
+    def rows(self, frames):
+        """Any frames, gathered (stock indexing): the ragged groups at the head of a drive."""
+        idx = torch.tensor([f % self.size for f in frames], dtype=torch.long, device=self.maps[0].device)
+        return [r.index_select(0, idx) for r in self.maps]
+
+
+def _drive_chunk(batch_fn, lo, hi, shape):
+    x = batch_fn(lo, hi)
+    _frames_ok(x, "predict_disparities_drive", shape)
+    if x.shape[0] != hi - lo:
+        raise _lib.DepthcoreError("predict_disparities_drive: batch_fn(%d, %d) returned %d frames" % (lo, hi, x.shape[0]))
+    return x if x.is_contiguous() else x.contiguous()
+
+
+def _drive_windows(encoder, decoder, front, n_frames, batch_fn, n_prev, streams, chunk, min_depth, max_depth):
+    plan = drive_window_plan(n_frames, n_prev, streams)
+    S = min(streams, n_frames)
+    out = ring = shape = None
+    hi = 0
+    with _EvalMode(encoder, decoder, front):
+        wp = window_predictor_class(front)(encoder, decoder, front, S, min_depth, max_depth)
+        for g, (t0, t1, ids, steps) in enumerate(plan):
+            while hi < t1:                                       # every frame passes the encoder and the decoder once, here
+                nxt = min(hi + chunk, n_frames)
+                x = _drive_chunk(batch_fn, hi, nxt, shape)
+                shape = tuple(x.shape[2:])
+                maps = wp._maps(x, "predict_disparities_drive")
+                if ring is None:
+                    ring = _MapRing(maps, min(n_prev + S + chunk, n_frames), S - 1)
+                ring.store(hi, maps)
+                hi = nxt
+            if g:
+                wp.reset()
+            for j, frames in enumerate(steps):
+                B = len(frames)
+                dec = ring.run(frames[0], B) if frames == list(range(frames[0], frames[0] + B)) else ring.rows(frames)
+                disp = wp._recur(dec, j == len(steps) - 1)
+            if out is None:
+                out = torch.empty((n_frames,) + tuple(disp.shape[1:]), dtype=torch.float32, device=disp.device)
+            if ids == list(range(t0, t1)):
+                _scaled_disparity(disp, out[t0:t1], False, min_depth, max_depth)
+            else:
+                dst = torch.empty_like(disp)
+                _scaled_disparity(disp, dst, False, min_depth, max_depth)
+                ops.copy_segments([dst[b] for b in range(len(ids))], [out[t] for t in ids])
+    return out
+
+
+def _drive_v5(encoder, decoder, gru, n_frames, batch_fn, chunk, min_depth, max_depth):
+    out = fused = shape = None
+    with _EvalMode(encoder, gru, decoder):
+        sp = SequencePredictor(encoder, gru, decoder, 1, min_depth, max_depth)        # one stream: the states live there
+        for lo in range(0, n_frames, chunk):
+            hi = min(lo + chunk, n_frames)
+            x = _drive_chunk(batch_fn, lo, hi, shape)
+            shape = tuple(x.shape[2:])
+            feats = [f if f.is_contiguous() else f.contiguous() for f in encoder(x)]
+            if fused is None:
+                fused = [torch.empty((min(chunk, n_frames),) + tuple(f.shape[1:]), dtype=torch.float32, device=f.device) for f in feats]
+                out = torch.empty((n_frames, 1) + shape, dtype=torch.float32, device=x.device)
+            for i in range(hi - lo):                             # the recurrence, in order; the states carry over to the next chunk
+                ops.copy_segments(sp._fuse([f[i:i + 1] for f in feats]), [u[i:i + 1] for u in fused])
+            disp = decoder([u[:hi - lo] for u in fused])[("disp", 0)]
+            _scaled_disparity(disp, out[lo:hi], False, min_depth, max_depth)
+    return out
+
+
+def predict_disparities_drive(encoder, decoder, front, n_frames, batch_fn, n_prev=6, streams=16, chunk=16, min_depth=0.1, max_depth=100.0):
+    """A recurrent model on the `n_frames` consecutive frames of one drive -> (n_frames,1,h,w) scaled disparities in frame
+    order, on the device.  `front`: a ConvGRUBlocks_v5, ConvGRUBlocks_v8 or ConvGRUBlocks_v9(attention=False).
+    batch_fn(lo, hi) -> frames lo .. hi - 1 as a (hi - lo,3,h,w) float32 device tensor; called once per chunk of `chunk`
+    consecutive frames, in order.  Contract: predict_disparities'.
+
+    v8 / v10: frame t is predicted from the window of frames max(0, t - n_prev) .. t, started from the learned initial states
+    -- what predict_disparities_windows computes for those windows, without sending a frame through the encoder and the
+    decoder once per window it belongs to.  Every frame passes encoder -> decoder(pre_disp) exactly ONCE, `chunk` frames a
+    batch; its four decoder maps stay on the device in a ring of n_prev + streams + chunk frames (about 15 MB per frame at
+    192 x 640; plus streams - 1 mirrored slots, so that a step's frames are always one slice) until no later window reads
+    them.  The windows of `streams` consecutive targets advance in lockstep through WindowPredictor / GruWindowPredictor on
+    drive_window_plan's schedule: in a group of full windows a step's decoder maps are a slice of the ring -- no gather, no
+    copy --; the ragged groups of the first n_prev frames gather their rows.  One reset and one head per group.
+
+    v5: one stream whose hidden states are carried along the whole drive from the learned h0 (n_prev and streams are not
+    used).  Per chunk the encoder runs once on all its frames, the recurrence walks them in order (SequencePredictor's fused
+    step at width 1, the states carried across chunks), and the decoder runs once on the chunk."""
+    if n_frames < 1 or n_prev < 0 or streams < 1 or chunk < 1:
+        raise ValueError("predict_disparities_drive: n_frames, streams, chunk >= 1 and n_prev >= 0, got %r, %r, %r, %r"
+                         % (n_frames, streams, chunk, n_prev))
+    n_frames, n_prev, streams, chunk = int(n_frames), int(n_prev), int(streams), int(chunk)
+    if hasattr(front, "cgru_4"):                                 # ConvGRUBlocks_v5: a cell per encoder level
+        return _drive_v5(encoder, decoder, front, n_frames, batch_fn, chunk, min_depth, max_depth)
+    return _drive_windows(encoder, decoder, front, n_frames, batch_fn, n_prev, streams, chunk, min_depth, max_depth)
+
+
+def render_drive(pred, size, percentile=95.0, chunk=64, lut=None):
+    """The colour images of a drive under ONE range, so that a surface keeps its colour from frame to frame: -> (images, (vmin,
+    vmax)), images a host uint8 array (N, Ho, Wo, 3) and the pair two np.float32.
+
+    pred: (N,1,h,w) float32 disparities at network resolution -- a device tensor (491 KB per frame at 192 x 640), or host data
+    that is copied over.  The range is ops.disparity_range_pooled's, computed once over all frames at size = (Ho, Wo); the
+    pictures are rendered `chunk` at a time (ops.render_disparity_fixed, one launch) and leave through one pinned buffer."""
+    if not torch.is_tensor(pred):
+        pred = torch.from_numpy(np.ascontiguousarray(pred, np.float32))
+    if not pred.is_cuda:
+        pred = pred.to(torch.device("cuda", torch.cuda.current_device()))
+    if pred.dtype != torch.float32 or pred.dim() != 4 or pred.shape[1] != 1 or pred.shape[0] < 1:
+        raise _lib.DepthcoreError("render_drive: pred must be (N,1,h,w) float32 with N >= 1, got %s %s" % (tuple(pred.shape), pred.dtype))
+    if chunk <= 0:
+        raise ValueError("chunk must be positive")
+    d = pred if pred.is_contiguous() else pred.contiguous()
+    if lut is not None:
+        lut = (lut if torch.is_tensor(lut) else torch.from_numpy(np.ascontiguousarray(lut, np.uint8))).to(d.device)
+    N, (Ho, Wo) = d.shape[0], (int(size[0]), int(size[1]))
+    rng = ops.disparity_range_pooled(d, (Ho, Wo), percentile)
+    c, nb = min(int(chunk), N), Ho * Wo * 3
+    dev = torch.empty(c * nb, dtype=torch.uint8, device=d.device)
+    pinned = torch.empty(c * nb, dtype=torch.uint8, pin_memory=True)
+    images = np.empty((N, Ho, Wo, 3), np.uint8)
+    for c0 in range(0, N, c):
+        k = min(c, N - c0)
+        ops.render_disparity_fixed(d[c0:c0 + k], (Ho, Wo), rng, lut, out=dev)
+        pinned[:k * nb].copy_(dev[:k * nb], non_blocking=True)
+        torch.cuda.current_stream(d.device).synchronize()
+        images[c0:c0 + k] = pinned[:k * nb].numpy().reshape(k, Ho, Wo, 3)
+    vmin, vmax = rng.cpu().numpy()
+    return images, (vmin, vmax)

@@ -20,8 +20,9 @@ from .convs import (ACT_ELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, PAD_REFL
                     stem_supported, wino_conv3x3)
 from .data import seq_item_rows, seq_rows  # noqa: F401
 from .eval_ops import (BENCHMARK_SIZE, STEREO_SCALE_FACTOR, TILE_KINDS, TRAINER_CROP, _MAGMA, _PROTOCOLS, _depth_errors,  # noqa: F401
-                       _render_disparity, depth_errors, depth_png16, eigen_crop, flip_concat, lidar_depth_maps,
-                       lidar_depth_maps_staged, log_panels, magma_lut, pose_ate, post_process_disparity, render_disparity)
+                       _render_disparity, depth_errors, depth_png16, disparity_range_pooled, eigen_crop, flip_concat,
+                       lidar_depth_maps, lidar_depth_maps_staged, log_panels, magma_lut, pose_ate, post_process_disparity,
+                       render_disparity, render_disparity_fixed)
 from .layer_ops import (_aligned8, _Backproject, _DispToDepth, _GridSample, _PoseHead, _PoseMatrix, _Project3D, _Smooth, _SSIM,  # noqa: F401
                         _UpsampleBilinear, _UpsampleNearest2x, backproject, disp_to_depth, grid_sample_border, pix_coords,
                         pose_head, pose_matrix, project3d, smooth_loss, ssim, upsample_bilinear, upsample_nearest2x)
