@@ -7,7 +7,7 @@
 // the forward read or wrote: nothing but cc and c_cur (cell) and pre (hand-over) is kept per frame.  Every thread owns the
 // elements it writes: no atomics, two runs give the same bits.  sigmoid and tanh are the accurate expf / tanhf (not __expf):
 // the states are carried over the frames of a sequence.
-#include "lstm_dev.h"            // lstm_sigmoid, lstm_fwd1, handover_pre, handover_d, LSTM_BLOCK, lstm_grid, all16: shared with lstm_infer.hip, gru_c2f.hip
+#include "c2f_dev.h"             // the hand-over walk; through it lstm_dev.h: lstm_sigmoid, lstm_fwd1, LSTM_BLOCK, lstm_grid
 
 namespace dc {
 
@@ -101,108 +101,38 @@ __global__ __launch_bounds__(LSTM_BLOCK) void lstm_cell_bwd_kernel(const float* 
     }
 }
 
-// ---- coarse-to-fine hand-over ---------------------------------------------------------------------------------------------
-// PixelShuffle(2): up[b, q, 2y + i, 2x + j] = tanh(pre[b, 4q + 2i + j, y, x])   (handover_pre: lstm_dev.h)
-// d(pre pre-ReLU) from the two consumers of pre: handover_d (lstm_dev.h)
-
-// Vector form (w % 4 == 0, 16-byte aligned bases): a thread takes the four channels 4q..4q+3 at four neighbouring pixels of a
-// row: 12 float4 loads, 4 float4 stores of pre and 4 float4 stores of up (two output rows of eight pixels).
-// items = B * (C/4) * h * (w/4)
-__global__ __launch_bounds__(LSTM_BLOCK) void lstm_handover_fwd_vec_kernel(const float* __restrict__ a, const float* __restrict__ h_prev,
-                                                                          const float* __restrict__ h_new, float* __restrict__ pre,
-                                                                          float* __restrict__ up, unsigned items, int h, int w) {
-    const unsigned w4 = w >> 2, P = (unsigned)h * w;
-    for (unsigned it = blockIdx.x * LSTM_BLOCK + threadIdx.x; it < items; it += gridDim.x * LSTM_BLOCK) {
-        const unsigned x4 = it % w4, r = it / w4, y = r % h, bq = r / h;          // bq = b * (C/4) + q
-        const size_t in0 = (size_t)bq * 4 * P + (size_t)y * w + 4 * x4;
-        float4 p[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const size_t o = in0 + (size_t)k * P;
-            const float4 va = *reinterpret_cast<const float4*>(a + o), vp = *reinterpret_cast<const float4*>(h_prev + o);
-            const float4 vn = *reinterpret_cast<const float4*>(h_new + o);
-            p[k] = make_float4(handover_pre(va.x, vp.x, vn.x), handover_pre(va.y, vp.y, vn.y), handover_pre(va.z, vp.z, vn.z),
-                               handover_pre(va.w, vp.w, vn.w));
-            *reinterpret_cast<float4*>(pre + o) = p[k];
-        }
-        if (up) {
-            float* u0 = up + (size_t)bq * 4 * P + (size_t)(2 * y) * (2 * w) + 8 * x4;       // (2h, 2w) plane of 4 P floats
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const float4 e = p[2 * i], o = p[2 * i + 1];                                 // j = 0 / 1
-                float* row = u0 + (size_t)i * 2 * w;
-                *reinterpret_cast<float4*>(row) = make_float4(tanhf(e.x), tanhf(o.x), tanhf(e.y), tanhf(o.y));
-                *reinterpret_cast<float4*>(row + 4) = make_float4(tanhf(e.z), tanhf(o.z), tanhf(e.w), tanhf(o.w));
-            }
-        }
+// ---- coarse-to-fine hand-over: the item walk of c2f_dev.h with the cell "h_new is given" ------------------------------------
+struct GivenCell {
+    const float *h_prev, *h_new;
+    template <class V> struct S { V hp, hn; };
+    template <class V> __device__ __forceinline__ S<V> eval(unsigned, size_t o) const { return {ld<V>(h_prev + o), ld<V>(h_new + o)}; }
+    template <class V> __device__ __forceinline__ void store(size_t, const S<V>&) const {}
+};
+// d_a = d, d_h_prev = d_h_new = d / 2, each where wanted
+struct GivenCellBwd {
+    float *d_a, *d_h_prev, *d_h_new;
+    template <class V> __device__ __forceinline__ void bwd(unsigned, size_t o, V pre, V gp, V gu) const {
+        const V d = handover_d(pre, gp, gu), half = halve(d);
+        if (d_a) st(d_a + o, d);
+        if (d_h_prev) st(d_h_prev + o, half);
+        if (d_h_new) st(d_h_new + o, half);
     }
-}
-// Scalar form: one element of pre per thread; n = B * C * P
+};
+
+// VEC: 12 float4 loads, 4 float4 stores of pre and 4 of up per item; up may be NULL
+template <bool VEC>
 __global__ __launch_bounds__(LSTM_BLOCK) void lstm_handover_fwd_kernel(const float* __restrict__ a, const float* __restrict__ h_prev,
                                                                       const float* __restrict__ h_new, float* __restrict__ pre,
-                                                                      float* __restrict__ up, unsigned n, int h, int w) {
-    const unsigned P = (unsigned)h * w;
-    for (unsigned e = blockIdx.x * LSTM_BLOCK + threadIdx.x; e < n; e += gridDim.x * LSTM_BLOCK) {
-        const float v = handover_pre(a[e], h_prev[e], h_new[e]);
-        pre[e] = v;
-        if (up) {
-            const unsigned x = e % w, r = e / w, y = r % h, bc = r / h, k = bc & 3, bq = bc >> 2;
-            up[(size_t)bq * 4 * P + (size_t)(2 * y + (k >> 1)) * (2 * w) + 2 * x + (k & 1)] = tanhf(v);
-        }
-    }
+                                                                      float* __restrict__ up, unsigned n, int C, int h, int w) {
+    handover_fwd_walk<VEC, false>(GivenCell{h_prev, h_new}, a, nullptr, pre, up, (size_t)C * h * w, n, C, h, w);
 }
-
 // g_pre / g_up may be NULL (zero); d_a / d_h_prev / d_h_new may be NULL (not wanted)
-__global__ __launch_bounds__(LSTM_BLOCK) void lstm_handover_bwd_vec_kernel(const float* __restrict__ pre, const float* __restrict__ g_pre,
-                                                                          const float* __restrict__ g_up, float* __restrict__ d_a,
-                                                                          float* __restrict__ d_h_prev, float* __restrict__ d_h_new,
-                                                                          unsigned items, int h, int w) {
-    const unsigned w4 = w >> 2, P = (unsigned)h * w;
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (unsigned it = blockIdx.x * LSTM_BLOCK + threadIdx.x; it < items; it += gridDim.x * LSTM_BLOCK) {
-        const unsigned x4 = it % w4, r = it / w4, y = r % h, bq = r / h;
-        const size_t in0 = (size_t)bq * 4 * P + (size_t)y * w + 4 * x4;
-        float4 gu[4] = {zero, zero, zero, zero};                                              // per channel k, pixels x..x+3
-        if (g_up) {
-            const float* u0 = g_up + (size_t)bq * 4 * P + (size_t)(2 * y) * (2 * w) + 8 * x4;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const float* row = u0 + (size_t)i * 2 * w;
-                const float4 lo = *reinterpret_cast<const float4*>(row), hi = *reinterpret_cast<const float4*>(row + 4);
-                gu[2 * i] = make_float4(lo.x, lo.z, hi.x, hi.z);
-                gu[2 * i + 1] = make_float4(lo.y, lo.w, hi.y, hi.w);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const size_t o = in0 + (size_t)k * P;
-            const float4 vp = *reinterpret_cast<const float4*>(pre + o);
-            const float4 gp = g_pre ? *reinterpret_cast<const float4*>(g_pre + o) : zero;
-            const float4 d = make_float4(handover_d(vp.x, gp.x, gu[k].x), handover_d(vp.y, gp.y, gu[k].y),
-                                         handover_d(vp.z, gp.z, gu[k].z), handover_d(vp.w, gp.w, gu[k].w));
-            const float4 half = make_float4(d.x * 0.5f, d.y * 0.5f, d.z * 0.5f, d.w * 0.5f);
-            if (d_a) *reinterpret_cast<float4*>(d_a + o) = d;
-            if (d_h_prev) *reinterpret_cast<float4*>(d_h_prev + o) = half;
-            if (d_h_new) *reinterpret_cast<float4*>(d_h_new + o) = half;
-        }
-    }
-}
+template <bool VEC>
 __global__ __launch_bounds__(LSTM_BLOCK) void lstm_handover_bwd_kernel(const float* __restrict__ pre, const float* __restrict__ g_pre,
                                                                       const float* __restrict__ g_up, float* __restrict__ d_a,
                                                                       float* __restrict__ d_h_prev, float* __restrict__ d_h_new,
-                                                                      unsigned n, int h, int w) {
-    const unsigned P = (unsigned)h * w;
-    for (unsigned e = blockIdx.x * LSTM_BLOCK + threadIdx.x; e < n; e += gridDim.x * LSTM_BLOCK) {
-        float gu = 0.f;
-        if (g_up) {
-            const unsigned x = e % w, r = e / w, y = r % h, bc = r / h, k = bc & 3, bq = bc >> 2;
-            gu = g_up[(size_t)bq * 4 * P + (size_t)(2 * y + (k >> 1)) * (2 * w) + 2 * x + (k & 1)];
-        }
-        const float d = handover_d(pre[e], g_pre ? g_pre[e] : 0.f, gu);
-        if (d_a) d_a[e] = d;
-        if (d_h_prev) d_h_prev[e] = d * 0.5f;
-        if (d_h_new) d_h_new[e] = d * 0.5f;
-    }
+                                                                      unsigned n, int C, int h, int w) {
+    handover_bwd_walk<VEC>(GivenCellBwd{d_a, d_h_prev, d_h_new}, pre, g_pre, g_up, n, C, h, w);
 }
 
 }  // namespace dc
@@ -235,37 +165,27 @@ extern "C" int dc_lstm_cell_bwd(const float* cc, const float* c_cur, const float
     return DC_OK;
 }
 
-static bool handover_ok(int B, int C, int h, int w) {
-    return B > 0 && C > 0 && (C & 3) == 0 && h > 0 && w > 0 && (size_t)B * C * h * w < (1ull << 31);
-}
+static bool handover_ok(int B, int C, int h, int w, size_t* n) { return (C & 3) == 0 && c2f_sizes(B, C, h, w, 1, n); }
 
 extern "C" int dc_lstm_handover_fwd(const float* a, const float* h_prev, const float* h_new, float* pre, float* up, int B, int C, int h,
                                     int w, void* stream) {
-    if (!a || !h_prev || !h_new || !pre || !handover_ok(B, C, h, w)) return DC_EINVAL;
-    const size_t n = (size_t)B * C * h * w;
-    if ((w & 3) == 0 && all16({a, h_prev, h_new, pre, up})) {
-        const size_t items = n >> 4;
-        hipLaunchKernelGGL(lstm_handover_fwd_vec_kernel, dim3(lstm_grid(items)), dim3(LSTM_BLOCK), 0, (hipStream_t)stream, a, h_prev, h_new,
-                           pre, up, (unsigned)items, h, w);
-    } else {
-        hipLaunchKernelGGL(lstm_handover_fwd_kernel, dim3(lstm_grid(n)), dim3(LSTM_BLOCK), 0, (hipStream_t)stream, a, h_prev, h_new, pre, up,
-                           (unsigned)n, h, w);
-    }
+    size_t n;
+    if (!a || !h_prev || !h_new || !pre || !handover_ok(B, C, h, w, &n)) return DC_EINVAL;
+    const bool vec = c2f_vec(C, w, up, (size_t)C * h * w, {a, h_prev, h_new, pre, up});
+    const C2fLaunch l = c2f_launch(vec, n);
+    hipLaunchKernelGGL(vec ? lstm_handover_fwd_kernel<true> : lstm_handover_fwd_kernel<false>, dim3(l.grid), dim3(LSTM_BLOCK), 0,
+                       (hipStream_t)stream, a, h_prev, h_new, pre, up, l.count, C, h, w);
     DC_CHECK_LAUNCH();
     return DC_OK;
 }
 extern "C" int dc_lstm_handover_bwd(const float* pre, const float* g_pre, const float* g_up, float* d_a, float* d_h_prev, float* d_h_new,
                                     int B, int C, int h, int w, void* stream) {
-    if (!pre || (!d_a && !d_h_prev && !d_h_new) || !handover_ok(B, C, h, w)) return DC_EINVAL;
-    const size_t n = (size_t)B * C * h * w;
-    if ((w & 3) == 0 && all16({pre, g_pre, g_up, d_a, d_h_prev, d_h_new})) {
-        const size_t items = n >> 4;
-        hipLaunchKernelGGL(lstm_handover_bwd_vec_kernel, dim3(lstm_grid(items)), dim3(LSTM_BLOCK), 0, (hipStream_t)stream, pre, g_pre, g_up,
-                           d_a, d_h_prev, d_h_new, (unsigned)items, h, w);
-    } else {
-        hipLaunchKernelGGL(lstm_handover_bwd_kernel, dim3(lstm_grid(n)), dim3(LSTM_BLOCK), 0, (hipStream_t)stream, pre, g_pre, g_up, d_a,
-                           d_h_prev, d_h_new, (unsigned)n, h, w);
-    }
+    size_t n;
+    if (!pre || (!d_a && !d_h_prev && !d_h_new) || !handover_ok(B, C, h, w, &n)) return DC_EINVAL;
+    const bool vec = c2f_vec(C, w, nullptr, 0, {pre, g_pre, g_up, d_a, d_h_prev, d_h_new});
+    const C2fLaunch l = c2f_launch(vec, n);
+    hipLaunchKernelGGL(vec ? lstm_handover_bwd_kernel<true> : lstm_handover_bwd_kernel<false>, dim3(l.grid), dim3(LSTM_BLOCK), 0,
+                       (hipStream_t)stream, pre, g_pre, g_up, d_a, d_h_prev, d_h_new, l.count, C, h, w);
     DC_CHECK_LAUNCH();
     return DC_OK;
 }

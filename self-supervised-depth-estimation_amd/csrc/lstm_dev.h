@@ -1,6 +1,7 @@
 // The per-element expressions of the ConvLSTM v8 passes and their launch shape, stated once for the training forms (lstm.hip),
-// the inference step (lstm_infer.hip) and the ConvGRU v10 hand-over, which shares the hand-over's item walk (gru_c2f.hip).  sigmoid and tanh are the accurate expf / tanhf (not __expf): the states are
-// carried over the frames of a sequence.
+// the inference step (lstm_infer.hip) and the ConvGRU v10 hand-over (gru_c2f.hip); the hand-over's item walk, which the three
+// share, is c2f_dev.h.  sigmoid and tanh are the accurate expf / tanhf (not __expf): the states are carried over the frames of
+// a sequence.
 #pragma once
 #include "dc_common.h"
 

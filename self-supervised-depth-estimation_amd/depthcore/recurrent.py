@@ -481,6 +481,27 @@ def _step_outputs(name, h_, B, ts):
     return (None if up_ is None else up_.data_ptr()), stride
 
 
+def _infer_step(name, inputs, mult, gate_err, states, y, r, pre, up, B):
+    """The body of lstm_infer_step and gru_c2f_infer_step: nothing reaches autograd, the shapes and rows are checked, and the entry
+    dc_<name>(*inputs, y, r, *states, pre, up, up's row stride, B, C, hh, w, stream) is called once.  inputs {label: tensor}: first
+    the gates (>= B, mult * C, hh, w) -- gate_err is their mismatch text -- then operands of >= B rows of the state's shape;
+    states {label: tensor}: h first, all (S >= B, C, hh, w), rewritten in place in their first B rows."""
+    inputs = {k: t.detach() for k, t in inputs.items()}
+    states = {k: t.detach() for k, t in states.items()}
+    ts = {k: (None if t is None else t.detach()) for k, t in dict(y=y, r=r, pre=pre, up=up).items()}
+    (gt, *rest), h_ = inputs.values(), next(iter(states.values()))
+    B = gt.shape[0] if B is None else int(B)
+    _, C, _ = _gate_dims(gt, h_, mult, lambda: gate_err % (tuple(gt.shape), tuple(h_.shape)), rows=False)
+    hh, w = h_.shape[2], h_.shape[3]
+    if any(t.shape != h_.shape for t in states.values()) or any(t.dim() != 4 or t.shape[1:] != h_.shape[1:] for t in rest) \
+            or not 1 <= B <= min(t.shape[0] for t in (gt, *rest, h_)):
+        raise DepthcoreError("%s: B = %d streams of %s" % (name, B, ", ".join(
+            "%s %s" % (k, tuple(t.shape)) for k, t in list(inputs.items()) + list(states.items()))))
+    up_ptr, stride = _step_outputs(name, h_, B, ts)
+    check(getattr(_lib.lib(), "dc_" + name)(*[ptr(t) for t in inputs.values()], ptr(ts["y"]), ptr(ts["r"]), *[ptr(t) for t in states.values()],
+                                            ptr(ts["pre"]), up_ptr, stride, B, C, hh, w, stream(h_)), "dc_" + name)
+
+
 def lstm_infer_step(cc, h, c, y=None, r=None, pre=None, up=None, B=None):
     """A v8 frame at one scale for B lockstep streams in ONE launch (dc_lstm_infer_step), no autograd:
         c' = sigmoid(f) * c + sigmoid(i) * tanh(g),  h' = sigmoid(o) * tanh(c'),  pre = relu((y + r) + (h + h') / 2),
@@ -489,18 +510,7 @@ def lstm_infer_step(cc, h, c, y=None, r=None, pre=None, up=None, B=None):
     (resConfUnit1.conv2's output, the unit's ReLU-ed input) both or neither -- neither is the state update alone; pre
     (>= B, C, hh, w) and up are written where given.  up holds (C/4, 2hh, 2w) per row and may be a channel slice of a wider
     contiguous buffer (the upper half of the next scale's cat(dec, up)): its row stride is passed down.  B: default cc's rows."""
-    ts = dict(cc=cc, h=h, c=c, y=y, r=r, pre=pre, up=up)
-    ts = {k: (None if t is None else t.detach()) for k, t in ts.items()}
-    cc_, h_, c_ = ts["cc"], ts["h"], ts["c"]
-    B = cc_.shape[0] if B is None else int(B)
-    _, C, P = _gate_dims(cc_, h_, 4, lambda: "gate pre-activations %s do not match the state %s" % (tuple(cc_.shape), tuple(h_.shape)),
-                         rows=False)
-    hh, w = h_.shape[2], h_.shape[3]
-    if c_.shape != h_.shape or not 1 <= B <= min(cc_.shape[0], h_.shape[0]):
-        raise DepthcoreError("lstm_infer_step: B = %d streams of cc %s, h %s, c %s" % (B, tuple(cc_.shape), tuple(h_.shape), tuple(c_.shape)))
-    up_ptr, stride = _step_outputs("lstm_infer_step", h_, B, ts)
-    check(_lib.lib().dc_lstm_infer_step(ptr(cc_), ptr(ts["y"]), ptr(ts["r"]), ptr(h_), ptr(c_), ptr(ts["pre"]), up_ptr, stride, B, C, hh, w,
-                                        stream(h_)), "dc_lstm_infer_step")
+    _infer_step("lstm_infer_step", dict(cc=cc), 4, "gate pre-activations %s do not match the state %s", dict(h=h, c=c), y, r, pre, up, B)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -553,15 +563,4 @@ def gru_c2f_infer_step(gates, cnm, h, y=None, r=None, pre=None, up=None, B=None)
         h' = (1 - u) * h + u * cnm,  pre = relu((y + r) + (h + h') / 2),  up = pixel_shuffle(tanh(pre), 2),  h[:B] <- h'.
     gates (B, 2C, hh, w), cnm (>= B, C, hh, w); h (S >= B, C, hh, w) the state buffer, REWRITTEN IN PLACE in its first B rows;
     y, r, pre, up as lstm_infer_step's.  B: default gates' rows."""
-    ts = dict(gates=gates, cnm=cnm, h=h, y=y, r=r, pre=pre, up=up)
-    ts = {k: (None if t is None else t.detach()) for k, t in ts.items()}
-    gt, cn, h_ = ts["gates"], ts["cnm"], ts["h"]
-    B = gt.shape[0] if B is None else int(B)
-    _, C, P = _gate_dims(gt, h_, 2, lambda: "gates %s do not match the state %s" % (tuple(gt.shape), tuple(h_.shape)), rows=False)
-    hh, w = h_.shape[2], h_.shape[3]
-    if cn.dim() != 4 or cn.shape[1:] != h_.shape[1:] or not 1 <= B <= min(gt.shape[0], cn.shape[0], h_.shape[0]):
-        raise DepthcoreError("gru_c2f_infer_step: B = %d streams of gates %s, cnm %s, h %s" % (
-            B, tuple(gt.shape), tuple(cn.shape), tuple(h_.shape)))
-    up_ptr, stride = _step_outputs("gru_c2f_infer_step", h_, B, ts)
-    check(_lib.lib().dc_gru_c2f_infer_step(ptr(gt), ptr(cn), ptr(ts["y"]), ptr(ts["r"]), ptr(h_), ptr(ts["pre"]), up_ptr, stride, B, C, hh, w,
-                                           stream(h_)), "dc_gru_c2f_infer_step")
+    _infer_step("gru_c2f_infer_step", dict(gates=gates, cnm=cnm), 2, "gates %s do not match the state %s", dict(h=h), y, r, pre, up, B)

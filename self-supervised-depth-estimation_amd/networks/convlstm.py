@@ -94,45 +94,46 @@ class FeatureFusionBlock_v2(nn.Module):
         return self.fuse(input_1, input_2, input_2)             # (x + x) / 2 is x bit for bit; its two half gradients sum to d
 
 
-class ConvGRUBlocks_v8(nn.Module):
-    """networks/rnn.py:371-469.  The reference hard-codes the 192 x 640 map sizes and the decoder's channel counts; `height` /
-    `width` / `num_ch_dec` reproduce those numbers by default and let other input sizes be built, as ConvGRUBlocks_v5 does."""
+class CoarseToFineBlocks(nn.Module):
+    """The arrangement that ConvGRUBlocks_v8 (rnn.py:371-469) and ConvGRUBlocks_v9 (:472-569, networks/convgru_c2f.py) share:
+    per scale a recurrent model `cgru_{s}` with its learned initial state(s) and a FeatureFusionBlock_v2 `fusion_{s}`, walked
+    coarse to fine with the pixel-shuffled hand-over of a scale concatenated to the decoder map of the next finer one.  A
+    subclass names its cell model and gives
+        initial_states()                  -> [state of scale s for s = 0..3]
+        _scale(s, x, input_1, state)      -> (new state, disparity, up or None)      one scale of a frame
+    The reference hard-codes the 192 x 640 map sizes and the decoder's channel counts; `height` / `width` / `num_ch_dec`
+    reproduce those numbers by default and let other input sizes be built, as ConvGRUBlocks_v5 does."""
 
-    def __init__(self, kernel_size, bias, device, attention=False, height=192, width=640, num_ch_dec=(16, 32, 64, 128)):
+    def __init__(self, cell_model, refusal, kernel_size, bias, device, attention, height, width, num_ch_dec):
+        """cell_model(dims, kernel_size, bias, device): a scale's recurrent model; refusal: the text for attention=True."""
         super().__init__()
         if attention:
-            raise NotImplementedError("ConvGRUBlocks_v8(attention=True): the attention variant is not built "
-                                      "(trainer_gru.py:141-144 passes attention=False)")
+            raise NotImplementedError(refusal)
         ch = [int(c) for c in num_ch_dec]
         for s in range(4):
             # scale 3 has no upscaled hand-over to concatenate: input 128, hidden 256; below it input = hidden = 2 * num_ch_dec[s]
             dims = {"input_dim": ch[3] if s == 3 else 2 * ch[s], "hidden_dim_1": 2 * ch[s], "height": height >> s, "width": width >> s}
-            setattr(self, "cgru_%d" % s, ConvLSTMModel_v1(dims, kernel_size, bias, device))
+            setattr(self, "cgru_%d" % s, cell_model(dims, kernel_size, bias, device))
         for s in range(4):
             setattr(self, "fusion_%d" % s, FeatureFusionBlock_v2(2 * ch[s], up=(s != 0), attention=False))
 
     def cells(self):
         return [getattr(self, "cgru_%d" % s) for s in range(4)]
 
-    def initial_states(self):
-        return [(cell.h0_layer1, cell.c0_layer1) for cell in self.cells()]
-
     def forward(self, dec_outputs, hidden_states):
-        """One frame: dec_outputs[("disp", s)] the decoder's pre_disp map of scale s, hidden_states[s] = (h, c).  Returns
-        ([(h', c') for s = 0..3], {("disp", s): disparity})."""
+        """One frame: dec_outputs[("disp", s)] the decoder's pre_disp map of scale s, hidden_states[s] the state of scale s as
+        initial_states() gives it.  Returns ([new state for s = 0..3], {("disp", s): disparity})."""
         new, disp, up = [None] * 4, {}, None
         for s in (3, 2, 1, 0):
             dec = dec_outputs[("disp", s)]
             x = dec if s == 3 else torch.cat([dec, up], 1)
-            h_prev = hidden_states[s][0]
-            new[s] = getattr(self, "cgru_%d" % s)(x, hidden_states[s])
-            out = getattr(self, "fusion_%d" % s).fuse(torch.cat([dec, dec], 1) if s == 3 else x, h_prev, new[s][0])
-            disp[("disp", s)], up = out if s else (out, None)
+            new[s], disp[("disp", s)], up = self._scale(s, x, torch.cat([dec, dec], 1) if s == 3 else x, hidden_states[s])
         return new, disp
 
     def run_sequence(self, dec_outputs):
-        """trainer_gru.py:437-460 for batch_size 1: dec_outputs[("disp", s)] (n, C_s, h_s, w_s) holds the decoder maps of the n
-        frames of one sequence; the frames are walked in order from the learned (h0, c0); returns {("disp", s): (n, 1, h_s, w_s)}."""
+        """trainer_gru.py:437-460 / :747-763 for batch_size 1: dec_outputs[("disp", s)] (n, C_s, h_s, w_s) holds the decoder maps
+        of the n frames of one sequence; the frames are walked in order from the learned initial states; returns
+        {("disp", s): (n, 1, h_s, w_s)}."""
         n = dec_outputs[("disp", 0)].shape[0]
         states = self.initial_states()
         outs = {s: [] for s in range(4)}
@@ -141,3 +142,19 @@ class ConvGRUBlocks_v8(nn.Module):
             for s in range(4):
                 outs[s].append(disp[("disp", s)])
         return {("disp", s): torch.cat(outs[s], 0) for s in range(4)}
+
+
+class ConvGRUBlocks_v8(CoarseToFineBlocks):
+    """networks/rnn.py:371-469: ConvLSTM cells, a scale's state is (h, c)."""
+
+    def __init__(self, kernel_size, bias, device, attention=False, height=192, width=640, num_ch_dec=(16, 32, 64, 128)):
+        super().__init__(ConvLSTMModel_v1, "ConvGRUBlocks_v8(attention=True): the attention variant is not built "
+                         "(trainer_gru.py:141-144 passes attention=False)", kernel_size, bias, device, attention, height, width, num_ch_dec)
+
+    def initial_states(self):
+        return [(cell.h0_layer1, cell.c0_layer1) for cell in self.cells()]
+
+    def _scale(self, s, x, input_1, state):
+        new = getattr(self, "cgru_%d" % s)(x, state)
+        out = getattr(self, "fusion_%d" % s).fuse(input_1, state[0], new[0])
+        return (new,) + (out if s else (out, None))

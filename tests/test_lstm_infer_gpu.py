@@ -81,6 +81,20 @@ def test_kernel_vs_fp64(shape):
         assert torch.equal(a[k], b[k]), k                                    # two runs from the same inputs: the same bits
 
 
+def test_the_step_is_the_training_launches_bit_for_bit():
+    """The same expressions in the same order: h', c', pre and up of the step are those of ops.lstm_cell followed by
+    ops.lstm_handover on a = y + r."""
+    from depthcore import ops
+    for shape in ((1, 8, 9, 68), (2, 4, 3, 5)):
+        t = _inputs(*shape, 550)
+        got = _run(t)
+        d = {k: v.to(DEV) for k, v in t.items()}
+        hn, cn = ops.lstm_cell(d["cc"], d["c"])
+        pre, up = ops.lstm_handover(d["y"] + d["r"], d["h"], hn)
+        assert torch.equal(got["h"], hn) and torch.equal(got["c"], cn)
+        assert torch.equal(got["pre"], pre) and torch.equal(got["up"], up)
+
+
 @pytest.mark.parametrize("shape", [(2, 8, 2, 4), (2, 4, 3, 5)])             # float4, scalar
 def test_rows_behind_B_are_not_touched(shape):
     B, C, hh, w = shape
